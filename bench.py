@@ -1,6 +1,6 @@
 """bench.py - NGCF 3-layer forward on MI355X: propagated edges/s + roofline of the SpMM kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,6 +15,11 @@ is not part of the step at this width: the reference itself raises for embed_siz
 Unit of work: one stored nonzero of L processed in one layer; value = n_layers * nnz(L) * steps / time.
 N > 1: the SAME graph is row-partitioned over the ranks (strong scaling), exchange scheme `--exchange`, rows moved by the
 CU-free p2p exchange (copy engines; NGCF_DIST_COLLECTIVES=torch: RCCL collectives) - DESIGN.md 6.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line.  Everything else - the secondary
+measurements (other workloads, widths, exchange schemes and dropout modes, the transport cross-check) and the CPU baseline
+with its parity spot check against the oracle - runs only with --full (and there --no-secondary / --no-cpu-baseline
+leave parts of it out).  --dump-outputs DIR writes what the last timed step computed as float32 .npy files (dump_outputs).
 
 Prints ONE JSON line on rank 0.
 """
@@ -66,16 +71,23 @@ def parse():
                          "sums reduce-scattered to their owners, all-gather of the owned items' carry rows per layer; allgather: the "
                          "literal scheme of BASELINE config 4 (all-gather of every rank's user and item carry rows per layer, 10x the "
                          "bytes).  The other one is timed as a labelled secondary field of the same line")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (other exchange "
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements (other exchange "
                     "scheme at N > 1; the reference-legal 130-wide first layer through model.forward() at N = 1)")
     ap.add_argument("--seg-len", type=int, default=0, help="override the row-segment length (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and its parity check)")
     ap.add_argument("--uniform-items", action="store_true", help="secondary line: no popularity skew")
     ap.add_argument("--hipgraph", action="store_true", help="Seoul-sized workloads: replay the forward as a hipGraph")
     ap.add_argument("--dropout-mode", default="reference", choices=["reference", "device"],
                     help="c1_train: where the dropout masks come from (NGCF.node_dropout_mode / mess_dropout_mode); the other "
                          "mode is timed as a labelled secondary field")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements and the CPU baseline with its "
+                    "parity spot check (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    args.secondary = args.full and not args.no_secondary
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    return args
 
 
 def host_cores():
@@ -203,13 +215,17 @@ def seoul_train_setup(pkg, dev, batch, mode, seed=1801, graphed=False, auto_grap
            for k, hi in (("u_id", nu), ("pos_item", ni), ("neg_item", ni), ("age", 76), ("sex", 2), ("month", 13), ("day", 32), ("dow", 7))}
     ids["year"] = torch.full((batch,), 18, device=dev)
 
+    last = {}
+
     def step():
         u, p, n = model(node_flag=True, **ids)
+        last["upn"] = (u, p, n)
         opt.zero_grad()
         loss = crit(u, p, n)
         loss.backward()
         opt.step()
         return loss
+    step.last = last
     if graphed:        # the same step captured once and replayed (opt-in: seoul_tourism_recommendation_ngcf_amd.GraphedTrainStep)
         gts = pkg.GraphedTrainStep(model, crit, opt, ids, node_flag=True)
         return model, (lambda: gts(**ids)), slices[0], ids
@@ -217,7 +233,8 @@ def seoul_train_setup(pkg, dev, batch, mode, seed=1801, graphed=False, auto_grap
 
 
 def time_train_steps(step, steps, warmup):
-    """(ms per step wall clock with a sync on both sides, ms per step the host spent issuing it - i.e. without the final wait).
+    """(ms per step wall clock with a sync on both sides, ms per step the host spent issuing it - i.e. without the final wait,
+    the last step's loss tensor).
     r04: the median of up to five blocks (each at least 10 steps) with the garbage collector off inside a block - one host-side
     stall inside a single block of a launch-bound step is worth tenths of a millisecond per step."""
     import gc
@@ -226,12 +243,12 @@ def time_train_steps(step, steps, warmup):
         loss = step()
     torch.cuda.synchronize()
     n_blocks = max(1, min(5, steps // 10))
-    per_block = steps // n_blocks
+    sizes = [steps // n_blocks + (1 if b < steps % n_blocks else 0) for b in range(n_blocks)]     # exactly `steps` in all
     was = gc.isenabled()
     gc.disable()
     wall, issue = [], []
     try:
-        for _ in range(n_blocks):
+        for per_block in sizes:
             t0 = time.perf_counter()
             for _ in range(per_block):
                 loss = step()
@@ -244,7 +261,7 @@ def time_train_steps(step, steps, warmup):
             gc.enable()
     assert torch.isfinite(loss).item(), "non-finite loss"
     mid = sorted(range(n_blocks), key=lambda i: wall[i])[n_blocks // 2]
-    return wall[mid], issue[mid], float(loss)
+    return wall[mid], issue[mid], loss
 
 
 def cpu_train_baseline(coo_slices_cpu, n_user, model, ids, batch, n_threads, steps=5):
@@ -291,7 +308,7 @@ def train_secondary(pkg, dev, batch, mode, steps=30, warmup=5, graphed=False, au
     ms, ms_issue, loss = time_train_steps(step, steps, warmup)
     n_layer = len(TRAIN_CFG["layers"])
     return {"ms_per_step": ms, "host_issue_ms_per_step": ms_issue, "value": n_layer * coo["nnz"] / (ms * 1e-3), "unit": "edges/s",
-            "loss": loss, "steps": steps, "dropout_mode": mode, "hipgraph": bool(graphed),
+            "loss": float(loss), "steps": steps, "dropout_mode": mode, "hipgraph": bool(graphed),
             "model_mode": "eval (experiment.py:61,72: the loop's steady state from epoch 2 on; message dropout off, node dropout on)" if eval_mode else "train",
             "forward_backward_graphs": bool(auto_graph and mode == "device" and not graphed and len(model._train_graphs) > 0),
             "note": f"main.py:63-76 / experiment.py:45-58 on the Seoul-shaped stand-in: embed {TRAIN_CFG['embed']} -> {list(TRAIN_CFG['layers'])}, "
@@ -305,6 +322,8 @@ def main_train(args, pkg, dev):
     mode = args.dropout_mode
     model, step, coo, ids = seoul_train_setup(pkg, dev, args.batch, mode)
     ms, ms_issue, loss = time_train_steps(step, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, step.last["upn"], model)
     n_layer = len(TRAIN_CFG["layers"])
     out = {
         "metric": "NGCF 3-layer forward: propagated edges/sec + achieved HBM GB/s, d=128",
@@ -321,9 +340,9 @@ def main_train(args, pkg, dev):
         "roofline": {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
                      "note": "launch-bound: the working set (E 1.5 MB, CSR 7 MB) is cache-resident and a step is ~100 launches of a few "
                              "microseconds; an HBM fraction is not meaningful here (SURVEY 8d)"},
-        "loss": loss,
+        "loss": float(loss),
     }
-    if not args.no_secondary:
+    if args.secondary:
         other = "device" if mode == "reference" else "reference"
         try:
             out["secondary"] = {f"dropout_mode_{other}": train_secondary(pkg, dev, args.batch, other, args.steps, args.warmup)}
@@ -337,7 +356,7 @@ def main_train(args, pkg, dev):
             out["secondary"]["device_masks_hipgraph"] = train_secondary(pkg, dev, args.batch, "device", max(args.steps, 100), 10, graphed=True)
         except Exception as exc:  # noqa: BLE001
             out["secondary"]["device_masks_hipgraph"] = {"error": repr(exc)[:300]}
-    if not args.no_cpu_baseline:
+    if args.cpu_baseline:
         N = coo["n_user"] + coo["n_item"]
         L = torch.sparse_coo_tensor(torch.stack([coo["rows"], coo["cols"]]).cpu(), coo["vals"].cpu(), (N, N))
         torch.manual_seed(1801)
@@ -403,8 +422,11 @@ def c3_train_measure(pkg, lib, dev, lap, n_user, n_item, nnz, batch, steps, warm
            for k, hi in (("u_id", n_user), ("pos_item", n_item), ("neg_item", n_item), ("age", 76), ("sex", 2), ("month", 13), ("day", 32), ("dow", 7))}
     ids["year"] = torch.full((batch,), 18, device=dev)
 
+    last = {}
+
     def step():
         u, p, n = model(node_flag=True, **ids)
+        last["upn"] = (u, p, n)
         opt.zero_grad()
         loss = crit(u, p, n)
         loss.backward()
@@ -430,7 +452,8 @@ def c3_train_measure(pkg, lib, dev, lap, n_user, n_item, nnz, batch, steps, warm
             "spmm_products_timed": int(n_l.value), "spmm_products_per_step": n_l.value / max(steps, 1),
             "mean_spmm_product_ms": tot.value / max(n_l.value, 1),
             "spmm_model_a_bytes": {str(d): spmm_model_a_bytes(csr.nnz, N, N, d) for d in sorted({d0, *layers})},
-            "peak_memory_GiB": torch.cuda.max_memory_allocated() / 2 ** 30, "adam_fused": fused, "model": model, "ids": ids, "d0": d0, "layers": list(layers),
+            "peak_memory_GiB": torch.cuda.max_memory_allocated() / 2 ** 30, "adam_fused": fused, "model": model, "ids": ids, "upn": last["upn"],
+            "loss_tensor": loss, "d0": d0, "layers": list(layers),
             "note": f"experiment.py:45-58 at scale: embed {d0} -> {list(layers)}, node dropout {c['node_dropout']} + message dropout "
                     f"{list(c['mess_dropout'])} (device masks), batch {batch}, Adam lr {c['lr']}, BPR wd {c['wd']}, node_flag=True, train mode; "
                     "step = forward + BPR + backward + Adam.step; the products timed are the full SpMMs of the step (3 forward L.E + the "
@@ -466,7 +489,9 @@ def main_c3_train(args, pkg, lib, dev):
     coo = pkg.graphs.synthetic_bipartite(n_user, n_item, n_inter, seed=seed, device=dev, item_skew=not args.uniform_items)
     lap = pkg.graphs.to_sparse_coo(coo)
     r = c3_train_measure(pkg, lib, dev, lap, n_user, n_item, coo["nnz"], args.batch, args.steps, args.warmup, seed)
-    model, ids = r.pop("model"), r.pop("ids")
+    model, ids, upn, loss_t = r.pop("model"), r.pop("ids"), r.pop("upn"), r.pop("loss_tensor")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss_t, upn, model)
     a = r["spmm_model_a_bytes"]
     per_product = (a[str(d0)] + 2 * a[str(layers[0])]) / 3            # the forward's three products (130, 128, 128 wide); the backward's are 128 wide
     achieved = per_product / (r["mean_spmm_product_ms"] * 1e-3) / 1e9
@@ -488,7 +513,7 @@ def main_c3_train(args, pkg, lib, dev):
         "train": {k: v for k, v in r.items() if k not in ("value", "unit")},
         "loss": r["loss"],
     }
-    if not args.no_cpu_baseline:
+    if args.cpu_baseline:
         dt, closs = cpu_c3_train_sample(lap.cpu(), model, ids, n_user, args.batch, host_cores())
         out["cpu_baseline"] = {"value": coo["nnz"] / dt, "unit": "edges/s", "cores": host_cores(), "kind": "port", "cpu_model": cpu_model(),
                                "seconds": dt, "loss": closs,
@@ -499,6 +524,41 @@ def main_c3_train(args, pkg, lib, dev):
     else:
         out["cpu_baseline"] = None
     print(json.dumps(out), flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # --dump-outputs: the .npy payload of one run, in all
+DUMP_SEED = 4099
+
+
+def dump_outputs(out_dir, loss, upn, model=None):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files in out_dir - loss.npy (the BPR loss, shape [1]),
+    u_emb / pos_emb / neg_emb.npy (the three gathered row sets BPR consumed, [batch, W]) and, when the step leaves all_E on this
+    device, all_users_emb / all_items_emb.npy: a fixed sample of all_E's user and item rows (drawn by a generator seeded with
+    DUMP_SEED, so the same rows on every run with the same arguments; sorted; at most 4096 per table).  Rows are sampled only
+    where the whole set would not fit DUMP_BUDGET_BYTES."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+
+    def rows(t, cap):
+        t = t.detach()
+        if t.shape[0] <= cap:
+            return t
+        pick = torch.randperm(t.shape[0], generator=g)[:cap].sort().values
+        return t[pick.to(t.device)]
+    tables = []
+    if model is not None and model.all_users_emb is not None:
+        tables = [("all_users_emb", model.all_users_emb), ("all_items_emb", model.all_items_emb)]
+    arrays = {"loss": loss.detach().reshape(1)}
+    left = DUMP_BUDGET_BYTES - 4
+    share = left // 2 if tables else left
+    for name, t in zip(("u_emb", "pos_emb", "neg_emb"), upn):
+        arrays[name] = rows(t, max(1, share // 3 // max(1, t.shape[-1] * 4)))
+    left -= sum(a.numel() * 4 for a in arrays.values())
+    for name, t in tables:
+        arrays[name] = rows(t, min(4096, max(1, left // len(tables) // (t.shape[1] * 4))))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
 
 
 def edges_per_step_of(n_layer, nnz):
@@ -598,6 +658,7 @@ def main():
     pos = torch.randint(0, n_item, (args.batch,), generator=g).to(dev)
     neg = torch.randint(0, n_item, (args.batch,), generator=g).to(dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
+    last = {}                                                 # the last step's gathered rows (--dump-outputs)
 
     if full_forward:
         csr = model.laplacian_csr(0)
@@ -618,6 +679,7 @@ def main():
                 u, p, n = fwd.replay()
             else:
                 u, p, n = model(year=year, u_id=u_id, pos_item=pos, neg_item=neg, node_flag=False, **feats)
+            last["upn"] = (u, p, n)
             return crit(u, p, n)
     elif world == 1:
         csr = model.laplacian_csr(0)
@@ -631,6 +693,7 @@ def main():
             u = pkg.engine.gather_rows(model.all_users_emb, u_id, status)
             p = pkg.engine.gather_rows(model.all_items_emb, pos, status)
             n = pkg.engine.gather_rows(model.all_items_emb, neg, status)
+            last["upn"] = (u, p, n)
             return crit(u, p, n)
     else:
         note("interactions drawn")
@@ -642,6 +705,7 @@ def main():
         def step():
             sh.propagate()
             u, p, n = sh.gather(u_id, pos, neg)
+            last["upn"] = (u, p, n)
             return crit(u, p, n)
 
     def barrier():
@@ -694,6 +758,8 @@ def main():
     torch.set_grad_enabled(False)                             # the metric is the forward pass (inference path)
     dt, loss, n_launch, spmm_ms = timed(step, True)
     headline_host = list(host_issue)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last["upn"], model if world == 1 else None)
     note(f"headline timed: {dt / args.steps * 1e3:.3f} ms per step")
     n_layer = len(layers)
 
@@ -769,7 +835,7 @@ def main():
     # collective that never completes would otherwise hold every rank until the process group's timeout aborts the job.  A
     # watchdog prints the finished headline and ends the process if the secondaries overrun their budget.
     watchdog = None
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.secondary:
         import threading
         budget = float(os.environ.get("NGCF_BENCH_SECONDARY_TIMEOUT_S", "240"))
         fallback = build_line(dt, loss, n_launch, spmm_ms, sh, spmm_shapes, local_nnz)
@@ -792,7 +858,7 @@ def main():
         watchdog.daemon = True
         watchdog.start()
     transport_check = None
-    if world > 1 and sh.backend == "p2p" and not args.no_secondary:
+    if world > 1 and sh.backend == "p2p" and args.secondary:
         # The same scheme over torch.distributed collectives (RCCL), timed the same way: a cross-check of the p2p transport's
         # RESULT (the two losses must agree) and its price tag.  `value` is the p2p run unless the losses disagree - then the
         # RCCL run is the headline and the line says so.
@@ -817,7 +883,7 @@ def main():
             transport_check = {"p2p": {"ms_per_step": dt / args.steps * 1e3, "loss": float(loss)}, "torch_rccl": {"error": repr(exc)[:300]}}
 
     secondary = {}
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.secondary:
         other = "bipartite" if args.exchange == "allgather" else "allgather"
         try:       # the headline must not depend on the secondary measurement
             sh2 = ngcf_dist.ShardedPropagation.from_interactions(model, *inter, mode=other, device=dev)
@@ -833,7 +899,7 @@ def main():
             del sh2
         except Exception as exc:  # noqa: BLE001
             secondary[f"exchange_{other}"] = {"error": repr(exc)[:300]}
-    if world == 1 and not seoul and not args.no_secondary and d0 % 5 != 0:
+    if world == 1 and not seoul and args.secondary and d0 % 5 != 0:
         try:       # the headline must not depend on the secondary measurement
             # the widths the reference can actually run (embed_size must be a multiple of 5, NGCF.py:39-43,114): same graph,
             # embed_size = 5*ceil(d0/5) -> [d0]*n, through the whole model.forward() including the feature injection
@@ -858,7 +924,7 @@ def main():
         except Exception as exc:  # noqa: BLE001
             secondary["reference_legal_width"] = {"error": repr(exc)[:300]}
 
-    if world == 1 and not seoul and not args.no_secondary:
+    if world == 1 and not seoul and args.secondary:
         # BASELINE configs 0-1 (Seoul-shaped stand-in graph, 2 layers, d = 64 / 512): the whole NGCF.forward incl. the feature
         # injection + BPR, replayed as a hipGraph - launch-bound sizes, reported beside the headline
         for wl in ("c1", "c2"):
@@ -891,7 +957,7 @@ def main():
             except Exception as exc:  # noqa: BLE001
                 secondary[f"{wl}_seoul_shaped_hipgraph"] = {"error": repr(exc)[:300]}
 
-    if world == 1 and not seoul and not args.no_secondary:
+    if world == 1 and not seoul and args.secondary:
         # the reference's own training step (main.py:63-76, experiment.py:45-58) on the Seoul-shaped stand-in, in both dropout modes
         torch.set_grad_enabled(True)
         for mode in ("reference", "device"):
@@ -910,7 +976,7 @@ def main():
         if args.workload == "c3":
             try:   # the training step at scale on the headline's own graph (own line: --workload c3_train)
                 r3 = c3_train_measure(pkg, lib, dev, lap, n_user, n_item, nnz, args.batch, steps=5, warmup=2, seed=seed)
-                r3.pop("model"), r3.pop("ids")
+                r3.pop("model"), r3.pop("ids"), r3.pop("upn"), r3.pop("loss_tensor")
                 secondary["c3_train_device_masks"] = r3
             except Exception as exc:  # noqa: BLE001
                 secondary["c3_train_device_masks"] = {"error": repr(exc)[:300]}
@@ -923,9 +989,9 @@ def main():
         out["secondary"] = secondary
     if seoul:
         out["roofline"]["note"] = "working set is cache-resident at this size: the HBM fraction is not meaningful (SURVEY 8d)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and seoul:
+    if rank == 0 and world == 1 and args.cpu_baseline and seoul:
         out["cpu_baseline"] = cpu_baseline_full(coo, model, host_cores(), seed)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif rank == 0 and world == 1 and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(coo, model, host_cores(), seed)
     elif rank == 0:
         out["cpu_baseline"] = None

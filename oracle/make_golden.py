@@ -1,6 +1,7 @@
 """Generate tests/golden/*.npz by IMPORTING the reference (build container only).
 
 Run:  python oracle/make_golden.py            (needs /root/reference; CPU only)
+      python oracle/make_golden.py checkpoints    (only tests/golden/reference_checkpoints.npz)
 
 The reference's Python never enters this repository: this script imports
 `/root/reference/model/{NGCF,bprloss,matrix}.py`, drives them on small seeded inputs and
@@ -17,8 +18,15 @@ import os
 import sys
 import warnings
 
-import numpy as np
-import torch
+# torch's CPU BLAS (MKL) picks its kernels by CPU vendor, ISA and thread count, and their last bits differ (an Intel and an
+# AMD host disagree on three of the forward cases by default).  The fixtures are captured in MKL's vendor-neutral
+# COMPATIBLE mode on one thread, which every host reproduces; tests/conftest.py and tests/test_oracle_golden.py do the same.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+torch.set_num_threads(1)
 
 sys.dont_write_bytecode = True
 REF = "/root/reference/model"
@@ -219,6 +227,24 @@ def run_matrix_case():
     print("  wrote matrix")
 
 
+def run_checkpoint_case():
+    """The structure of the 23 checkpoints shipped with the reference (saved_model_data/, saved_data_layer2/): per file the
+    state-dict names in order, their shapes and dtypes, and the last layer's w2 bias - what tests/test_reference_checkpoints.py
+    checks the mirror module against.  The weights themselves (1.6 MB a file) are not stored."""
+    import glob
+    paths = sorted(glob.glob(os.path.join(REF, "saved_model_data", "*.pth")) + glob.glob(os.path.join(REF, "saved_data_layer2", "*.pth")))
+    out = {"files": np.asarray([os.path.relpath(p, REF) for p in paths])}
+    for i, p in enumerate(paths):
+        sd = torch.load(p, weights_only=True, map_location="cpu")
+        n_layer = sum(1 for k in sd if k.startswith("w1_list.") and k.endswith(".weight"))
+        out[f"c{i}_names"] = np.asarray(list(sd.keys()))
+        out[f"c{i}_shapes"] = np.asarray([list(v.shape) + [-1] * (2 - v.dim()) for v in sd.values()], dtype=np.int64)
+        out[f"c{i}_dtypes"] = np.asarray([str(v.dtype).replace("torch.", "") for v in sd.values()])
+        out[f"c{i}_last_bias"] = sd[f"w2_list.{n_layer - 1}.bias"].numpy()
+    np.savez_compressed(os.path.join(OUT, "reference_checkpoints.npz"), **out)
+    print(f"  wrote reference_checkpoints ({len(paths)} files)")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     print("generating golden vectors with torch", torch.__version__, "numpy", np.__version__)
@@ -239,9 +265,10 @@ def main():
                      neg_empty=False, dup_users=False, heavy=[4], train=True)
     run_bpr_cases()
     run_matrix_case()
+    run_checkpoint_case()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print(f"total fixture bytes: {tot}")
 
 
 if __name__ == "__main__":
-    main()
+    run_checkpoint_case() if sys.argv[1:] == ["checkpoints"] else main()

@@ -1,8 +1,13 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# torch's CPU BLAS (MKL) picks its kernels by CPU vendor, ISA and thread count, with different last bits; the golden vectors
+# were captured in MKL's vendor-neutral COMPATIBLE mode (oracle/make_golden.py), which every host reproduces.  Must be set
+# before torch first calls MKL.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")

@@ -11,6 +11,16 @@ from conftest import FWD_CASES, load_golden
 from golden_util import batch_of, lap_list_of, layer_params, sd_of
 
 
+@pytest.fixture(autouse=True)
+def one_thread():
+    """MKL's GEMM splits its work by thread count, and the last bits follow: the vectors were captured on one thread
+    (oracle/make_golden.py), so the bit-exact comparisons run on one thread too."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(n)
+
+
 def _feats(sd):
     return {"age": sd["age_emb.weight"], "sex": sd["sex_emb.weight"], "month": sd["month_emb.weight"],
             "day": sd["day_emb.weight"], "dow": sd["dow_emb.weight"]}
