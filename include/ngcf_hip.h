@@ -43,7 +43,7 @@ const char *ngcf_last_error(void);
 const char *ngcf_target_arch(void);
 /* ABI version of this header.  ngcf_version() returns the value the library was built with; the Python mirror refuses to bind
  * a library whose version differs (a stale .so would otherwise receive shifted arguments). */
-#define NGCF_ABI_VERSION 7
+#define NGCF_ABI_VERSION 8
 int ngcf_version(void);
 
 /* Tunables of the kernel dispatch (thresholds, lab switches).  The library reads its NGCF_* environment variables ONCE, in
@@ -358,6 +358,33 @@ int ngcf_topk_rows_f32(const float *scores, int64_t ld, int64_t n_rows, int64_t 
  * memory that receives the score matrix (it is what `torch.mm` would have returned), out_val [B, k], out_idx [B, k] int64. */
 int ngcf_recommend_topk_f32(const float *u, int64_t ldu, int64_t B, const float *items, int64_t ldi, int64_t n_items,
                             int D, int k, float *scratch, int64_t ld_scratch, float *out_val, int64_t *out_idx, void *stream);
+
+/* ---- full-catalogue ranking and held-out metrics (the NGCF evaluation protocol) ---- */
+/* Score-and-select with no score matrix: batch row b ranks user r = user_ids ? user_ids[b] : b (embedding users[r*ldu + 0..D))
+ * against every item, score(b, i) = sum_k users[r,k]*items[i,k] as one ascending-k fmaf chain from 0 (fp32 MFMA; the same bits as
+ * ngcf_recommend_topk_f32), and writes the k best: values descending, equal values lowest item first, NaN above +inf.
+ * Exclusion (excl_rowptr may be NULL): items excl_colidx[excl_rowptr[r] .. excl_rowptr[r+1]) - excl_col_offset never appear;
+ * ids ascending within a row, duplicates allowed, ids outside [0, n_items) ignored.  With excl_col_offset = n_user the user rows
+ * of the model's Laplacian CSR serve as the exclusion set.  Fewer than k eligible items: the trailing slots are (-inf, -1).
+ * An r outside [0, n_user_rows) sets *status and leaves its output row untouched (ngcf_gather_rows_f32's rule).
+ * 1 <= k <= min(n_items, 256) (larger k: ngcf_recommend_topk_f32); any D >= 1; n_items < 2^31.  Deterministic, no float atomics:
+ * the row of a user does not depend on B, on the batch order or on the item split.  The workspace (ngcf_rank_workspace_bytes,
+ * 0 when none is needed) holds the per-split lists when the batch is too small to fill the chip on its own. */
+int64_t ngcf_rank_workspace_bytes(int64_t B, int64_t n_items, int D, int k);
+int ngcf_rank_topk_f32(const float *users, int64_t ldu, const int64_t *user_ids, int64_t n_user_rows, int64_t B,
+                       const float *items, int64_t ldi, int64_t n_items, int D, int k,
+                       const int64_t *excl_rowptr, const int32_t *excl_colidx, int64_t excl_col_offset,
+                       float *out_val, int64_t *out_idx, int32_t *status,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+/* Held-out metrics of top lists top_idx [B, k] (entries of -1 ignored) against truth rows (ascending, like the exclusion rows;
+ * T = the distinct ids >= 0 after truth_col_offset).  For each cut-off K of ks_host[0..n_ks) (1 <= n_ks <= 8, K <= k), slots
+ * 4q..4q+3 are recall = hits/|T|, ndcg = sum over hit ranks j of 1/log2(j+2) / sum_{j < min(K,|T|)} 1/log2(j+2),
+ * precision = hits/K, hr = hits > 0; slot 4*n_ks counts the users with non-empty T (users with empty T add nothing).
+ * per_user [B, 4*n_ks] (may be NULL) gets the per-row values; sums (device, [4*n_ks + 1]) is ADDED to, in a fixed order
+ * (per-block partials, then one workgroup): bit-identical from run to run, and a user set can be ranked in chunks. */
+int ngcf_rank_metrics(const int64_t *top_idx, int64_t B, int k, const int64_t *user_ids, int64_t n_user_rows,
+                      const int64_t *truth_rowptr, const int32_t *truth_colidx, int64_t truth_col_offset,
+                      const int32_t *ks_host, int n_ks, float *per_user, double *sums, int32_t *status, void *stream);
 
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*

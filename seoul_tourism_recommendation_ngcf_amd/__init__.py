@@ -8,5 +8,6 @@ from .NGCF import NGCF
 from .bprloss import BPR
 from .graphed import GraphedForward, GraphedTrainStep
 from . import engine, graphs
+from . import evaluate
 
-__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs"]
+__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate"]

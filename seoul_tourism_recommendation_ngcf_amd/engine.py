@@ -481,3 +481,184 @@ def shard_plan(rowptr_host: torch.Tensor, row_begin: int, row_end: int, world: i
     bounds = (C.c_int64 * (world + 1))()
     _lib.check(lib.ngcf_shard_plan(C.cast(rp.data_ptr(), C.POINTER(C.c_int64)), row_begin, row_end, world, bounds))
     return [int(b) for b in bounds]
+
+
+# ---- full-catalogue ranking and held-out metrics (ngcf_rank_topk_f32 / ngcf_rank_metrics, csrc/rank.hip) --------------------------
+RANK_K_MAX = 256
+
+
+class ItemSets:
+    """A sorted item list per user in CSR form - the exclusion set (train items) or the truth set (held-out items) of a full
+    ranking.  `rowptr` int64 [n_rows + 1] and `colidx` int32 on the device; stored ids minus `col_offset` are item ids in
+    [0, n_items).  Ids are ascending within every row (the kernels walk them with a cursor / binary search)."""
+
+    def __init__(self, rowptr: torch.Tensor, colidx: torch.Tensor, col_offset: int, n_items: int, keep_alive=()):
+        self.rowptr, self.colidx = rowptr, colidx
+        self.col_offset, self.n_items = int(col_offset), int(n_items)
+        self.n_rows = int(rowptr.numel()) - 1
+        self._keep = keep_alive
+
+    @classmethod
+    def from_pairs(cls, users: torch.Tensor, items: torch.Tensor, n_user: int, n_item: int) -> "ItemSets":
+        """From (user, item) pairs in any order, duplicates allowed: a sort and unique on the pairs' device (set-up, not hot path)."""
+        users = users.reshape(-1).to(torch.int64)
+        items = items.reshape(-1).to(device=users.device, dtype=torch.int64)
+        if users.numel() != items.numel():
+            raise RuntimeError("ItemSets.from_pairs: users and items differ in length")
+        if users.numel() and (int(users.min()) < 0 or int(users.max()) >= n_user or int(items.min()) < 0 or int(items.max()) >= n_item):
+            raise IndexError(f"ItemSets.from_pairs: a pair lies outside {n_user} users x {n_item} items")
+        key = torch.unique(users * n_item + items)                   # sorted by (user, item), de-duplicated
+        u, i = key // n_item, key % n_item
+        rowptr = torch.zeros(n_user + 1, dtype=torch.int64, device=users.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(u, minlength=n_user), 0)
+        return cls(rowptr, i.to(torch.int32).contiguous(), 0, n_item)
+
+    @classmethod
+    def from_laplacian(cls, csr: LaplacianCSR, n_user: int) -> "ItemSets":
+        """The user rows of a model's Laplacian CSR (`model.laplacian_csr(year)`): row u holds columns n_user + item, so with
+        col_offset = n_user they are the user's training items, borrowed with no copy.  The CSR's column array is never
+        reordered after it is built (the swept plan keeps its own arrays), so the check below holds for the CSR's life."""
+        lib = _lib.load()
+        n_item = csr.n_cols - n_user
+        if csr.n_rows < n_user or n_item < 1:
+            raise RuntimeError(f"ItemSets.from_laplacian: a CSR of {csr.n_rows} x {csr.n_cols} has no {n_user} user rows")
+        rp_ptr, ci_ptr = int(lib.ngcf_csr_rowptr(csr._h) or 0), int(lib.ngcf_csr_colidx(csr._h) or 0)
+        rowptr_all = _device_view(rp_ptr, csr.n_rows + 1, torch.int64)
+        nnz_user = int(rowptr_all[n_user])
+        rowptr = rowptr_all[:n_user + 1]
+        colidx = _device_view(ci_ptr, max(nnz_user, 1), torch.int32)[:nnz_user]
+        if nnz_user > 1:
+            row_of = torch.repeat_interleave(torch.arange(n_user, device=rowptr.device), rowptr.diff())
+            same_row = row_of[1:] == row_of[:-1]
+            if bool((same_row & (colidx[1:] < colidx[:-1])).any()):
+                raise RuntimeError("ItemSets.from_laplacian: the CSR's columns are not ascending within its user rows")
+        return cls(rowptr, colidx, n_user, n_item, keep_alive=(csr,))
+
+
+class _DevView:
+    """`__cuda_array_interface__` carrier over library-owned device memory (as dist._DevMem)."""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"data": (int(ptr), False), "shape": (int(n),), "typestr": typestr, "version": 2}
+
+
+def _device_view(ptr: int, n: int, dtype) -> torch.Tensor:
+    """A torch tensor over `n` elements of library-owned device memory (no copy; the owner must outlive it)."""
+    if ptr == 0:
+        raise RuntimeError("null device pointer")
+    return torch.as_tensor(_DevView(ptr, n, {torch.int64: "<i8", torch.int32: "<i4"}[dtype]),
+                           device=torch.device("cuda", torch.cuda.current_device()))
+
+
+def _check_sets(s: "ItemSets", dev, n_user_rows: int, what: str):
+    if s.rowptr.device != dev or s.colidx.device != dev:
+        raise RuntimeError(f"{what}: the item sets live on {s.rowptr.device}, the embeddings on {dev}")
+    if s.n_rows < n_user_rows:
+        raise RuntimeError(f"{what}: {s.n_rows} rows of item sets for {n_user_rows} users")
+
+
+def rank_topk(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, user_ids: Optional[torch.Tensor] = None,
+              exclude: Optional[ItemSets] = None, status: Optional[torch.Tensor] = None):
+    """Top-k items of every item for every requested user, without a score matrix (ngcf_rank_topk_f32): fp32 MFMA scores with
+    the bits of `recommend_topk`, a streaming selection per user, the user's `exclude` items left out.  With `user_ids`, batch row b
+    ranks user_emb[user_ids[b]] (no gather); otherwise row b.  Returns (values [B, k], int64 indices [B, k]); slots past the
+    eligible items are (-inf, -1).  Strided views (rows of all_E) are taken as they are.  A user id outside the table raises
+    IndexError (one host sync); with a caller's int32 `status` word it is only flagged there and the call does not sync."""
+    lib = _lib.load()
+    _f32c(user_emb, "user_emb"), _f32c(item_emb, "item_emb")
+    if user_emb.dim() != 2 or item_emb.dim() != 2 or user_emb.shape[1] != item_emb.shape[1]:
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({tuple(user_emb.shape)} and {tuple(item_emb.t().shape)})")
+    n_rows, D, n_items = int(user_emb.shape[0]), int(user_emb.shape[1]), int(item_emb.shape[0])
+    k = int(k)
+    if k < 1 or k > n_items:
+        raise RuntimeError(f"selected index k out of range (k={k}, row length {n_items})")
+    if k > RANK_K_MAX:
+        raise RuntimeError(f"rank_topk: k={k} > {RANK_K_MAX} is not supported; recommend_topk takes k up to 1024")
+    dev = user_emb.device
+    user_emb = user_emb if user_emb.stride(1) == 1 else user_emb.contiguous()
+    item_emb = item_emb if item_emb.stride(1) == 1 else item_emb.contiguous()
+    if user_ids is not None:
+        user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        B = int(user_ids.numel())
+    else:
+        B = n_rows
+    if exclude is not None:
+        _check_sets(exclude, dev, n_rows, "rank_topk")
+        if exclude.n_items != n_items:
+            raise RuntimeError(f"rank_topk: the exclusion sets index {exclude.n_items} items, the item table has {n_items}")
+    vals = torch.empty((B, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, k), dtype=torch.int64, device=dev)
+    if B == 0:
+        return vals, idx
+    nb = int(lib.ngcf_rank_workspace_bytes(B, n_items, D, k))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    check_status = status is None
+    if check_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(lib.ngcf_rank_topk_f32(_ptr(user_emb), _row_major_ld(user_emb, "user_emb"), _ptr(user_ids), n_rows, B,
+                                          _ptr(item_emb), _row_major_ld(item_emb, "item_emb"), n_items, D, k,
+                                          _ptr(None if exclude is None else exclude.rowptr),
+                                          _ptr(None if exclude is None else exclude.colidx),
+                                          0 if exclude is None else exclude.col_offset, _ptr(vals), _ptr(idx), _ptr(status),
+                                          _ptr(ws), nb, _stream()))
+    if check_status and user_ids is not None and int(status.item()) != 0:
+        raise IndexError(f"rank_topk: a user id lies outside [0, {n_rows})")
+    return vals, idx
+
+
+def ranking_metrics(top_idx: torch.Tensor, truth: ItemSets, ks: Sequence[int], user_ids: Optional[torch.Tensor] = None,
+                    sums: Optional[torch.Tensor] = None, per_user: bool = False, status: Optional[torch.Tensor] = None):
+    """Recall / NDCG / precision / hit rate @K of top lists `top_idx` [B, k] (int64, -1 = empty slot) against `truth`
+    (ngcf_rank_metrics).  Batch row b is user user_ids[b] (or b).  Users with an empty truth row are not evaluated.
+    Returns {"recall@K": mean, "ndcg@K": ..., "precision@K": ..., "hr@K": ..., "users": n}.  With `sums` (a float64 device
+    tensor of 4*len(ks) + 1 slots) the call adds into it and returns it instead - chunks of one ranking read back once."""
+    lib = _lib.load()
+    _require_device(top_idx, "top_idx")
+    if top_idx.dim() != 2 or top_idx.dtype != torch.int64:
+        raise RuntimeError("ranking_metrics: top_idx must be a 2-D int64 tensor")
+    ks = [int(x) for x in ks]
+    B, k = int(top_idx.shape[0]), int(top_idx.shape[1])
+    if not ks or len(ks) > 8 or min(ks) < 1 or max(ks) > k:
+        raise RuntimeError(f"ranking_metrics: between 1 and 8 cut-offs in [1, {k}], got {ks}")
+    dev = top_idx.device
+    top_idx = top_idx.contiguous()
+    _check_sets(truth, dev, 0, "ranking_metrics")
+    if user_ids is not None:
+        user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        if int(user_ids.numel()) != B:
+            raise RuntimeError("ranking_metrics: user_ids and top_idx differ in length")
+    elif truth.n_rows < B:
+        raise RuntimeError(f"ranking_metrics: {truth.n_rows} truth rows for {B} users")
+    n_slots = 4 * len(ks) + 1
+    own = sums is None
+    if own:
+        sums = torch.zeros(n_slots, dtype=torch.float64, device=dev)
+    elif sums.dtype != torch.float64 or sums.numel() != n_slots or sums.device != dev or not sums.is_contiguous():
+        raise RuntimeError(f"ranking_metrics: sums must be a contiguous float64 tensor of {n_slots} slots on {dev}")
+    pu = torch.empty((B, 4 * len(ks)), dtype=torch.float32, device=dev) if per_user else None
+    check_status = status is None
+    if check_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ks_arr = (C.c_int32 * len(ks))(*ks)
+    with _on(dev):
+        _lib.check(lib.ngcf_rank_metrics(_ptr(top_idx), B, k, _ptr(user_ids), truth.n_rows, _ptr(truth.rowptr), _ptr(truth.colidx),
+                                         truth.col_offset, ks_arr, len(ks), _ptr(pu), _ptr(sums), _ptr(status), _stream()))
+    if check_status and user_ids is not None and int(status.item()) != 0:
+        raise IndexError(f"ranking_metrics: a user id lies outside [0, {truth.n_rows})")
+    if not own:
+        return (sums, pu) if per_user else sums
+    out = metrics_from_sums(sums, ks)
+    return (out, pu) if per_user else out
+
+
+def metrics_from_sums(sums: torch.Tensor, ks: Sequence[int]) -> dict:
+    """The means of a `ranking_metrics` slot vector (one read-back)."""
+    s = sums.double().cpu().tolist()
+    n = int(round(s[-1]))
+    out = {}
+    for q, K in enumerate(ks):
+        for j, name in enumerate(("recall", "ndcg", "precision", "hr")):
+            out[f"{name}@{K}"] = s[4 * q + j] / n if n else 0.0
+    out["users"] = n
+    return out

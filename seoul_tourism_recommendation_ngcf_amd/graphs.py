@@ -57,6 +57,43 @@ def synthetic_bipartite(n_user: int, n_item: int, n_inter: int, seed: int, devic
     return coo
 
 
+def bipartite_from_interactions(u: torch.Tensor, i: torch.Tensor, w: torch.Tensor, n_user: int, n_item: int):
+    """The Laplacian COO of given unique interaction triplets (u, i, w) - e.g. the train part of `holdout_split` - in the layout of
+    `synthetic_bipartite` (count-degree normalised, both triangles, row-sorted) + sizes.  Triplets in any order."""
+    u = u.to(torch.int64)
+    i = i.to(device=u.device, dtype=torch.int64)
+    order = torch.argsort(u * n_item + i)
+    u, i, w = u[order], i[order], w.to(u.device)[order]
+    coo = _normalise(u, i, w, n_user, n_item)
+    coo.update({"n_user": n_user, "n_item": n_item, "interactions": int(u.numel()), "nnz": int(2 * u.numel())})
+    return coo
+
+
+def holdout_split(u: torch.Tensor, i: torch.Tensor, w: torch.Tensor, test_frac: float, seed: int):
+    """Held-out split of interaction triplets: of every user with n >= 2 interactions, ceil(test_frac * n) chosen at random (at
+    most n - 1, so the user keeps a training item) go to the test part.  Deterministic for a seed on a given device; the input
+    order is kept in both parts.  Returns ((u, i, w) train, (u, i, w) test)."""
+    if not 0.0 <= test_frac <= 1.0:
+        raise ValueError(f"holdout_split: test_frac={test_frac} outside [0, 1]")
+    dev = u.device
+    n = int(u.numel())
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    r = torch.rand((n,), generator=g, device=dev, dtype=torch.float64)
+    o = torch.argsort(r)
+    o = o[torch.sort(u[o], stable=True).indices]                 # grouped by user, a random order inside each user
+    cnt = torch.bincount(u, minlength=int(u.max()) + 1 if n else 0)
+    start = torch.cumsum(cnt, 0) - cnt
+    uo = u[o]
+    rank = torch.arange(n, device=dev) - start[uo]
+    n_u = cnt[uo]
+    n_test = torch.ceil(n_u.double() * test_frac - 1e-9).to(torch.int64).clamp(max=n_u - 1)
+    test = torch.zeros(n, dtype=torch.bool, device=dev)
+    test[o] = (n_u >= 2) & (rank < n_test)
+    train = ~test
+    return (u[train], i[train], w[train]), (u[test], i[test], w[test])
+
+
 def seoul_standin(device, seed: int = 1801, n_user: int = 5840, n_item: int = 100) -> List[Dict[str, torch.Tensor]]:
     """two year slices; mask Bernoulli(0.75) (per-user bottom quartile zeroed,
     utils.py:117-121), weights U(0.5, 5.0); slice 1 = slice 0 overlaid with a fresh draw (the `R` carry-over
