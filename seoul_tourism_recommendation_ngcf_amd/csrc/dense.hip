@@ -541,6 +541,265 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same layer on the bf16 matrix cores with an exact three-way split (r05, dense_resident = 4, the default).
+// layer_dense_resident_kernel keeps the fp32 matrix pipe ~71 % busy and is bound by it: v_mfma_f32_32x32x2_f32 runs at 1/16 of
+// the bf16 rate.  Every fp32 operand is split here as x = h + m + l (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m); both
+// residuals are exact in fp32 and the three parts carry the whole significand), and the product is accumulated in fp32 from the
+// six terms that matter, smallest first: mm, lh, hl, mh, hm, hh (a bf16 x bf16 product is exact in fp32; the dropped ml, lm, ll
+// are below 2^-24 relative).  6 v_mfma_f32_32x32x16_bf16 (32 cycles each) replace 8 v_mfma_f32_32x32x2_f32 (64 cycles each) per
+// 16 k-values: 3/8 of the matrix time.  Not bit-identical to the fp32 kernels; error at fp32 level (tests/test_dense_split_gpu.py).
+// Weights: pack_weights_split_kernel writes the three parts once per call in the B-fragment layout of 32x32x16 (lane (r, h)
+// holds B[k = 8h + j][column r], j = 0..7: 16 contiguous bytes).  All three parts of a 256 x 128 panel are 192 KB and do not fit
+// the 160 KB of LDS; h and m (2 x 8 KB per 16-column chunk: 128 KB at d_in = 128, 144 KB at 130 - the footprint of the fp32
+// resident kernel) stay resident, and l (64 / 72 KB, L2 resident) is read straight from global memory into registers, one chunk
+// ahead.  64-column output panels would fit as well, but a row would then be split over two workgroups and the row norm of the
+// epilogue would need a second pass over the output.  A lane reads the 8 input columns c*16 + 8h .. +7 of its row for both
+// k-steps of a chunk (k-step 0: the sums, against W1; k-step 1: the products, against W2) and splits them in registers.
+// The row loop, look-ahead, epilogue and stores are those of layer_dense_resident_kernel.
+// ---------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ void split3(f32x8 x, bf16x8 &h, bf16x8 &m, bf16x8 &l)
+{
+    h = __builtin_convertvector(x, bf16x8);                     // round to nearest even (v_cvt_pk_bf16_f32)
+    const f32x8 r = x - __builtin_convertvector(h, f32x8);      // exact
+    m = __builtin_convertvector(r, bf16x8);
+    l = __builtin_convertvector(r - __builtin_convertvector(m, f32x8), bf16x8);
+}
+
+// One thread per B fragment (chunk c, k-step s, column tile t, lane): Whm[((c*2 + s)*4 + t)*2 + p][lane] holds part p (h, m), and
+// Wl[(c*2 + s)*4 + t][lane] part l, of W_s[t*32 + lane%32][c*16 + 8*(lane/32) + j], j = 0..7 (W_0 = W1, W_1 = W2; zero outside).
+__global__ __launch_bounds__(256) void pack_weights_split_kernel(const float *__restrict__ W1, const float *__restrict__ b1,
+                                                                 const float *__restrict__ W2, const float *__restrict__ b2,
+                                                                 int d_in, int d_out, int n_chunks, bf16x8 *__restrict__ Whm,
+                                                                 bf16x8 *__restrict__ Wl, float *__restrict__ bias2)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < n_chunks * 512) {
+        const int lane = idx & 63, frag = idx >> 6, t = frag & 3, s = (frag >> 2) & 1, c = frag >> 3;
+        const int col = t * 32 + (lane & 31), in0 = c * NGCF_DC + 8 * (lane >> 5);
+        const float *w = (s ? W2 : W1) + (int64_t)col * d_in;
+        f32x8 x;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (col < d_out && in0 + j < d_in) ? w[in0 + j] : 0.f;
+        bf16x8 h, m, l;
+        split3(x, h, m, l);
+        Whm[(frag * 2 + 0) * 64 + lane] = h;
+        Whm[(frag * 2 + 1) * 64 + lane] = m;
+        Wl[idx] = l;
+    }
+    if (blockIdx.x == 0)
+        for (int j = threadIdx.x; j < 128; j += 256)
+            bias2[j] = j < d_out ? (b1[j] + b1[j]) + b2[j] : 0.f;   // b1 is added twice, NGCF.py:131,133
+}
+
+__global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
+    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
+    const bf16x8 *__restrict__ Whm, const bf16x8 *__restrict__ Wl, const float *__restrict__ bias2, int n_chunks, float leaky,
+    float drop_p, uint64_t drop_seed_in, const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc,
+    float *__restrict__ norm, int64_t ldn)
+{
+    const uint64_t drop_seed = drop_p > 0.f ? resolve_seed(drop_seed_in) : drop_seed_in;
+    constexpr int NT = 4, WCOLS = 128;
+    extern __shared__ bf16x8 Wsh[];                 // parts h and m of every chunk: [n_chunks * 2 * 4 * 2][64]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 31, lh = lane >> 5;
+    for (int i = tid; i < n_chunks * 1024; i += kResWaves * 64) Wsh[i] = Whm[i];
+    __syncthreads();
+    const int64_t n_tiles = (n_rows + 31) / 32;
+    const int d4 = (d_in + 3) & ~3;
+    float bz[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) bz[t] = bias2[t * 32 + li];
+    const int last = n_chunks - 1;
+    const int64_t tile_step = (int64_t)gridDim.x * kResWaves;
+    auto row_of = [&](int64_t t) {
+        int64_t g = t * 32 + li;
+        return g < n_rows ? g : n_rows - 1;
+    };
+    // the lane's 8 input columns of a chunk, c*16 + 8h + {0..3} (a) and {4..7} (b), of LE and E; columns past d_in are re-read
+    // from the row's last float4 and zeroed at use
+    auto fetch = [&](const float *le_row, const float *e_row, int c, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {
+        const int ca = c * NGCF_DC + lh * 8, cb = ca + 4;
+        const int cca = ca < d4 ? ca : d4 - 4, ccb = cb < d4 ? cb : d4 - 4;
+        la = *reinterpret_cast<const f32x4 *>(le_row + cca);
+        ea = *reinterpret_cast<const f32x4 *>(e_row + cca);
+        lb = *reinterpret_cast<const f32x4 *>(le_row + ccb);
+        eb = *reinterpret_cast<const f32x4 *>(e_row + ccb);
+    };
+    // part l of the weights of a chunk: fragment (k-step s, column tile t) at s*4 + t
+    auto fetch_l = [&](int c, bf16x8 (&bl)[8]) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f) bl[f] = Wl[(c * 8 + f) * 64 + lane];
+    };
+    f32x4 la0, lb0, ea0, eb0, la1, lb1, ea1, eb1;
+    bf16x8 bl0[8], bl1[8];                           // part l of chunks 0, 2, 4, .. and 1, 3, 5, ..
+    fetch_l(0, bl0);
+    int64_t tile = (int64_t)blockIdx.x * kResWaves + wave;
+    {
+        const int64_t g0 = row_of(tile < n_tiles ? tile : 0);
+        fetch(LE + g0 * ldLE, Es + g0 * ldE, 0, la0, lb0, ea0, eb0);
+        fetch(LE + g0 * ldLE, Es + g0 * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
+    }
+    for (; tile < n_tiles; tile += tile_step) {
+        const int64_t row0 = tile * 32;
+        const int64_t grow_l = row_of(tile);
+        const float *le_row = LE + grow_l * ldLE, *e_row = Es + grow_l * ldE;
+        f32x16 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        // the A fragments of a chunk: sums (k-step 0) and products (k-step 1), each split into h, m, l
+        auto form = [&](int c, f32x4 la, f32x4 lb, f32x4 ea, f32x4 eb, bf16x8 (&a)[2][3]) {
+            const int ca = c * NGCF_DC + lh * 8, cb = ca + 4;
+            if (cb + 4 > d_in) {                      // only the last chunk of a width that is not a multiple of 16
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (ca + q >= d_in) la[q] = 0.f, ea[q] = 0.f;
+                    if (cb + q >= d_in) lb[q] = 0.f, eb[q] = 0.f;
+                }
+            }
+            const f32x4 sa = la + ea, sb = lb + eb, pa = la * ea, pb = lb * eb;
+            split3(__builtin_shufflevector(sa, sb, 0, 1, 2, 3, 4, 5, 6, 7), a[0][0], a[0][1], a[0][2]);
+            split3(__builtin_shufflevector(pa, pb, 0, 1, 2, 3, 4, 5, 6, 7), a[1][0], a[1][1], a[1][2]);
+        };
+        // the 48 MFMAs of a chunk
+        auto chunk_mfma = [&](int c, const bf16x8 (&a)[2][3], const bf16x8 (&bl)[8]) {
+            const bf16x8 *wc = Wsh + c * 1024 + lane;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const bf16x8 &ah = a[s][0], &am = a[s][1], &al = a[s][2];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {          // one accumulation chain per tile (32x32x16 needs no interleaving)
+                    const bf16x8 bh = wc[((s * 4 + t) * 2 + 0) * 64], bm = wc[((s * 4 + t) * 2 + 1) * 64];
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s * 4 + t], acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
+                }
+            }
+        };
+        // chunk c uses set c & 1 of the raw operands (two chunks ahead) and of part l (one chunk ahead), both unconditional: past
+        // the end the last chunk is re-read; the next tile's chunk 0 of part l is requested with its first rows
+        int c = 0;
+        for (; c + 1 < n_chunks; c += 2) {
+            {
+                bf16x8 a[2][3];
+                form(c, la0, lb0, ea0, eb0, a);
+                fetch(le_row, e_row, c + 2 < last ? c + 2 : last, la0, lb0, ea0, eb0);
+                fetch_l(c + 1, bl1);
+                __builtin_amdgcn_sched_barrier(0);
+                chunk_mfma(c, a, bl0);
+            }
+            {
+                bf16x8 a[2][3];
+                form(c + 1, la1, lb1, ea1, eb1, a);
+                fetch(le_row, e_row, c + 3 < last ? c + 3 : last, la1, lb1, ea1, eb1);
+                fetch_l(c + 2 < last ? c + 2 : last, bl0);
+                __builtin_amdgcn_sched_barrier(0);
+                chunk_mfma(c + 1, a, bl1);
+            }
+        }
+        if (c < n_chunks) {
+            bf16x8 a[2][3];
+            form(c, la0, lb0, ea0, eb0, a);
+            chunk_mfma(c, a, bl0);
+        }
+        {   // the next tile's first two chunks, ahead of this tile's stores (the last tile of a wave re-reads its own)
+            const int64_t gn = row_of(tile + tile_step < n_tiles ? tile + tile_step : tile);
+            fetch(LE + gn * ldLE, Es + gn * ldE, 0, la0, lb0, ea0, eb0);
+            fetch(LE + gn * ldLE, Es + gn * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
+            fetch_l(0, bl0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- epilogue (wave-local): bias, LeakyReLU, dropout, row norm, stores - as layer_dense_resident_kernel
+        const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+        const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+        float rowss[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
+        const bool any_drop = drop_mask || drop_p > 0.f;
+        if (!any_drop) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = acc[t][r] + bz[t];
+                    v = v >= 0.f ? v : leaky * v;
+                    acc[t][r] = v;
+                    rowss[r] = fmaf(v, v, rowss[r]);
+                }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int col = t * 32 + li;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = acc[t][r] + bz[t];
+                    v = v >= 0.f ? v : leaky * v;
+                    const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
+                    else {
+                        const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
+                        v = h < drop_thr ? 0.f : v * keep_scale;
+                    }
+                    acc[t][r] = v;
+                    rowss[r] = fmaf(v, v, rowss[r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float s2 = rowss[r];
+            s2 += __shfl_xor(s2, 1);
+            s2 += __shfl_xor(s2, 2);
+            s2 += __shfl_xor(s2, 4);
+            s2 += __shfl_xor(s2, 8);
+            s2 += __shfl_xor(s2, 16);
+            rowss[r] = s2;
+        }
+        if (row0 + 32 <= n_rows && d_out == WCOLS) {          // full tile: no per-element tests
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
+                float *nrow = norm + grow * ldn + li;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) nrow[t * 32] = acc[t][r] * inv;
+            }
+            if (carry) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float *crow = carry + (row0 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ldc + li;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) crow[t * 32] = acc[t][r];
+                }
+            }
+            continue;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (grow >= n_rows) continue;
+            const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int col = t * 32 + li;
+                if (col < d_out) {
+                    const float v = acc[t][r];
+                    if (carry) carry[grow * ldc + col] = v;
+                    norm[grow * ldn + col] = v * inv;
+                }
+            }
+        }
+    }
+}
+
 #ifdef NGCF_LAB
 // ---------------------------------------------------------------------------------------------
 // LAB ONLY: layer_dense_resident_kernel with TWO row tiles per wave (64 rows x 128 columns, 128 accumulator registers): a B operand
@@ -1422,7 +1681,9 @@ extern "C" int64_t ngcf_dense_workspace_bytes(int d_in, int d_out)
     if (dop < 0 || d_in <= 0) return -1;
     dop = std::max(dop, 128);                  // small matrices run narrow layers on 32-row x 128-column tiles
     const int64_t n_chunks = (d_in + NGCF_DC - 1) / NGCF_DC;
-    return align_up((n_chunks * NGCF_KC * dop + dop) * (int64_t)sizeof(float), 256) + 256;
+    const int64_t fp32_packed = (n_chunks * NGCF_KC * dop + dop) * (int64_t)sizeof(float);
+    const int64_t split_packed = 128 * (int64_t)sizeof(float) + n_chunks * 3 * 8 * 1024;   // bias, parts h + m, part l
+    return align_up(std::max(fp32_packed, split_packed), 256) + 256;
 }
 
 template <int RW, int CW, int NT>
@@ -1517,9 +1778,11 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         LAUNCH_CHECK();
         return NGCF_OK;
     }
-    pack_weights_kernel<<<dim3((unsigned)(n_chunks * (dop / 32))), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks, dop,
-                                                                                    small_rows ? 1 : dop <= 128 ? dop / 32 : 4, Wt, bias2);
-    LAUNCH_CHECK();
+    auto pack_fp32 = [&]() {       // the fp32 kernels' packed weights (the split kernel packs its own)
+        pack_weights_kernel<<<dim3((unsigned)(n_chunks * (dop / 32))), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks, dop,
+                                                                                        small_rows ? 1 : dop <= 128 ? dop / 32 : 4, Wt, bias2);
+        return hipGetLastError();
+    };
 #define NGCF_DENSE(RW, CW, NT) \
     return launch_dense<RW, CW, NT>(al, n_rows, LE, ldLE, Es, ldEs, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, \
                                     drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream)
@@ -1533,6 +1796,28 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
             lds_bytes <= 150 * 1024 && n_rows >= (int64_t)ngcf_opts().dense_resident_min_rows) {
             static bool attr_set[kMaxDevices] = {};      // the attribute is per device
             const int dev_i = current_device_slot();
+            if (resident == 4) {
+                // the bf16 three-way split (layer_dense_split_kernel): bias at the start of the workspace, then parts h + m of
+                // every chunk (the LDS image), then part l
+                static bool split_set[kMaxDevices] = {};
+                if (!split_set[dev_i]) {
+                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_split_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    split_set[dev_i] = true;
+                }
+                float *sbias = Wt;
+                bf16x8 *whm = reinterpret_cast<bf16x8 *>(Wt + 128);
+                bf16x8 *wl = whm + (int64_t)n_chunks * 1024;
+                pack_weights_split_kernel<<<dim3((unsigned)(n_chunks * 2)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks,
+                                                                                              whm, wl, sbias);
+                LAUNCH_CHECK();
+                layer_dense_split_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)n_chunks * 16 * 1024, stream>>>(
+                    LE, ldLE, Es, ldEs, n_rows, d_in, d_out, whm, wl, sbias, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask,
+                    carry, ldc, norm, ldn);
+                LAUNCH_CHECK();
+                return NGCF_OK;
+            }
+            HIP_TRY(pack_fp32());
             if (!attr_set[dev_i]) {
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1607,6 +1892,7 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
             return NGCF_OK;
         }
     }
+    HIP_TRY(pack_fp32());
     if (direct) {
         const int64_t blocks = (n_rows + 31) / 32;
         if (dop == 256)
