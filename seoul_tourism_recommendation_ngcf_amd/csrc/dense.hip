@@ -1729,6 +1729,9 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     const int64_t need = ngcf_dense_workspace_bytes(d_in, d_out);
     if (!workspace || workspace_bytes < need)
         return fail(NGCF_ERR_WORKSPACE, "layer_dense: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
+    // Nothing to compute, and no kernel may run: the persistent kernels' row_of() would clamp to row -1 (dense_resident_min_rows
+    // can be set to 0 or below).
+    if (n_rows == 0) return NGCF_OK;
     const int n_chunks = (d_in + NGCF_DC - 1) / NGCF_DC;
     float *Wt = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
     float *bias2 = Wt + (int64_t)n_chunks * NGCF_KC * dop;
@@ -1778,9 +1781,9 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         LAUNCH_CHECK();
         return NGCF_OK;
     }
-    auto pack_fp32 = [&]() {       // the fp32 kernels' packed weights (the split kernel packs its own)
+    auto pack_fp32 = [&](int nt) {  // the fp32 kernels' packed weights, nt tiles per wave (the split kernel packs its own)
         pack_weights_kernel<<<dim3((unsigned)(n_chunks * (dop / 32))), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks, dop,
-                                                                                        small_rows ? 1 : dop <= 128 ? dop / 32 : 4, Wt, bias2);
+                                                                                        nt, Wt, bias2);
         return hipGetLastError();
     };
 #define NGCF_DENSE(RW, CW, NT) \
@@ -1817,7 +1820,9 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
                 LAUNCH_CHECK();
                 return NGCF_OK;
             }
-            HIP_TRY(pack_fp32());
+            // the resident kernels read four column tiles per lane, also where small_rows picked 32-row tiles for the staged
+            // kernel (a dense_resident_min_rows at or below 16 384 rows)
+            HIP_TRY(pack_fp32(4));
             if (!attr_set[dev_i]) {
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1892,7 +1897,7 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
             return NGCF_OK;
         }
     }
-    HIP_TRY(pack_fp32());
+    HIP_TRY(pack_fp32(small_rows ? 1 : dop <= 128 ? dop / 32 : 4));
     if (direct) {
         const int64_t blocks = (n_rows + 31) / 32;
         if (dop == 256)

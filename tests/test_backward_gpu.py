@@ -200,8 +200,13 @@ def test_weight_gradient_kernel_matches_fp64(n_rows, d_in, d_out, strided, dev):
     and the empty case.  Summation order differs from any reference GEMM: tolerance, relative to the result's scale."""
     from seoul_tourism_recommendation_ngcf_amd import autograd, engine
     g = torch.Generator(device=dev).manual_seed(n_rows + d_in)
-    mk = lambda n, d: torch.randn((n, d + (12 if strided else 0)), generator=g, device=dev)[:, :d]  # noqa: E731
-    dM, LE, E = mk(n_rows, d_out), mk(n_rows, d_in), mk(n_rows, d_in)
+
+    def mk(n, d, poison=False):     # strided: a column slice of a wider matrix; LE / E with NaN in the other columns
+        t = torch.randn((n, d + (12 if strided else 0)), generator=g, device=dev)
+        if poison:
+            t[:, d:] = float("nan")
+        return t[:, :d]
+    dM, LE, E = mk(n_rows, d_out), mk(n_rows, d_in, True), mk(n_rows, d_in, True)
     ws = engine.Workspace()
     g1, gb1, g2, gb = autograd._bwd_weight(dM, LE, E, ws)
     assert g1.shape == (d_out, d_in) and g2.shape == (d_out, d_in) and gb.shape == (d_out,)
@@ -218,6 +223,14 @@ def test_weight_gradient_kernel_matches_fp64(n_rows, d_in, d_out, strided, dev):
     assert torch.equal(got, torch.cat([a1, a2], 1)) and torch.equal(gb, gb2)             # fixed summation order
 
 
+def _nan_around(n, d, before, after, g, dev):
+    """randn * 0.5 [n, d] as columns before .. before + d of an [n, before + d + after] device matrix whose other columns hold NaN."""
+    X = torch.randn((n, before + d + after), generator=g) * 0.5
+    X[:, :before] = float("nan")
+    X[:, before + d:] = float("nan")
+    return X.to(dev)[:, before:before + d]
+
+
 @pytest.mark.parametrize("n_rows,d_in,d_out,strided", [(1, 4, 4, False), (130, 128, 128, False), (1000, 130, 128, True), (333, 65, 64, True),
                                                         (257, 160, 96, False), (500, 300, 128, False), (64, 515, 512, True)])
 def test_fused_input_gradient_kernel_vs_torch(n_rows, d_in, d_out, strided, dev):
@@ -227,9 +240,8 @@ def test_fused_input_gradient_kernel_vs_torch(n_rows, d_in, d_out, strided, dev)
     g = torch.Generator().manual_seed(n_rows + d_in)
     dM = (torch.randn((n_rows, d_out), generator=g) * 0.3).to(dev)
     W1, W2 = ((torch.randn((d_out, d_in), generator=g) * 0.1).to(dev) for _ in range(2))
-    if strided:      # LE / E as column slices of wider matrices (all_E blocks, padded LE)
-        LE = (torch.randn((n_rows, d_in + 30), generator=g) * 0.5).to(dev)[:, :d_in]
-        E = (torch.randn((n_rows, d_in + 7), generator=g) * 0.5).to(dev)[:, 3:3 + d_in]
+    if strided:      # LE / E as column slices of wider matrices (all_E blocks, padded LE), NaN in the other columns
+        LE, E = _nan_around(n_rows, d_in, 0, 30, g, dev), _nan_around(n_rows, d_in, 3, 4, g, dev)
     else:
         LE, E = ((torch.randn((n_rows, d_in), generator=g) * 0.5).to(dev) for _ in range(2))
     dLE, dE = ag._bwd_input(dM, W1, W2, LE, E, eng.Workspace())
@@ -253,9 +265,8 @@ def test_resident_input_gradient_kernel_is_bit_identical_to_the_staged_one(n_row
     dM = torch.full((n_rows, ldm), float("nan"), device=dev)[:, :d_out]
     dM.copy_((torch.randn((n_rows, d_out), generator=g) * 0.3).to(dev))
     W1, W2 = ((torch.randn((d_out, d_in), generator=g) * 0.1).to(dev) for _ in range(2))
-    if strided:
-        LE = (torch.randn((n_rows, d_in + 30), generator=g) * 0.5).to(dev)[:, :d_in]
-        E = (torch.randn((n_rows, d_in + 7), generator=g) * 0.5).to(dev)[:, 3:3 + d_in]
+    if strided:      # NaN in the columns around the slices
+        LE, E = _nan_around(n_rows, d_in, 0, 30, g, dev), _nan_around(n_rows, d_in, 3, 4, g, dev)
     else:
         LE, E = ((torch.randn((n_rows, d_in), generator=g) * 0.5).to(dev) for _ in range(2))
     ws = eng.Workspace()

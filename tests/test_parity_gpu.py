@@ -855,6 +855,13 @@ def test_odd_shapes_against_oracle(U, I, inter, d0, layers, B, dev):
     assert abs(float(loss) - ref_loss) <= 1e-4 * abs(ref_loss) + 1e-6
 
 
+def _nan_padded(n, d, g, dev):
+    """randn * 0.5 [n, d] as the column slice of a wider (16-byte aligned, padded) matrix whose padding columns hold NaN."""
+    X = torch.randn((n, (d // 32 + 1) * 32), generator=g) * 0.5
+    X[:, d:] = float("nan")
+    return X.to(dev)[:, :d]
+
+
 @pytest.mark.parametrize("d_in,d_out,mode", [(128, 128, "eval"), (130, 128, "hash"), (64, 100, "mask"), (144, 128, "last"),
                                              (120, 128, "mask"), (128, 128, "last"), (113, 128, "hash")])
 def test_resident_dense_kernel_is_bit_identical_to_the_staged_one(d_in, d_out, mode, dev, lib_options):
@@ -867,9 +874,8 @@ def test_resident_dense_kernel_is_bit_identical_to_the_staged_one(d_in, d_out, m
     eng = _pkg().engine
     n = 140_001                                              # above the kernel's threshold; not a multiple of 32: a partial last tile
     g = torch.Generator().manual_seed(d_in + d_out)
-    ld = (d_in + 31) // 32 * 32
-    LE = (torch.randn((n, ld), generator=g) * 0.5).to(dev)[:, :d_in]
-    E = (torch.randn((n, ld), generator=g) * 0.5).to(dev)[:, :d_in]
+    LE = _nan_padded(n, d_in, g, dev)                        # NaN in the padding columns: selected away, never multiplied by 0
+    E = _nan_padded(n, d_in, g, dev)
     W1, W2 = ((torch.randn((d_out, d_in), generator=g) * 0.1).to(dev) for _ in range(2))
     b1, b2 = ((torch.randn((d_out,), generator=g) * 0.1).to(dev) for _ in range(2))
     mask = (torch.rand((n, d_out), generator=g) > 0.3).float().to(dev) / 0.7 if mode == "mask" else None
@@ -891,6 +897,34 @@ def test_resident_dense_kernel_is_bit_identical_to_the_staged_one(d_in, d_out, m
     assert float((outs[0][1].norm(dim=1) - 1).abs().max()) < 1e-5
 
 
+@pytest.mark.parametrize("d_in,d_out,n,mode", [(130, 128, 4099, "hash"), (64, 64, 16384, "eval"), (113, 100, 33, "mask"),
+                                               (17, 32, 1, "last"), (144, 97, 16383, "eval")])
+def test_resident_dense_kernel_below_the_small_tile_limit_is_bit_identical_to_the_staged_one(d_in, d_out, n, mode, dev,
+                                                                                             lib_options):
+    """With dense_resident_min_rows lowered to 16 384 rows or fewer the resident kernel also takes the matrices on which the
+    staged kernel runs 32-row tiles (output columns padded to 128, one column tile per wave): it must still get the weights in
+    its own layout (four column tiles per lane).  Same k order per element: the carry agrees bit for bit; the row norm adds the
+    squares of the four waves of a small tile in another order, so the normalised block agrees to rounding."""
+    eng = _pkg().engine
+    g = torch.Generator().manual_seed(d_in + d_out + n)
+    LE, E = _nan_padded(n, d_in, g, dev), _nan_padded(n, d_in, g, dev)
+    W1, W2 = ((torch.randn((d_out, d_in), generator=g) * 0.1).to(dev) for _ in range(2))
+    b1, b2 = ((torch.randn((d_out,), generator=g) * 0.1).to(dev) for _ in range(2))
+    mask = (torch.rand((n, d_out), generator=g) > 0.3).float().to(dev) / 0.7 if mode == "mask" else None
+    kw = dict(drop_p=0.3 if mode in ("hash", "mask") else 0.0, drop_seed=77 if mode == "hash" else 0, drop_mask=mask)
+    outs = []
+    for resident in (1, 0):
+        lib_options(dense_resident=resident, dense_resident_min_rows=1)
+        carry = None if mode == "last" else torch.full((n, d_out), 5.0, device=dev)
+        norm = torch.full((n, d_out), 7.0, device=dev)
+        eng.layer_dense(LE, E, W1, b1, W2, b2, carry, norm, eng.Workspace(), **kw)
+        outs.append((carry, norm))
+    torch.testing.assert_close(outs[0][1], outs[1][1], rtol=2e-6, atol=1e-7)
+    assert float((outs[0][1].norm(dim=1) - 1).abs().max()) < 1e-5
+    if mode != "last":
+        assert torch.equal(outs[0][0], outs[1][0])
+
+
 @pytest.mark.parametrize("d_in,d_out,n,mode", [(515, 512, 5941, "eval"), (512, 512, 300, "hash"), (256, 256, 4099, "mask"),
                                               (130, 200, 1000, "last"), (260, 300, 33, "eval"), (8, 512, 64, "hash"),
                                               (256, 256, 40_003, "eval")])
@@ -902,9 +936,8 @@ def test_direct_dense_kernel_is_bit_identical_to_the_staged_one(d_in, d_out, n, 
     import os
     eng = _pkg().engine
     g = torch.Generator().manual_seed(d_in + d_out + n)
-    ld = (d_in + 31) // 32 * 32
-    LE = (torch.randn((n, ld), generator=g) * 0.5).to(dev)[:, :d_in]
-    E = (torch.randn((n, ld), generator=g) * 0.5).to(dev)[:, :d_in]
+    LE = _nan_padded(n, d_in, g, dev)                        # NaN in the padding columns: selected away, never multiplied by 0
+    E = _nan_padded(n, d_in, g, dev)
     W1, W2 = ((torch.randn((d_out, d_in), generator=g) * 0.1).to(dev) for _ in range(2))
     b1, b2 = ((torch.randn((d_out,), generator=g) * 0.1).to(dev) for _ in range(2))
     mask = (torch.rand((n, d_out), generator=g) > 0.3).float().to(dev) / 0.7 if mode == "mask" else None
