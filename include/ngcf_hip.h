@@ -43,16 +43,15 @@ const char *ngcf_last_error(void);
 const char *ngcf_target_arch(void);
 /* ABI version of this header.  ngcf_version() returns the value the library was built with; the Python mirror refuses to bind
  * a library whose version differs (a stale .so would otherwise receive shifted arguments). */
-#define NGCF_ABI_VERSION 8
+#define NGCF_ABI_VERSION 9
 int ngcf_version(void);
 
-/* Tunables of the kernel dispatch (thresholds, lab switches).  The library reads its NGCF_* environment variables ONCE, in
+/* Tunables of the kernel dispatch (thresholds, switches).  The library reads its NGCF_* environment variables ONCE, in
  * ngcf_options_from_env() on first use (no launch path touches the environment); call it again to re-read them, or set single
  * options by name (the variable's name without the NGCF_ prefix, lower case: "dense_resident", "swept_lead", ...; the table
  * is NgcfOptions in csrc/common.h).  Unknown names are an error.  Not thread-safe against concurrent launches. */
 int ngcf_options_from_env(void);
 int ngcf_set_option(const char *name, int64_t value);
-int ngcf_set_option_str(const char *name, const char *value);
 
 /* Timing of the dominant kernel for bench.py's roofline line: while enabled, every SpMM kernel launch is
  * bracketed by a hipEvent pair on its own stream.  ngcf_prof_collect waits for them and returns the number

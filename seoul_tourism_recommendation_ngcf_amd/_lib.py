@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must be loaded before libngcf_hip.so, see module do
 from . import _build
 
 OK, ERR_ARG, ERR_HIP, ERR_INDEX, ERR_WORKSPACE = 0, 1, 2, 3, 4
-ABI_VERSION = 8          # NGCF_ABI_VERSION of include/ngcf_hip.h these prototypes were written against
+ABI_VERSION = 9          # NGCF_ABI_VERSION of include/ngcf_hip.h these prototypes were written against
 
 _vp, _i64, _i32, _f32, _u64 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint64
 
@@ -26,7 +26,6 @@ PROTOTYPES = {
     "ngcf_version": (C.c_int, []),
     "ngcf_options_from_env": (C.c_int, []),
     "ngcf_set_option": (C.c_int, [C.c_char_p, _i64]),
-    "ngcf_set_option_str": (C.c_int, [C.c_char_p, C.c_char_p]),
     "ngcf_prof_enable": (C.c_int, [C.c_int]),
     "ngcf_prof_collect": (C.c_int, [C.POINTER(_i64), C.POINTER(C.c_double)]),
     "ngcf_csr_from_coo": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.POINTER(_vp), _vp]),
@@ -160,10 +159,7 @@ def load():
 
 def set_option(name: str, value) -> None:
     """One tunable of the kernel dispatch by name (include/ngcf_hip.h, ngcf_set_option): tests and tools."""
-    if isinstance(value, str):
-        check(load().ngcf_set_option_str(name.encode(), value.encode()))
-    else:
-        check(load().ngcf_set_option(name.encode(), int(value)))
+    check(load().ngcf_set_option(name.encode(), int(value)))
 
 
 def options_from_env() -> None:

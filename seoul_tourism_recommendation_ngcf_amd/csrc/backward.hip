@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void layer_bwd_pre_kernel(const float *__restr
         ydot = clamped ? 0.f : dot / (den * den);            // (y.dy)/|x| with y = x/|x|
     }
     const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    const uint32_t thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+    const uint32_t thr = msg_drop_thr(drop_p);
     using V = typename VecT<VEC>::type;
     for (int j = lane * VEC; j < d; j += 64 * VEC) {
         float cv[VEC], gv[VEC], dc[VEC], mk[VEC], out[VEC];
@@ -262,8 +262,7 @@ __global__ __launch_bounds__(256) void layer_bwd_pre_kernel(const float *__restr
             if (drop_mask) {
                 t *= mk[q];                                   // the host-drawn noise tensor of the forward (0 or 1/(1-p))
             } else if (drop_p > 0.f) {
-                const uint32_t h = mix32(seed ^ ((uint64_t)r_hash * 0x9E3779B97F4A7C15ULL + (uint64_t)(j + q)));
-                t = h < thr ? 0.f : t * keep_scale;
+                t = msg_drop(t, seed, r_hash, j + q, thr, keep_scale);
             }
             out[q] = t * (cv[q] > 0.f ? 1.f : leaky);         // sign(C) == sign(M) wherever C was kept
         }

@@ -50,7 +50,7 @@ inline int fail(int code, const char *fmt, ...)
 // ---------------------------------------------------------------------------------------------
 // options: every tunable of the dispatch code in ONE struct.  csr.hip fills it once per process (the only getenv() of the
 // library is in ngcf_options_from_env there: launches never touch the environment) and ngcf_set_option changes single
-// fields at run time (tests, tools/).  Fields marked LAB select code that is compiled only with -DNGCF_LAB.
+// fields at run time (tests, tools/).
 // ---------------------------------------------------------------------------------------------
 struct NgcfOptions {
     // spmm.hip
@@ -63,11 +63,10 @@ struct NgcfOptions {
     int64_t fork_min = 200000000;  // NGCF_FORK_MIN: entry-columns from which the halves are forked under capture
     // dense.hip
     int dense_direct = 1;          // NGCF_DENSE_DIRECT: 0 never, 1 up to 8 192 rows, 2 at any row count
-    int dense_resident = 4;        // NGCF_DENSE_RESIDENT: 4 the bf16 three-way split kernel; 1 the fp32 weights-resident kernel; 0 keeps the staged kernel; (LAB) 2: layer_dense_resident_il_kernel where it applies
+    int dense_resident = 4;        // NGCF_DENSE_RESIDENT: 4 the bf16 three-way split kernel; 1 the fp32 weights-resident kernel; 0 keeps the staged kernel
     int dense_resident_min_rows = 106496;  // NGCF_DENSE_RESIDENT_MIN_ROWS: rows from which the weights-resident kernel runs (65 536 = one round of its 2 048 waves; measured cross-over, profiles/r04_dense_rows_lab.txt)
     int dense_small_tiles = 1;     // NGCF_DENSE_SMALL_TILES: 32-row tiles for <= 128 output columns on <= 16 384 rows
     int dense_tall = 1;            // NGCF_DENSE_TALL: 256 / 512 output columns as 96-row x 128-column workgroups: 0 never, 1 where measured faster, 2 always
-    int dense_il_lab = 0;          // NGCF_DENSE_IL_LAB (LAB): the interleaved kernel taken apart: 1 no stores, 2 no loads, 3 neither
     // backward.hip
     int t_rows_bitmap = 1;         // NGCF_T_ROWS_BITMAP: 0 keeps the row-sparse transposed product on the slot-table kernel at every size
     int bwd_input_resident = 1;    // NGCF_BWD_INPUT_RESIDENT: 0 keeps the staged input-gradient kernel at every size
@@ -75,7 +74,6 @@ struct NgcfOptions {
     int slice_max_mb = 48;         // NGCF_SLICE_MAX_MB: largest table slice a d-sliced group may gather from
     // spmm_swept.hip (plan)
     int swept_lpe = 16;            // NGCF_SWEPT_LPE: lanes per entry of the swept plan: 16 = 64-float slices, 32 = 128-float slices
-    int swept_waves = 0;           // NGCF_SWEPT_WAVES (LAB: 8)
     int swept_cut = 4;             // NGCF_SWEPT_CUT: rows are cut at 1/cut of a wave task's share
     int swept_no_moments = 0;      // NGCF_SWEPT_NO_MOMENTS
     int swept_order_rows = 0;      // NGCF_SWEPT_ORDER=rows
@@ -87,9 +85,6 @@ struct NgcfOptions {
     int swept_sync_every = 1;      // NGCF_SWEPT_SYNC_EVERY
     int swept_prio_kb = 256;       // NGCF_SWEPT_PRIO_KB
     int swept_prio_graded = 1;     // NGCF_SWEPT_PRIO_GRADED
-    int swept_nt = 0;              // NGCF_SWEPT_NT (LAB)
-    int swept_merge = 0;           // NGCF_SWEPT_MERGE (LAB)
-    char swept_trace[480] = "";    // NGCF_SWEPT_TRACE (LAB): file prefix of the sweep-spread trace
 };
 extern NgcfOptions g_opts;                      // csr.hip
 const NgcfOptions &ngcf_opts();                 // csr.hip: reads the environment on first use
@@ -219,6 +214,19 @@ __device__ inline uint32_t mix32(uint64_t x)
     x *= 0xc4ceb9fe1a85ec53ULL;
     x ^= x >> 33;
     return (uint32_t)x;
+}
+
+// Device-side message dropout (nn.Dropout on a layer's activated output, NGCF.py:142): element (row, col) is dropped iff its
+// hash is below msg_drop_thr(p); a kept one is scaled by keep_scale = 1/(1-p).  The forward dense kernels and the backward's
+// layer_bwd_pre_kernel must draw the same mask bit for bit: all of them go through these two functions.
+__device__ __forceinline__ uint32_t msg_drop_thr(float drop_p)
+{
+    return drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+}
+__device__ __forceinline__ float msg_drop(float v, uint64_t seed, int64_t row, int col, uint32_t thr, float keep_scale)
+{
+    const uint32_t h = mix32(seed ^ ((uint64_t)row * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
+    return h < thr ? 0.f : v * keep_scale;
 }
 
 // Device-side node dropout (NGCF.py:93-100 semantics: keep each stored entry w.p. 1-p, values NOT rescaled,

@@ -38,13 +38,11 @@ const OptField kOptFields[] = {
     {"dense_resident", &NgcfOptions::dense_resident, nullptr},
     {"dense_resident_min_rows", &NgcfOptions::dense_resident_min_rows, nullptr},
     {"dense_small_tiles", &NgcfOptions::dense_small_tiles, nullptr},
-    {"dense_il_lab", &NgcfOptions::dense_il_lab, nullptr},
     {"dense_tall", &NgcfOptions::dense_tall, nullptr},
     {"bwd_input_resident", &NgcfOptions::bwd_input_resident, nullptr},
     {"t_rows_bitmap", &NgcfOptions::t_rows_bitmap, nullptr},
     {"slice_max_mb", &NgcfOptions::slice_max_mb, nullptr},
     {"swept_lpe", &NgcfOptions::swept_lpe, nullptr},
-    {"swept_waves", &NgcfOptions::swept_waves, nullptr},
     {"swept_cut", &NgcfOptions::swept_cut, nullptr},
     {"swept_no_moments", &NgcfOptions::swept_no_moments, nullptr},
     {"swept_order_rows", &NgcfOptions::swept_order_rows, nullptr},
@@ -55,8 +53,6 @@ const OptField kOptFields[] = {
     {"swept_sync_every", &NgcfOptions::swept_sync_every, nullptr},
     {"swept_prio_kb", &NgcfOptions::swept_prio_kb, nullptr},
     {"swept_prio_graded", &NgcfOptions::swept_prio_graded, nullptr},
-    {"swept_nt", &NgcfOptions::swept_nt, nullptr},
-    {"swept_merge", &NgcfOptions::swept_merge, nullptr},
 };
 bool g_opts_read = false;
 }  // namespace
@@ -78,7 +74,6 @@ extern "C" int ngcf_options_from_env(void)
         else o.*(f.l) = v;
     }
     if (const char *e = getenv("NGCF_SWEPT_ORDER")) o.swept_order_rows = !strcmp(e, "rows");
-    if (const char *e = getenv("NGCF_SWEPT_TRACE")) snprintf(o.swept_trace, sizeof(o.swept_trace), "%s", e);
     g_opts = o;
     g_opts_read = true;
     return NGCF_OK;
@@ -101,17 +96,6 @@ extern "C" int ngcf_set_option(const char *name, int64_t value)
             return NGCF_OK;
         }
     return fail(NGCF_ERR_ARG, "ngcf_set_option: unknown option '%s'", name);
-}
-
-extern "C" int ngcf_set_option_str(const char *name, const char *value)
-{
-    if (!name) return fail(NGCF_ERR_ARG, "ngcf_set_option_str: null name");
-    (void)ngcf_opts();
-    if (!strcmp(name, "swept_trace")) {
-        snprintf(g_opts.swept_trace, sizeof(g_opts.swept_trace), "%s", value ? value : "");
-        return NGCF_OK;
-    }
-    return fail(NGCF_ERR_ARG, "ngcf_set_option_str: unknown option '%s'", name);
 }
 
 

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
 
     // ---- epilogue: bias, LeakyReLU, dropout, row sum of squares
     const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+    const uint32_t drop_thr = msg_drop_thr(drop_p);
     float rowss[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
@@ -250,8 +250,7 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
                     v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
                 } else if (drop_p > 0.f) {
                     const int64_t grow = row0 + rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                    v = h < drop_thr ? 0.f : v * keep_scale;
+                    v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
                 }
                 acc[t][r] = v;
                 rowss[r] = fmaf(v, v, rowss[r]);
@@ -460,7 +459,7 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident_kernel(
         }
         // ---- epilogue (wave-local): bias, LeakyReLU, dropout, row norm, stores
         const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-        const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+        const uint32_t drop_thr = msg_drop_thr(drop_p);
         float rowss[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
@@ -485,10 +484,7 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident_kernel(
                     v = v >= 0.f ? v : leaky * v;
                     const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-                    else {
-                        const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                        v = h < drop_thr ? 0.f : v * keep_scale;
-                    }
+                    else v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
                     acc[t][r] = v;
                     rowss[r] = fmaf(v, v, rowss[r]);
                 }
@@ -719,7 +715,7 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
         }
         // ---- epilogue (wave-local): bias, LeakyReLU, dropout, row norm, stores - as layer_dense_resident_kernel
         const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-        const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+        const uint32_t drop_thr = msg_drop_thr(drop_p);
         float rowss[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
@@ -744,10 +740,7 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
                     v = v >= 0.f ? v : leaky * v;
                     const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-                    else {
-                        const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                        v = h < drop_thr ? 0.f : v * keep_scale;
-                    }
+                    else v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
                     acc[t][r] = v;
                     rowss[r] = fmaf(v, v, rowss[r]);
                 }
@@ -800,450 +793,7 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
     }
 }
 
-#ifdef NGCF_LAB
-// ---------------------------------------------------------------------------------------------
-// LAB ONLY: layer_dense_resident_kernel with TWO row tiles per wave (64 rows x 128 columns, 128 accumulator registers): a B operand
-// read from LDS feeds eight MFMAs instead of four (half the LDS read bytes per MFMA - MI355X_MICROARCH.md "DVFS give-back": what
-// raises the clock is less energy per MFMA), raw operands one chunk (128 MFMAs) ahead in one register set per tile.  Same k order
-// and epilogue arithmetic: bit-identical.  dense_resident = 3.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident2_kernel(
-    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
-    const float *__restrict__ Wt, const float *__restrict__ bias2, int n_chunks, float leaky, float drop_p, uint64_t drop_seed_in,
-    const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc, float *__restrict__ norm, int64_t ldn)
-{
-    const uint64_t drop_seed = drop_p > 0.f ? resolve_seed(drop_seed_in) : drop_seed_in;
-    constexpr int NT = 4, WCOLS = 128, TP = 2;
-    extern __shared__ float Wres[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int li = lane & 31, lh = lane >> 5;
-    {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(Wt);
-        f32x4 *dst = reinterpret_cast<f32x4 *>(Wres);
-        const int n4 = n_chunks * NGCF_KC * WCOLS / 4;
-        for (int i = tid; i < n4; i += kResWaves * 64) dst[i] = src[i];
-    }
-    __syncthreads();
-    const int64_t n_pairs = (n_rows + 32 * TP - 1) / (32 * TP);
-    const int d4 = (d_in + 3) & ~3;
-    const float *W = Wres + li * NT + lh * 4 * WCOLS;
-    float bz[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) bz[t] = bias2[t * 32 + li];
-    const int last = n_chunks - 1;
-    const int64_t pair_step = (int64_t)gridDim.x * kResWaves;
-    auto row_of = [&](int64_t pr, int u) {
-        int64_t g = pr * (32 * TP) + u * 32 + li;
-        return g < n_rows ? g : n_rows - 1;
-    };
-    auto fetch = [&](const float *le_row, const float *e_row, int c, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {
-        const int ca = c * NGCF_DC + lh * 4, cb = ca + 8;
-        const int cca = ca < d4 ? ca : d4 - 4, ccb = cb < d4 ? cb : d4 - 4;
-        la = *reinterpret_cast<const f32x4 *>(le_row + cca);
-        ea = *reinterpret_cast<const f32x4 *>(e_row + cca);
-        lb = *reinterpret_cast<const f32x4 *>(le_row + ccb);
-        eb = *reinterpret_cast<const f32x4 *>(e_row + ccb);
-    };
-    f32x4 la[TP], lb[TP], ea[TP], eb[TP];
-    int64_t pair = (int64_t)blockIdx.x * kResWaves + wave;
-#pragma unroll
-    for (int u = 0; u < TP; ++u) {
-        const int64_t g0 = row_of(pair < n_pairs ? pair : 0, u);
-        fetch(LE + g0 * ldLE, Es + g0 * ldE, 0, la[u], lb[u], ea[u], eb[u]);
-    }
-    for (; pair < n_pairs; pair += pair_step) {
-        const int64_t row0 = pair * (32 * TP);
-        const float *le_row[TP], *e_row[TP];
-#pragma unroll
-        for (int u = 0; u < TP; ++u) {
-            const int64_t g = row_of(pair, u);
-            le_row[u] = LE + g * ldLE, e_row[u] = Es + g * ldE;
-        }
-        f32x16 acc[TP][NT];
-#pragma unroll
-        for (int u = 0; u < TP; ++u)
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[u][t][r] = 0.f;
-        for (int c = 0; c < n_chunks; ++c) {
-            f32x4 a4[TP][4];
-            const int ca = c * NGCF_DC + lh * 4, cb = ca + 8;
-#pragma unroll
-            for (int u = 0; u < TP; ++u) {
-                if (cb + 4 > d_in) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        if (ca + q >= d_in) la[u][q] = 0.f, ea[u][q] = 0.f;
-                        if (cb + q >= d_in) lb[u][q] = 0.f, eb[u][q] = 0.f;
-                    }
-                }
-                a4[u][0] = la[u] + ea[u], a4[u][1] = lb[u] + eb[u], a4[u][2] = la[u] * ea[u], a4[u][3] = lb[u] * eb[u];
-            }
-            {   // the next chunk - of this pair, or chunk 0 of the wave's next pair (the last pair re-reads its own): unconditional
-                const bool nxt = c == last;
-                const int64_t np = pair + pair_step < n_pairs ? pair + pair_step : pair;
-#pragma unroll
-                for (int u = 0; u < TP; ++u) {
-                    const int64_t gn = row_of(np, u);
-                    const float *lr = nxt ? LE + gn * ldLE : le_row[u], *er = nxt ? Es + gn * ldE : e_row[u];
-                    fetch(lr, er, nxt ? 0 : c + 1, la[u], lb[u], ea[u], eb[u]);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const float *wc = W + (int64_t)c * NGCF_KC * WCOLS;
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                for (int sx = 0; sx < 4; ++sx) {
-                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(wc + (kb * 8 + sx) * WCOLS);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) {
-                        acc[u][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.x, acc[u][0], 0, 0, 0);
-                        acc[u][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.y, acc[u][1], 0, 0, 0);
-                        acc[u][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.z, acc[u][2], 0, 0, 0);
-                        acc[u][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.w, acc[u][3], 0, 0, 0);
-                    }
-                }
-        }
-        // ---- epilogue per tile (wave-local): bias, LeakyReLU, dropout, row norm, stores
-        const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-        const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-#pragma unroll
-        for (int u = 0; u < TP; ++u) {
-            const int64_t t0 = row0 + u * 32;
-            if (t0 >= n_rows) break;
-            float rowss[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = t * 32 + li;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = acc[u][t][r] + bz[t];
-                    v = v >= 0.f ? v : leaky * v;
-                    if (drop_mask || drop_p > 0.f) {
-                        const int64_t grow = t0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-                        else {
-                            const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                            v = h < drop_thr ? 0.f : v * keep_scale;
-                        }
-                    }
-                    acc[u][t][r] = v;
-                    rowss[r] = fmaf(v, v, rowss[r]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float s2 = rowss[r];
-                s2 += __shfl_xor(s2, 1);
-                s2 += __shfl_xor(s2, 2);
-                s2 += __shfl_xor(s2, 4);
-                s2 += __shfl_xor(s2, 8);
-                s2 += __shfl_xor(s2, 16);
-                rowss[r] = s2;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t grow = t0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (grow >= n_rows) continue;
-                const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const int col = t * 32 + li;
-                    if (col < d_out) {
-                        const float v = acc[u][t][r];
-                        if (carry) carry[grow * ldc + col] = v;
-                        norm[grow * ldn + col] = v * inv;
-                    }
-                }
-            }
-        }
-    }
-}
-#endif  // NGCF_LAB
-
-#ifdef NGCF_LAB
-// ---------------------------------------------------------------------------------------------
-// LAB ONLY (-DNGCF_LAB; measured slower than layer_dense_resident_kernel: profiles/r03_dense_il_lab.txt).
-// The resident kernel with the finished tiles leaving UNDER the next tiles' K loop (r03).
-// layer_dense_resident_kernel ends a tile with 128 (256 with a carry) store instructions per wave in one burst and relies on the
-// second wave of the SIMD to keep the matrix pipe busy meanwhile.  Here a SIMD runs ONE wave with the whole register file (512
-// per lane: __launch_bounds__(256), one workgroup per CU) that owns TWO row tiles at a time (64 rows x 128 columns, 128 accumulator
-// registers; a B operand read from LDS feeds eight MFMAs).  The activated values of a finished pair stay in 128 registers (+ 32 row
-// scales) and the K loop of the wave's NEXT pair issues two stores after every group of eight MFMAs (16 groups per chunk, 8
-// chunks: 256 stores), so that a wave's memory traffic is spread evenly over its matrix work instead of alternating with it.  The
-// K loop is unrolled completely (NCH chunks, a template parameter: 8 for d_in 113..128, 9 for 129..144) - the element of the
-// previous pair a group stores is then a fixed register - and there is no branch in it: a store behind a branch makes the
-// compiler wait for every load in flight at the join.  Raw operands are requested one chunk (128 MFMAs = 3.4 us) ahead.  The first
-// pair of a wave runs the loop without stores, the last one leaves in a burst after the loop (with the bounds tests of a partial
-// tile).  Same k order and the same epilogue arithmetic as the other two kernels: bit-identical results.
-// ---------------------------------------------------------------------------------------------
-constexpr int kIlWaves = 4;
-
-template <int NCH, bool CARRY, int LAB = 0>     // LAB (-DNGCF_LAB builds): 1 no stores, 2 no loads, +4 stores to L2-resident rows, +8 staged but not stored - wrong results, timing only
-__global__ __launch_bounds__(kIlWaves * 64) void layer_dense_resident_il_kernel(
-    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
-    const float *__restrict__ Wt, const float *__restrict__ bias2, float leaky, float drop_p, uint64_t drop_seed_in,
-    const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc, float *__restrict__ norm, int64_t ldn)
-{
-    const uint64_t drop_seed = drop_p > 0.f ? resolve_seed(drop_seed_in) : drop_seed_in;
-    constexpr int NT = 4, WCOLS = 128, TP = 1;   // TP: row tiles a wave works on at a time (2: 204 registers spilled)
-    extern __shared__ float Wres[];                 // [NCH * 32][128], the layout of pack_weights_kernel
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, lh = lane >> 5;
-    {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(Wt);
-        f32x4 *dst = reinterpret_cast<f32x4 *>(Wres);
-        constexpr int n4 = NCH * NGCF_KC * WCOLS / 4;
-        for (int i = tid; i < n4; i += kIlWaves * 64) dst[i] = src[i];
-    }
-    __syncthreads();
-    const int64_t n_pairs = (n_rows + 32 * TP - 1) / (32 * TP);
-    const int d4 = (d_in + 3) & ~3;
-    const float *W = Wres + li * NT + lh * 4 * WCOLS;     // the lane's k rows of a group: 4 lh + sx
-    float bz[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) bz[t] = bias2[t * 32 + li];
-    const int64_t pair_step = (int64_t)gridDim.x * kIlWaves;
-    const int ldn_i = (int)ldn, ldc_i = (int)ldc;          // (host: 64 rows of either fit 31 bits)
-    auto row_of = [&](int64_t pr, int u) {                 // the lane's row of tile u of pair pr (past the end: the last row, never stored)
-        int64_t g = pr * (32 * TP) + u * 32 + li;
-        return g < n_rows ? g : n_rows - 1;
-    };
-    // the lane's four 16-byte pieces of chunk C (le_l / e_l: the lane's row + 4 lh): only the LAST chunk can reach past the padded
-    // width (d_in > 16 (NCH - 1)), every other one is the row pointer + a constant
-    auto fetch = [&](auto Cc, const float *le_l, const float *e_l, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {
-        constexpr int C = decltype(Cc)::value;
-        if constexpr (LAB & 2) return;
-        if constexpr (C < NCH - 1) {
-            la = *reinterpret_cast<const f32x4 *>(le_l + C * NGCF_DC);
-            ea = *reinterpret_cast<const f32x4 *>(e_l + C * NGCF_DC);
-            lb = *reinterpret_cast<const f32x4 *>(le_l + C * NGCF_DC + 8);
-            eb = *reinterpret_cast<const f32x4 *>(e_l + C * NGCF_DC + 8);
-        } else {
-            const int ca = C * NGCF_DC + lh * 4, cb = ca + 8;
-            const int cca = (ca < d4 ? ca : d4 - 4) - lh * 4, ccb = (cb < d4 ? cb : d4 - 4) - lh * 4;
-            la = *reinterpret_cast<const f32x4 *>(le_l + cca);
-            ea = *reinterpret_cast<const f32x4 *>(e_l + cca);
-            lb = *reinterpret_cast<const f32x4 *>(le_l + ccb);
-            eb = *reinterpret_cast<const f32x4 *>(e_l + ccb);
-        }
-    };
-    f32x4 la[2][TP], lb[2][TP], ea[2][TP], eb[2][TP];   // the raw pieces of the next two chunks (set = chunk & 1)
-    if constexpr (LAB & 2) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int u = 0; u < TP; ++u) la[q][u] = lb[q][u] = ea[q][u] = eb[q][u] = f32x4{0.01f * lane, 0.02f, 0.03f, 0.04f};
-    }
-    int64_t pair = (int64_t)blockIdx.x * kIlWaves + wave;
-    if (pair >= n_pairs) return;
-#pragma unroll
-    for (int u = 0; u < TP; ++u) {
-        const int64_t g0 = row_of(pair, u);
-        fetch(std::integral_constant<int, 0>{}, LE + g0 * ldLE + lh * 4, Es + g0 * ldE + lh * 4, la[0][u], lb[0][u], ea[0][u], eb[0][u]);
-        fetch(std::integral_constant<int, 1>{}, LE + g0 * ldLE + lh * 4, Es + g0 * ldE + lh * 4, la[1][u], lb[1][u], ea[1][u], eb[1][u]);
-    }
-    f32x16 acc[TP][NT];
-    f32x16 pv[TP][NT];             // the previous pair: activated values, un-normalised (what `carry` receives)
-    float pinv[TP][16];            // and its row scales
-    float *pn = norm, *pc = carry; // the lane's 16 bytes (columns 4 li ..) of row 4 lh of the previous pair's destination
-    float *stg = Wres + NCH * NGCF_KC * WCOLS + wave * 512;   // the wave's two 1 KB slabs (a row pair each) for turning a row
-    f32x4 qn[TP][16], qc[TP][16];  // the previous tile as it leaves: lane = 16 bytes (columns 4 li ..) of row r (+ 4 lh), normalised / carry
-    f32x4 lab_sink = {0.f, 0.f, 0.f, 0.f};
-    const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const bool any_drop = drop_mask || drop_p > 0.f;
-
-    // one chunk: sums / products from the raw pieces, the next chunk requested (NXT: of the next pair), 16 groups of (B operand of
-    // the next group from LDS, eight MFMAs, two stores of the previous pair)
-    auto chunk = [&](auto Cc, auto STc, const float *const (&le_row)[TP], const float *const (&e_row)[TP],
-                     const float *const (&le_nxt)[TP], const float *const (&e_nxt)[TP]) {
-        constexpr int C = decltype(Cc)::value;
-        constexpr bool ST = decltype(STc)::value;
-        f32x4 a4[TP][4];
-        constexpr int S = C & 1;
-#pragma unroll
-        for (int u = 0; u < TP; ++u) {
-            if constexpr (C == NCH - 1) {
-                const int ca = C * NGCF_DC + lh * 4, cb = ca + 8;
-                if (cb + 4 > d_in) {                      // only the last chunk of an odd width
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        if (ca + q >= d_in) la[S][u][q] = 0.f, ea[S][u][q] = 0.f;
-                        if (cb + q >= d_in) lb[S][u][q] = 0.f, eb[S][u][q] = 0.f;
-                    }
-                }
-            }
-            a4[u][0] = la[S][u] + ea[S][u], a4[u][1] = lb[S][u] + eb[S][u], a4[u][2] = la[S][u] * ea[S][u], a4[u][3] = lb[S][u] * eb[S][u];
-            // the chunk after next - of this tile, or chunk 0 / 1 of the wave's next one (NCH odd: the sets swap roles from tile to
-            // tile, which a fixed register assignment cannot follow; then chunk NCH - 1 leaves its set to chunk 1 of the next tile
-            // and chunk 0 is requested by chunk NCH - 2 into the other one ... only for even NCH; odd NCH: see k_loop)
-            if constexpr (C + 2 < NCH) fetch(std::integral_constant<int, C + 2>{}, le_row[u], e_row[u], la[S][u], lb[S][u], ea[S][u], eb[S][u]);
-            else if constexpr ((NCH & 1) == 0)
-                fetch(std::integral_constant<int, C + 2 - NCH>{}, le_nxt[u], e_nxt[u], la[S][u], lb[S][u], ea[S][u], eb[S][u]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const float *wc = W + C * NGCF_KC * WCOLS;
-        f32x4 bv = *reinterpret_cast<const f32x4 *>(wc);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const int kb = g >> 2, sx = g & 3;
-            f32x4 bn = bv;
-            if (g < 15) bn = *reinterpret_cast<const f32x4 *>(wc + (((g + 1) >> 2) * 8 + ((g + 1) & 3)) * WCOLS);
-#pragma unroll
-            for (int u = 0; u < TP; ++u) {
-                acc[u][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.x, acc[u][0], 0, 0, 0);
-                acc[u][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.y, acc[u][1], 0, 0, 0);
-                acc[u][2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.z, acc[u][2], 0, 0, 0);
-                acc[u][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u][kb][sx], bv.w, acc[u][3], 0, 0, 0);
-                if constexpr (ST && C < 8 && !(LAB & 1)) {
-                    // chunk C stores rows r = 2 C and 2 C + 1 (of both halves lh) of the previous tile: four 16-byte stores, four
-                    // groups apart (the values were turned and scaled by activate(): instructions between the MFMAs of this loop
-                    // cost several times what they cost there - tools/dense_il_parts_lab.py)
-                    if ((g & 3) == 2) {
-                        const int js = g >> 3, rs = 2 * C + js, ros = u * 32 + (rs & 3) + 8 * (rs >> 2);
-                        if constexpr (LAB & 8) lab_sink += qn[u][rs];
-                        else if ((g >> 2 & 1) == 0) *reinterpret_cast<f32x4 *>(pn + ros * ldn_i) = qn[u][rs];
-                        else if (CARRY) *reinterpret_cast<f32x4 *>(pc + ros * ldc_i) = qc[u][rs];
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            bv = bn;
-        }
-    };
-    auto k_loop = [&](auto STc, int64_t pr) {
-        const float *le_row[TP], *e_row[TP], *le_nxt[TP], *e_nxt[TP];
-        const int64_t nx = pr + pair_step < n_pairs ? pr + pair_step : pr;   // (the last pair of a wave re-reads its own first chunk)
-#pragma unroll
-        for (int u = 0; u < TP; ++u) {
-            const int64_t g = row_of(pr, u), gn = row_of(nx, u);
-            le_row[u] = LE + g * ldLE + lh * 4, e_row[u] = Es + g * ldE + lh * 4;
-            le_nxt[u] = LE + gn * ldLE + lh * 4, e_nxt[u] = Es + gn * ldE + lh * 4;
-#pragma unroll
-            for (int tt = 0; tt < NT; ++tt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[u][tt][r] = 0.f;
-        }
-        chunk(std::integral_constant<int, 0>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 1>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 2>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 3>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 4>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 5>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 6>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        chunk(std::integral_constant<int, 7>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        if constexpr (NCH > 8) chunk(std::integral_constant<int, 8>{}, STc, le_row, e_row, le_nxt, e_nxt);
-        if constexpr (NCH & 1) {     // odd: both sets are free only now
-#pragma unroll
-            for (int u = 0; u < TP; ++u) {
-                fetch(std::integral_constant<int, 0>{}, le_nxt[u], e_nxt[u], la[0][u], lb[0][u], ea[0][u], eb[0][u]);
-                fetch(std::integral_constant<int, 1>{}, le_nxt[u], e_nxt[u], la[1][u], lb[1][u], ea[1][u], eb[1][u]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    // bias, LeakyReLU, dropout, row scale: acc -> pv, pinv, pn, pc
-    auto activate = [&](int64_t pr) {
-        const int64_t row0 = pr * (32 * TP);
-#pragma unroll
-        for (int u = 0; u < TP; ++u) {
-            float rowss[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
-            if (!any_drop) {
-#pragma unroll
-                for (int tt = 0; tt < NT; ++tt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float v = acc[u][tt][r] + bz[tt];
-                        v = v >= 0.f ? v : leaky * v;
-                        pv[u][tt][r] = v;
-                        rowss[r] = fmaf(v, v, rowss[r]);
-                    }
-            } else {
-#pragma unroll
-                for (int tt = 0; tt < NT; ++tt) {
-                    const int col = tt * 32 + li;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float v = acc[u][tt][r] + bz[tt];
-                        v = v >= 0.f ? v : leaky * v;
-                        const int64_t grow = row0 + u * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-                        else {
-                            const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                            v = h < drop_thr ? 0.f : v * keep_scale;
-                        }
-                        pv[u][tt][r] = v;
-                        rowss[r] = fmaf(v, v, rowss[r]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float s2 = rowss[r];
-                s2 += __shfl_xor(s2, 1);
-                s2 += __shfl_xor(s2, 2);
-                s2 += __shfl_xor(s2, 4);
-                s2 += __shfl_xor(s2, 8);
-                s2 += __shfl_xor(s2, 16);
-                pinv[u][r] = 1.f / fmaxf(sqrtf(s2), 1e-12f);   // F.normalize eps, NGCF.py:144
-            }
-            // a lane holds 4 values of a row 32 columns apart; through a wave-private 1 KB slab of LDS (two, alternating) they
-            // become 16 contiguous bytes per lane: a store instruction then writes two complete rows
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-#pragma unroll
-                for (int tt = 0; tt < NT; ++tt) stg[(r & 1) * 256 + lh * 128 + tt * 32 + li] = pv[u][tt][r];
-                const f32x4 q = *reinterpret_cast<const f32x4 *>(stg + (r & 1) * 256 + lane * 4);
-                qn[u][r] = q * pinv[u][r];
-                if (CARRY) qc[u][r] = q;
-            }
-        }
-        const int64_t dst0 = (LAB & 4) ? ((int64_t)blockIdx.x * kIlWaves + wave) * (32 * TP) : row0;   // lab: every tile to the wave's first rows (L2 hits)
-        pn = norm + (dst0 + 4 * lh) * ldn + 4 * li;
-        if (CARRY) pc = carry + (dst0 + 4 * lh) * ldc + 4 * li;
-    };
-
-    k_loop(std::false_type{}, pair);
-    activate(pair);
-    int64_t prev = pair;
-    for (pair += pair_step; pair < n_pairs; pair += pair_step) {
-        k_loop(std::true_type{}, pair);               // stores pair `prev` (full: it is not the last one) on the way
-        activate(pair);
-        prev = pair;
-    }
-    // the wave's last pair leaves in a burst
-    if constexpr (LAB & 1) {           // (one store keeps the arithmetic alive)
-        f32x4 x = lab_sink;
-#pragma unroll
-        for (int u = 0; u < TP; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x += qn[u][r] + (CARRY ? qc[u][r] : qn[u][r]);
-        if (x.x + x.y + x.z + x.w == 1.2345f) norm[0] = x.x;
-        return;
-    }
-    const int64_t row0 = prev * (32 * TP);
-#pragma unroll
-    for (int u = 0; u < TP; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ro = u * 32 + (r & 3) + 8 * (r >> 2);
-            if (row0 + ro + 4 * lh >= n_rows) continue;
-            *reinterpret_cast<f32x4 *>(pn + ro * ldn_i) = qn[u][r];
-            if (CARRY) *reinterpret_cast<f32x4 *>(pc + ro * ldc_i) = qc[u][r];
-        }
-    if constexpr (LAB & 8)
-        if (lab_sink.x + lab_sink.y + lab_sink.z + lab_sink.w == 1.2345f) norm[1] = lab_sink.x;
-}
-
-#endif  // NGCF_LAB
+// Two resident variants (two row tiles per wave; stores under the next tile's K loop) were slower: profiles/r03_dense_il_lab.txt
 
 // ---------------------------------------------------------------------------------------------
 // 256 / 512 output columns with NO operand in LDS (r02).  At these widths a workgroup of layer_dense_kernel owns 32 (or 64) rows
@@ -1352,7 +902,7 @@ __global__ __launch_bounds__(CW * 64) void layer_dense_direct_kernel(
     }
     // ---- epilogue: bias, LeakyReLU, dropout, row sum of squares (as layer_dense_kernel with RW = 1)
     const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+    const uint32_t drop_thr = msg_drop_thr(drop_p);
     float rowss[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
@@ -1369,8 +919,7 @@ __global__ __launch_bounds__(CW * 64) void layer_dense_direct_kernel(
                 v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
             } else if (drop_p > 0.f) {
                 const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                v = h < drop_thr ? 0.f : v * keep_scale;
+                v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
             }
             acc[t][r] = v;
             rowss[r] = fmaf(v, v, rowss[r]);
@@ -1458,7 +1007,6 @@ __global__ __launch_bounds__(256) void pack_weights_tall_kernel(const float *__r
             bias2[j] = j < d_out ? (b1[j] + b1[j]) + b2[j] : 0.f;   // b1 is added twice, NGCF.py:131,133
 }
 
-template <int LAB>      // LAB (-DNGCF_LAB builds, timing only): 1 no barriers, 2 no row staging, 4 no weight loads in the loop
 __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
     const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
     const float *__restrict__ Wp, const float *__restrict__ bias2, int n_chunks, int n_ct, float leaky, float drop_p,
@@ -1554,10 +1102,8 @@ __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
             if (kb + 2 < 4) read_a(buf, kb + 2, a0);
             else {
                 const int b2 = buf >= 1 ? buf - 1 : 2;                 // (c + 2) % 3
-                if constexpr (!(LAB & 2)) {
-                    store_x(cl(c + 2), b2, x);
-                    load_x(cl(c + 4), x);
-                }
+                store_x(cl(c + 2), b2, x);
+                load_x(cl(c + 4), x);
                 read_a(buf == 2 ? 0 : buf + 1, 0, an);                 // chunk c + 1, written a step ago
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1581,18 +1127,18 @@ __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
     int c = 0;
     for (; c + 1 < n_chunks; c += 2) {
         step(c, buf, b0, x0);
-        if constexpr (!(LAB & 4)) load_b(cl(c + 2), b0);
-        if constexpr (!(LAB & 1)) __syncthreads();
+        load_b(cl(c + 2), b0);
+        __syncthreads();
         buf = buf == 2 ? 0 : buf + 1;
         step(c + 1, buf, b1, x1);
-        if constexpr (!(LAB & 4)) load_b(cl(c + 3), b1);
-        if constexpr (!(LAB & 1)) __syncthreads();
+        load_b(cl(c + 3), b1);
+        __syncthreads();
         buf = buf == 2 ? 0 : buf + 1;
     }
     if (c < n_chunks) step(c, buf, b0, x0);
     // ---- epilogue: bias, LeakyReLU, dropout; the activated value goes to both outputs (row_scale_kernel finishes `norm`)
     const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    const uint32_t drop_thr = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+    const uint32_t drop_thr = msg_drop_thr(drop_p);
     const int col = ct * 32 + li;
     const float bz = bias2[col];
     if (col >= d_out) return;
@@ -1606,8 +1152,7 @@ __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
             v = v >= 0.f ? v : leaky * v;
             if (drop_mask) v *= drop_mask[grow * ldm + col];          // "reference" mode: the noise tensor nn.Dropout drew, NGCF.py:142
             else if (drop_p > 0.f) {
-                const uint32_t h = mix32(drop_seed ^ ((uint64_t)grow * 0x9E3779B97F4A7C15ULL + (uint64_t)col));
-                v = h < drop_thr ? 0.f : v * keep_scale;
+                v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
             }
             if (carry) carry[grow * ldc + col] = v;
             norm[grow * ldn + col] = v;
@@ -1736,14 +1281,9 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     float *Wt = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
     float *bias2 = Wt + (int64_t)n_chunks * NGCF_KC * dop;
     const bool al = (ldLE % 4 == 0) && (ldEs % 4 == 0) && aligned16(LE) && aligned16(Es);
-    // 256 / 512 output columns and at most ONE workgroup per CU (<= 8 192 rows - the Seoul graph has 5 940): operands straight
-    // from global memory / L2, no staging (layer_dense_direct_kernel).  tools/dense_wide_lab.py: 94 vs 114 us at 5 940 x 515 -> 512,
-    // 50 vs 57 us at 256 -> 256, 97 vs 117 us at 8 192 x 512 -> 512; as soon as a CU gets a second workgroup the staged kernel
-    // (two workgroups share a CU's LDS and matrix pipe; the direct kernel runs one wave per SIMD) wins clearly: 170 vs 277 us at
-    // 12 288 rows, 1.08 vs 1.40 ms at 100 K.  NGCF_DENSE_DIRECT=0 / 2: never / at any row count.
-    const int direct_env = ngcf_opts().dense_direct;
-    const bool direct = direct_env && dop >= 256 && al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4 &&
-                        n_rows > 0 && (n_rows <= 8192 || direct_env == 2);
+    // 16-byte aligned rows padded to a multiple of 4 floats: what the tall, resident, split and direct kernels read
+    const bool padded = al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4;
+
     // 256 / 512 output columns as 96-row x 128-column workgroups, three row tiles per wave, the row norm in a second kernel
     // (layer_dense_tall_kernel): 248 workgroups for the Seoul graph's 5 940 rows where the direct kernel has 186.  Measured
     // (tools/dense_wide_lab.py, profiles/r03_dense_wide_lab.txt; tall / direct / staged, us incl. pack and row scale):
@@ -1753,152 +1293,81 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     // dense_tall = 0: never; 2: wherever the shape allows; 1: by these numbers.
     const int tall_env = ngcf_opts().dense_tall;
     const bool tall_pays = dop == 512 ? (n_rows <= 6144 || n_rows > 8192) : (n_rows > 8192 && n_rows <= 131072);
-    if (tall_env && dop >= 256 && al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4 && n_rows > 0 &&
-        (tall_pays || tall_env == 2)) {
+    if (tall_env && dop >= 256 && padded && (tall_pays || tall_env == 2)) {
         const int n_ct = dop / 32;
         pack_weights_tall_kernel<<<dim3((unsigned)(n_chunks * n_ct)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, dop, Wt, bias2);
         LAUNCH_CHECK();
         const int64_t groups = (n_rows + kTallRows - 1) / kTallRows;
-#define NGCF_TALL(L) \
-    layer_dense_tall_kernel<L><<<dim3((unsigned)(groups * (n_ct / 4))), 256, 0, stream>>>( \
-        LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, n_ct, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn)
-#ifdef NGCF_LAB
-        switch (ngcf_opts().dense_il_lab) {
-        case 1: NGCF_TALL(1); break;
-        case 2: NGCF_TALL(2); break;
-        case 3: NGCF_TALL(3); break;
-        case 4: NGCF_TALL(4); break;
-        case 7: NGCF_TALL(7); break;
-        default: NGCF_TALL(0); break;
-        }
-#else
-        NGCF_TALL(0);
-#endif
-#undef NGCF_TALL
+        layer_dense_tall_kernel<<<dim3((unsigned)(groups * (n_ct / 4))), 256, 0, stream>>>(
+            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, n_ct, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
+            norm, ldn);
         LAUNCH_CHECK();
         if (dop == 256) row_scale_kernel<2><<<dim3((unsigned)((n_rows + 3) / 4)), 256, 0, stream>>>(norm, ldn, n_rows, d_out);
         else row_scale_kernel<4><<<dim3((unsigned)((n_rows + 3) / 4)), 256, 0, stream>>>(norm, ldn, n_rows, d_out);
         LAUNCH_CHECK();
         return NGCF_OK;
     }
+
+    // Weights resident in LDS, no barriers: large row counts at the 128-wide shapes, from two tiles per wave on.  dense_resident
+    // = 4: the bf16 three-way split (layer_dense_split_kernel); 1 (any other non-zero value): the fp32 layer_dense_resident_kernel
+    // (128 -> 128, resident / staged us: 65 536 rows 59 / 59, 98 304 rows 95 / 85, 131 072 rows 96 / 104, 262 144 rows 184 / 212,
+    // C3's 1.1 M rows 633 / 780); 0: the staged kernel.
+    const int resident = ngcf_opts().dense_resident;
+    const int64_t lds_bytes = (int64_t)n_chunks * NGCF_KC * 128 * (int64_t)sizeof(float);
+    const bool resident_fits = resident && dop == 128 && padded && lds_bytes <= 150 * 1024 &&
+                               n_rows >= (int64_t)ngcf_opts().dense_resident_min_rows;
     auto pack_fp32 = [&](int nt) {  // the fp32 kernels' packed weights, nt tiles per wave (the split kernel packs its own)
         pack_weights_kernel<<<dim3((unsigned)(n_chunks * (dop / 32))), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks, dop,
                                                                                         nt, Wt, bias2);
         return hipGetLastError();
     };
-#define NGCF_DENSE(RW, CW, NT) \
-    return launch_dense<RW, CW, NT>(al, n_rows, LE, ldLE, Es, ldEs, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, \
-                                    drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream)
-    {
-        // weights resident in LDS, no barriers (layer_dense_resident_kernel): large row counts at the 128-wide shapes, from two
-        // tiles per wave on (128 -> 128, resident / staged us: 65 536 rows 59 / 59, 98 304 rows 95 / 85, 131 072 rows 96 / 104,
-        // 262 144 rows 184 / 212, C3's 1.1 M rows 633 / 780; NGCF_DENSE_RESIDENT=0 keeps the staged kernel)
-        const int resident = ngcf_opts().dense_resident;
-        const int64_t lds_bytes = (int64_t)n_chunks * NGCF_KC * 128 * (int64_t)sizeof(float);
-        if (resident && dop == 128 && al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4 &&
-            lds_bytes <= 150 * 1024 && n_rows >= (int64_t)ngcf_opts().dense_resident_min_rows) {
-            static bool attr_set[kMaxDevices] = {};      // the attribute is per device
-            const int dev_i = current_device_slot();
-            if (resident == 4) {
-                // the bf16 three-way split (layer_dense_split_kernel): bias at the start of the workspace, then parts h + m of
-                // every chunk (the LDS image), then part l
-                static bool split_set[kMaxDevices] = {};
-                if (!split_set[dev_i]) {
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_split_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    split_set[dev_i] = true;
-                }
-                float *sbias = Wt;
-                bf16x8 *whm = reinterpret_cast<bf16x8 *>(Wt + 128);
-                bf16x8 *wl = whm + (int64_t)n_chunks * 1024;
-                pack_weights_split_kernel<<<dim3((unsigned)(n_chunks * 2)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks,
-                                                                                              whm, wl, sbias);
-                LAUNCH_CHECK();
-                layer_dense_split_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)n_chunks * 16 * 1024, stream>>>(
-                    LE, ldLE, Es, ldEs, n_rows, d_in, d_out, whm, wl, sbias, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask,
-                    carry, ldc, norm, ldn);
-                LAUNCH_CHECK();
-                return NGCF_OK;
-            }
-            // the resident kernels read four column tiles per lane, also where small_rows picked 32-row tiles for the staged
-            // kernel (a dense_resident_min_rows at or below 16 384 rows)
-            HIP_TRY(pack_fp32(4));
-            if (!attr_set[dev_i]) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_set[dev_i] = true;
-            }
-#ifdef NGCF_LAB
-            if (resident == 3) {
-                static bool r2_set = false;
-                if (!r2_set) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    r2_set = true;
-                }
-                layer_dense_resident2_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)lds_bytes, stream>>>(
-                    LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
-                    norm, ldn);
-                LAUNCH_CHECK();
-                return NGCF_OK;
-            }
-#endif
-#ifdef NGCF_LAB
-            // resident == 2: the finished tile leaves under the next tile's K loop (layer_dense_resident_il_kernel; full 128
-            // output columns, 8 or 9 chunks)
-            if (resident == 2 && d_out == 128 && (n_chunks == 8 || n_chunks == 9) && ldn < (1 << 24) && ldc < (1 << 24) && ldn % 4 == 0 &&
-                aligned16(norm) && (!carry || (ldc % 4 == 0 && aligned16(carry)))) {
-                const int64_t il_lds = lds_bytes + kIlWaves * 2048;      // + two 1 KB slabs per wave
-#define NGCF_IL(NCH, CARRY) \
-    do { \
-        static bool il_set[kMaxDevices] = {}; \
-        if (!il_set[dev_i]) { \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_il_kernel<NCH, CARRY>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            il_set[dev_i] = true; \
-        } \
-        layer_dense_resident_il_kernel<NCH, CARRY><<<dim3(kResWGs), kIlWaves * 64, (size_t)il_lds, stream>>>( \
-            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn); \
-    } while (0)
-#define NGCF_IL_LAB(L) \
-    layer_dense_resident_il_kernel<8, true, L><<<dim3(kResWGs), kIlWaves * 64, (size_t)il_lds, stream>>>( \
-        LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn)
-                if (const int lab = ngcf_opts().dense_il_lab; lab && n_chunks == 8 && carry) {
-                    static bool lab_set = false;
-                    if (!lab_set) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_il_kernel<8, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_il_kernel<8, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_il_kernel<8, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_il_kernel<8, true, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_il_kernel<8, true, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                        lab_set = true;
-                    }
-                    switch (lab) {
-                    case 1: NGCF_IL_LAB(1); break;
-                    case 2: NGCF_IL_LAB(2); break;
-                    case 3: NGCF_IL_LAB(3); break;
-                    case 6: NGCF_IL_LAB(6); break;       // no loads, every store to the wave's first tile
-                    default: NGCF_IL_LAB(10); break;     // no loads, the stored values formed (LDS round trip, scaling) but not stored
-                    }
-                    LAUNCH_CHECK();
-                    return NGCF_OK;
-                }
-#undef NGCF_IL_LAB
-                if (n_chunks == 8) { if (carry) NGCF_IL(8, true); else NGCF_IL(8, false); }
-                else { if (carry) NGCF_IL(9, true); else NGCF_IL(9, false); }
-#undef NGCF_IL
-                LAUNCH_CHECK();
-                return NGCF_OK;
-            }
-#endif
-            layer_dense_resident_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)lds_bytes, stream>>>(
-                LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
-                norm, ldn);
-            LAUNCH_CHECK();
-            return NGCF_OK;
+    if (resident_fits && resident == 4) {
+        // bias at the start of the workspace, then parts h + m of every chunk (the LDS image), then part l
+        static bool split_set[kMaxDevices] = {};      // the attribute is per device
+        const int dev_i = current_device_slot();
+        if (!split_set[dev_i]) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_split_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            split_set[dev_i] = true;
         }
+        float *sbias = Wt;
+        bf16x8 *whm = reinterpret_cast<bf16x8 *>(Wt + 128);
+        bf16x8 *wl = whm + (int64_t)n_chunks * 1024;
+        pack_weights_split_kernel<<<dim3((unsigned)(n_chunks * 2)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks,
+                                                                                      whm, wl, sbias);
+        LAUNCH_CHECK();
+        layer_dense_split_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)n_chunks * 16 * 1024, stream>>>(
+            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, whm, wl, sbias, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask,
+            carry, ldc, norm, ldn);
+        LAUNCH_CHECK();
+        return NGCF_OK;
     }
+    if (resident_fits) {
+        // four column tiles per lane, also where small_rows picked 32-row tiles for the staged kernel (a dense_resident_min_rows
+        // at or below 16 384 rows)
+        HIP_TRY(pack_fp32(4));
+        static bool attr_set[kMaxDevices] = {};
+        const int dev_i = current_device_slot();
+        if (!attr_set[dev_i]) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_set[dev_i] = true;
+        }
+        layer_dense_resident_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)lds_bytes, stream>>>(
+            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
+            norm, ldn);
+        LAUNCH_CHECK();
+        return NGCF_OK;
+    }
+
     HIP_TRY(pack_fp32(small_rows ? 1 : dop <= 128 ? dop / 32 : 4));
-    if (direct) {
+    // 256 / 512 output columns and at most ONE workgroup per CU (<= 8 192 rows - the Seoul graph has 5 940): operands straight
+    // from global memory / L2, no staging (layer_dense_direct_kernel).  tools/dense_wide_lab.py: 94 vs 114 us at 5 940 x 515 -> 512,
+    // 50 vs 57 us at 256 -> 256, 97 vs 117 us at 8 192 x 512 -> 512; as soon as a CU gets a second workgroup the staged kernel
+    // (two workgroups share a CU's LDS and matrix pipe; the direct kernel runs one wave per SIMD) wins clearly: 170 vs 277 us at
+    // 12 288 rows, 1.08 vs 1.40 ms at 100 K.  NGCF_DENSE_DIRECT=0 / 2: never / at any row count.
+    const int direct_env = ngcf_opts().dense_direct;
+    if (direct_env && dop >= 256 && padded && (n_rows <= 8192 || direct_env == 2)) {
         const int64_t blocks = (n_rows + 31) / 32;
         if (dop == 256)
             layer_dense_direct_kernel<2, 4><<<dim3((unsigned)blocks), 128, 0, stream>>>(
@@ -1911,6 +1380,11 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         LAUNCH_CHECK();
         return NGCF_OK;
     }
+
+    // the staged kernel (layer_dense_kernel)
+#define NGCF_DENSE(RW, CW, NT) \
+    return launch_dense<RW, CW, NT>(al, n_rows, LE, ldLE, Es, ldEs, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, \
+                                    drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream)
     if (small_rows) NGCF_DENSE(1, 4, 1);
     switch (dop) {
     case 32: NGCF_DENSE(4, 1, 1);

@@ -112,12 +112,9 @@ int build_part(const ngcf_csr *c, const ngcf_csr::RowGroup &grp, bool force, hip
     if (!force && nnz < ((int64_t)1 << 22)) return NGCF_OK;          // small products are launch-bound, not L2-bound
     // workgroup shape: 16 waves x 36 rows.  (Round 1 ran the parts that need three or more row passes as 8 x 72: fewer,
     // longer wave tasks fetched 30 % less.  With the lag-driven wave priorities of the kernel 16 waves are faster there
-    // too - C3 user rows 1.60 vs 1.93 ms, profiles/r02_swept_lab.txt.)  Lab builds (-DNGCF_LAB) keep the 8-wave shape behind the option swept_waves.
+    // too - C3 user rows 1.60 vs 1.93 ms, profiles/r02_swept_lab.txt.)
     const int64_t cap = (int64_t)kSweptWGs * kLdsRows;               // output rows resident in LDS at a time
-    int waves = 16;
-#ifdef NGCF_LAB
-    if (ngcf_opts().swept_waves == 8) waves = 8;                      // the 8 x 72 shape is a lab instantiation
-#endif
+    const int waves = 16;
     const int RW = kLdsRows / waves;
     const int64_t n_wave_slots = (int64_t)kSweptWGs * waves;
     if (!force) {
@@ -166,7 +163,7 @@ int build_part(const ngcf_csr *c, const ngcf_csr::RowGroup &grp, bool force, hip
     // within +-2 % of the same entry count.  That alone leaves WHERE in the table a task's entries lie to chance, and the
     // sweep pays for it: a wave whose rows happen to hold few entries in the first half of the table runs ahead of the
     // others by (missing entries) / (entries per column) - on the C3 item rows sigma = 1.1 MiB of table slice, 4 096 waves
-    // spread over ~10 MiB against a 4 MiB L2 (measured with tools/swept_trace_lab.py, profiles/r02_swept_trace.txt; a table
+    // spread over ~10 MiB against a 4 MiB L2 (measured: profiles/r02_swept_trace.txt; a table
     // row is then fetched again for the late waves).  So inside buckets of kDealBucket neighbouring (task, piece) pairs of a
     // level - equal loads to within a fraction of a percent - the pairing is chosen to cancel the low-order cosine moments
     // of every task's entry positions (position = share of all entries left of the column, so that a uniform sweep is the
@@ -554,13 +551,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #endif
 
 // RW accumulator rows per wave, NW waves per workgroup (NW*RW*256 B of LDS)
-// DBG: every kDbgEvery chunks a wave stores (s_memrealtime, column it is gathering) into `dbg` - the sweep-spread
-// trace of tools/swept_trace_lab.py (NGCF_SWEPT_TRACE=<file>); the product never runs this instantiation otherwise
-constexpr int kDbgEvery = 2, kDbgSamples = 512;
-// One launch can take up to kMaxLaunchParts parts (row groups) of a product one after the other: a workgroup that has finished
+// The kernel can take up to kMaxLaunchParts parts (row groups) of a product one after the other: a workgroup that has finished
 // its share of the first goes straight on to the second, so the end-of-part stragglers (the last waves finish 5-8 % after the
 // first, profiles/r02_swept_trace.txt) would cost once per product instead of once per part; the sweep steps are numbered
-// through, so the XCD counters need no reset in between.  Off by default (launch_swept: measured slower).
+// through, so the XCD counters need no reset in between.  launch_swept passes one part per launch (merging measured slower).
 constexpr int kMaxLaunchParts = 4;
 struct SweptPartArgs {
     const int64_t *tptr;
@@ -579,11 +573,11 @@ struct SweptLaunch {
 // DROP: device-mode node dropout (common.h, EdgeDrop): a lane tests the entry it holds when it loads it - row from the wave's
 // table of matrix rows (one ds_bpermute), column from the packed entry - and zeroes the value of a dropped entry; the gather of
 // a dropped entry still happens (the round structure is fixed by the plan), its product is 0.
-template <int LPE, int RW, int NW, bool DBG, bool DROP>
+template <int LPE, int RW, int NW, bool DROP>
 __global__ __launch_bounds__(NW * 64) void spmm_swept_kernel(SweptLaunch L, int n_slices, const float *__restrict__ E,
                                                              int64_t ldE, float *__restrict__ out, int64_t ldo, int dp, unsigned *bar,
-                                                             int max_spin, int sync_k, unsigned prio_cols, int prio_graded, int nt_flags,
-                                                             unsigned long long *__restrict__ dbg, EdgeDrop dr_in)
+                                                             int max_spin, int sync_k, unsigned prio_cols, int prio_graded,
+                                                             EdgeDrop dr_in)
 {
     const EdgeDropR dr = resolve_drop(dr_in);
     constexpr int kSW = LPE * 4, kEPR = 64 / LPE, kCH = 16 * kEPR;
@@ -609,9 +603,6 @@ __global__ __launch_bounds__(NW * 64) void spmm_swept_kernel(SweptLaunch L, int 
     int perm = L.part[0].lead;                  // this wave's copy of perm_lds
     int step0 = 0;                              // sweep steps of the passes before this one
     const unsigned ld_bytes = (unsigned)ldE * 4u;
-    int dbg_n = 0, dbg_chunk = 0;
-    unsigned long long *dbg_w = DBG ? dbg + ((size_t)blockIdx.x * NW + wave) * (2 * kDbgSamples + 2) : nullptr;
-    if (DBG && lane == 0) dbg_w[0] = xcc_id;
     int sweep_no = 0;                           // sweeps (row pass x slice) so far, over all parts
     for (int pi = 0; pi < L.n_parts; ++pi) {
     const int64_t *__restrict__ tptr = L.part[pi].tptr;
@@ -684,18 +675,8 @@ __global__ __launch_bounds__(NW * 64) void spmm_swept_kernel(SweptLaunch L, int 
             auto load_entries = [&](int64_t pos, int &pk, float &v) {
                 const int64_t idx = pos + held;
                 const int64_t idc = idx < end ? idx : end - 1;
-                int pk_l;
-                float v_l;
-#ifdef NGCF_LAB
-                if (nt_flags & 1) {              // the entry lists are read once: streaming loads, they should not displace table rows in L2
-                    pk_l = __builtin_nontemporal_load(&e_pack[idc]);
-                    v_l = __builtin_nontemporal_load(&e_val[idc]);
-                } else
-#endif
-                {
-                    pk_l = e_pack[idc];
-                    v_l = e_val[idc];
-                }
+                const int pk_l = e_pack[idc];
+                const float v_l = e_val[idc];
                 pk = idx < end ? pk_l : idle_pk;
                 v = idx < end ? v_l : 0.f;
                 if (DROP) {
@@ -742,7 +723,7 @@ __global__ __launch_bounds__(NW * 64) void spmm_swept_kernel(SweptLaunch L, int 
                     if (prio_cols) {
                         // Inside a workgroup the same few waves fall behind and stay behind (the instruction arbiter serves the
                         // older wave of a SIMD first), up to 4.5 MiB of table on the C3 item rows while the workgroups themselves
-                        // stay within 0.3 MiB of each other (tools/swept_trace_lab.py): a wave that is more than prio_cols
+                        // stay within 0.3 MiB of each other (profiles/r02_swept_trace.txt): a wave that is more than prio_cols
                         // columns behind the front of its workgroup raises its priority, the others run at 0.
                         const unsigned mine = sweep_tag | (unsigned)(__builtin_amdgcn_readfirstlane(pkA) & kColMask);
                         unsigned front = 0;
@@ -757,13 +738,6 @@ __global__ __launch_bounds__(NW * 64) void spmm_swept_kernel(SweptLaunch L, int 
                         } else {
                             if (lag > prio_cols) __builtin_amdgcn_s_setprio(3);
                             else __builtin_amdgcn_s_setprio(0);
-                        }
-                    }
-                    if (DBG) {
-                        if (dbg_chunk++ % kDbgEvery == 0 && dbg_n < kDbgSamples && lane == 0) {
-                            dbg_w[2 + 2 * dbg_n] = __builtin_amdgcn_s_memrealtime();
-                            dbg_w[3 + 2 * dbg_n] = ((unsigned long long)sweep_no << 32) | (unsigned)(pkA & kColMask);
-                            ++dbg_n;
                         }
                     }
                     load_entries(pos + kCH, pkB, vB);                // the next chunk's entries, two gathers ahead
@@ -795,19 +769,13 @@ __global__ __launch_bounds__(NW * 64) void spmm_swept_kernel(SweptLaunch L, int 
                     const int drow = dst[task * RW + r];
                     if (drow != -1) {
                         float *o = drow >= 0 ? out + (int64_t)drow * ldo : partial + (int64_t)(-2 - drow) * dp;
-                        const f32x4 res = *reinterpret_cast<const f32x4 *>(wacc + r * kSW + p * 4);
-#ifdef NGCF_LAB
-                        if (nt_flags & 2) __builtin_nontemporal_store(res, reinterpret_cast<f32x4 *>(o + slice * kSW + p * 4));
-                        else
-#endif
-                        *reinterpret_cast<f32x4 *>(o + slice * kSW + p * 4) = res;
+                        *reinterpret_cast<f32x4 *>(o + slice * kSW + p * 4) = *reinterpret_cast<const f32x4 *>(wacc + r * kSW + p * 4);
                     }
                 }
             }
         }
     }
     }   // parts
-    if (DBG && lane == 0) dbg_w[1] = (unsigned long long)dbg_n;
 }
 
 // kernels + fix-ups of every part; `partial` = workspace base (rows of dp floats)
@@ -833,32 +801,15 @@ int launch_swept(const ngcf_csr *c, const float *E, int64_t ldE, int d, float *o
     const unsigned prio_cols = (unsigned)std::max(0, o.swept_prio_kb) * 1024u / (kSW * 4);
     // graded: priority 1 / 2 / 3 beyond 1x / 2x / 4x the threshold (C3 item rows 1.50 vs 1.61 ms against one step to 3)
     const int prio_graded = o.swept_prio_graded;
-#ifdef NGCF_LAB
-    const int nt_flags = o.swept_nt;                                           // 1: streaming loads of the entry lists, 2: streaming stores of the rows
-    const char *trace = o.swept_trace[0] ? o.swept_trace : nullptr;
-#else
-    const int nt_flags = 0;
-#endif
-    // consecutive parts of the same workgroup shape share a launch
-    // one launch per part by default: taking both halves of C3 in one launch (NGCF_SWEPT_MERGE=1) was measured SLOWER (3.01-3.11
-    // vs 2.96-2.98 ms per product, same box) - the workgroups that start the second part early gather from another table
-    // and take L2 away from the stragglers of the first
-    #ifdef NGCF_LAB
-    const int max_parts = o.swept_merge ? kMaxLaunchParts : 1;
-#else
-    const int max_parts = 1;
-#endif
-    for (size_t p0 = 0; p0 < w.parts.size();) {
+    // one launch per part: taking both halves of C3 in one launch was measured SLOWER (3.01-3.11 vs 2.96-2.98 ms per product,
+    // same box) - the workgroups that start the second part early gather from another table and take L2 away from the
+    // stragglers of the first
+    for (const auto &p : w.parts) {
         SweptLaunch L{};
-        size_t p1 = p0;
-        for (; p1 < w.parts.size() && L.n_parts < max_parts && w.parts[p1].waves == w.parts[p0].waves; ++p1) {
-            const auto &p = w.parts[p1];
-            // sweep steps a wave may run ahead: by the size of the part's table
-            const int lead = std::min(lead_env != -2 ? lead_env : (p.n_win >= 8 ? 2 : 1), kRing - 4);
-            L.part[L.n_parts++] = SweptPartArgs{p.tptr, p.e_pack, p.e_val, p.dst, p.prow, partial ? partial + p.partial_base * (int64_t)dp : nullptr,
-                                                p.n_rowpass, p.n_win, lead};
-        }
-        const int waves = w.parts[p0].waves;
+        // sweep steps a wave may run ahead: by the size of the part's table
+        const int lead = std::min(lead_env != -2 ? lead_env : (p.n_win >= 8 ? 2 : 1), kRing - 4);
+        L.part[L.n_parts++] = SweptPartArgs{p.tptr, p.e_pack, p.e_val, p.dst, p.prow, partial ? partial + p.partial_base * (int64_t)dp : nullptr,
+                                            p.n_rowpass, p.n_win, lead};
         // this stream's block of sweep counters (up to four streams per CSR get one of their own; a fifth shares the last)
         int bi = 0;
         for (; bi < w.barrier_used && w.barrier_owner[bi] != stream; ++bi) {}
@@ -868,52 +819,15 @@ int launch_swept(const ngcf_csr *c, const float *E, int64_t ldE, int d, float *o
         }
         unsigned *bar_blk = w.barrier + (size_t)bi * 32 * 8;
         HIP_TRY(hipMemsetAsync(bar_blk, 0, sizeof(uint32_t) * 32 * 8, stream));
-        unsigned long long *dbg = nullptr;
-#ifdef NGCF_LAB
-        const size_t dbg_words = (size_t)kSweptWGs * waves * (2 * kDbgSamples + 2);
-        if (trace) {
-            HIP_TRY(hipMalloc(&dbg, dbg_words * 8));
-            HIP_TRY(hipMemsetAsync(dbg, 0, dbg_words * 8, stream));
-        }
-#endif
-#define NGCF_SWEPT_LAUNCH(LPE_, RW_, NW_, DBG_, DROP_)                                                                                    \
-    spmm_swept_kernel<LPE_, RW_, NW_, DBG_, DROP_><<<dim3(kSweptWGs), NW_ * 64, 0, stream>>>(L, d / kSW, E, ldE, out, ldo, dp, bar_blk, \
-                                                                                      max_spin, sync_k, prio_cols, prio_graded,    \
-                                                                                      nt_flags, dbg, dr)
-#ifdef NGCF_LAB
-        if (waves == 8) {
-            if (dr.n > 0) NGCF_SWEPT_LAUNCH(16, 72, 8, false, true);
-            else if (trace) NGCF_SWEPT_LAUNCH(16, 72, 8, true, false);
-            else NGCF_SWEPT_LAUNCH(16, 72, 8, false, false);
-        } else if (trace && dr.n == 0) {
-            NGCF_SWEPT_LAUNCH(16, 36, 16, true, false);
-        } else
-#endif
-        if (waves != 16) return fail(NGCF_ERR_ARG, "swept: the plan's workgroup shape (%d waves) is not compiled into this library", waves);
-        else if (w.lpe == 32 && dr.n > 0) NGCF_SWEPT_LAUNCH(32, 18, 16, false, true);
-        else if (w.lpe == 32) NGCF_SWEPT_LAUNCH(32, 18, 16, false, false);
-        else if (dr.n > 0) NGCF_SWEPT_LAUNCH(16, 36, 16, false, true);
-        else NGCF_SWEPT_LAUNCH(16, 36, 16, false, false);
+#define NGCF_SWEPT_LAUNCH(LPE_, RW_, NW_, DROP_)                                                                                    \
+    spmm_swept_kernel<LPE_, RW_, NW_, DROP_><<<dim3(kSweptWGs), NW_ * 64, 0, stream>>>(L, d / kSW, E, ldE, out, ldo, dp, bar_blk, \
+                                                                                max_spin, sync_k, prio_cols, prio_graded, dr)
+        if (w.lpe == 32 && dr.n > 0) NGCF_SWEPT_LAUNCH(32, 18, 16, true);
+        else if (w.lpe == 32) NGCF_SWEPT_LAUNCH(32, 18, 16, false);
+        else if (dr.n > 0) NGCF_SWEPT_LAUNCH(16, 36, 16, true);
+        else NGCF_SWEPT_LAUNCH(16, 36, 16, false);
 #undef NGCF_SWEPT_LAUNCH
         LAUNCH_CHECK();
-#ifdef NGCF_LAB
-        if (trace) {     // lab only: host-synchronous dump, one file per launch
-            const auto &p = w.parts[p0];
-            std::vector<unsigned long long> h(dbg_words);
-            HIP_TRY(hipStreamSynchronize(stream));
-            HIP_TRY(hipMemcpy(h.data(), dbg, dbg_words * 8, hipMemcpyDeviceToHost));
-            (void)hipFree(dbg);
-            char path[512];
-            snprintf(path, sizeof(path), "%s.part%d", trace, (int)p0);
-            if (FILE *f = fopen(path, "wb")) {
-                const long long hdr[6] = {kSweptWGs, p.waves, kDbgSamples, p.win_cols, p.n_win, p.col_lo};
-                fwrite(hdr, sizeof(hdr), 1, f);
-                fwrite(h.data(), 8, h.size(), f);
-                fclose(f);
-            }
-        }
-#endif
-        p0 = p1;
     }
     for (const auto &p : w.parts) {
         if (p.n_heavy == 0) continue;

@@ -49,15 +49,12 @@ for name, (r, c, v, nr) in parts.items():
         ms = timeit(lambda: eng.spmm(csr, E, out=out, ws=ws))
         print(f"{name}: {label:18s} {ms:7.3f} ms  gather {v.numel() * d * 4 / ms / 1e9:6.2f} TB/s", flush=True)
     ref = out.clone()
-    for (kb, every, order), waves, cut in [(k_, w_, c_) for k_ in windows for w_ in (os.environ.get("LAB_WAVES", "0").split(","))
-                                    for c_ in os.environ.get("LAB_CUT", "4").split(",")]:
+    for (kb, every, order), cut in [(k_, c_) for k_ in windows for c_ in os.environ.get("LAB_CUT", "4").split(",")]:
         os.environ["NGCF_SWEPT_WINDOW_KB"] = str(kb)
         _reload_options()
         os.environ["NGCF_SWEPT_SYNC_EVERY"] = every
         _reload_options()
         os.environ["NGCF_SWEPT_ORDER"] = order
-        _reload_options()
-        os.environ["NGCF_SWEPT_WAVES"] = waves
         _reload_options()
         os.environ["NGCF_SWEPT_CUT"] = cut
         _reload_options()
@@ -75,6 +72,6 @@ for name, (r, c, v, nr) in parts.items():
                     _reload_options()
                     ms = timeit(lambda: eng.spmm(csr, E, out=out, ws=ws))
                     err = float((out - ref).abs().max())
-                    print(f"{name}: swept window {kb:5d} KiB x{every} {order} waves {waves:>2s} cut T/{cut} lead {lead:2d} prio {prio:>4s} KiB "
+                    print(f"{name}: swept window {kb:5d} KiB x{every} {order} cut T/{cut} lead {lead:2d} prio {prio:>4s} KiB "
                           f"graded {graded} {ms:7.3f} ms  gather {v.numel() * d * 4 / ms / 1e9:6.2f} TB/s  (plan {tb:.1f} s, max diff {err:.1e})",
                           flush=True)
