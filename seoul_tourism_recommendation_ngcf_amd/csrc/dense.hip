@@ -1,4 +1,22 @@
-// dense.hip - the dense half of a layer on the fp32 matrix cores, and the fused layer entry point.
+// dense.hip - the dense half of a layer on the matrix cores, and the fused layer entry point.
+//
+// Five forward kernels compute the same layer; ngcf_layer_dense_f32 picks one by shape:
+//   layer_dense_kernel           staged: rows of LE / E and a chunk of weights through LDS, one barrier per chunk (any shape)
+//   layer_dense_resident_kernel  persistent, fp32 weights resident in LDS (97-128 columns, many rows)
+//   layer_dense_split_kernel     the same persistent loop on the bf16 matrix cores, exact three-way split (the default there)
+//   layer_dense_direct_kernel    256 / 512 columns, at most one workgroup per CU: no operand in LDS
+//   layer_dense_tall_kernel      256 / 512 columns, 96-row workgroups; row_scale_kernel normalises afterwards
+// What they share is defined once:
+//   tile_row()                     accumulator register -> row of the 32 x 32 tile (all five)
+//   DenseAct                       LeakyReLU and the two dropout forms of one output element (resident, direct)
+//   dense_epilogue<CW, NT, EVAL>   bias, DenseAct, row sums of squares, butterfly, cross-wave exchange, stores (resident, direct; the
+//                                  staged and split kernels keep copies of it for their measured speed - see there)
+//   fetch_pieces() / zero_tail()   a lane's clamped 16-byte reads of its row; columns past d_in zeroed at use (resident,
+//                                  split, direct)
+//   dense_persistent_tiles<SPLIT>  the persistent row-tile loop and its look-ahead (resident, split: only the operands differ)
+//   pack_bias2()                   2*b1 + b2 (the three pack kernels)
+// The fp32 kernels add the k-values of an output element in one order; the epilogue copies and row_scale_kernel (behind tall)
+// repeat the summation order of dense_epilogue by hand: bit-identical results (tests/test_parity_gpu.py).
 #include "common.h"
 #include <type_traits>
 
@@ -21,6 +39,177 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: stays in registers inside lambdas
+
+// bias2[j] = 2*b1[j] + b2[j] for the DOP packed columns (b1 is added twice, NGCF.py:131,133); one workgroup of a pack kernel
+__device__ __forceinline__ void pack_bias2(const float *__restrict__ b1, const float *__restrict__ b2, int d_out, int DOP,
+                                           float *__restrict__ bias2)
+{
+    for (int j = threadIdx.x; j < DOP; j += 256) bias2[j] = j < d_out ? (b1[j] + b1[j]) + b2[j] : 0.f;
+}
+
+// Row of accumulator register r (0..15) in lane half lh (lane >> 5) of a 32 x 32 MFMA tile whose first row is `base` (the column is
+// lane & 31).  The base is added HERE, first, so that the sum keeps one association everywhere (scalar parts first): as
+// base + an int helper the staged and tall kernels compiled to different, slower code.
+template <class T> __device__ __forceinline__ T tile_row(T base, int r, int lh) { return base + (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// What happens to one output element after the bias: LeakyReLU, then message dropout in one of its two forms.
+struct DenseAct {
+    float leaky, drop_p, keep_scale;
+    uint32_t drop_thr;
+    uint64_t drop_seed;            // resolved
+    const float *drop_mask;        // "reference" mode: the noise tensor nn.Dropout drew on the host (0 or 1/(1-p)), NGCF.py:142
+    int64_t ldm, n_rows;
+    int d_out;
+    __device__ __forceinline__ DenseAct(float leaky_, float drop_p_, uint64_t seed, const float *mask, int64_t ldm_, int64_t n_rows_,
+                                        int d_out_)
+        : leaky(leaky_), drop_p(drop_p_), keep_scale(drop_p_ > 0.f ? 1.f / (1.f - drop_p_) : 1.f), drop_thr(msg_drop_thr(drop_p_)),
+          drop_seed(seed), drop_mask(mask), ldm(ldm_), n_rows(n_rows_), d_out(d_out_)
+    {
+    }
+    __device__ __forceinline__ float operator()(float v, int64_t grow, int col) const
+    {
+        v = v >= 0.f ? v : leaky * v;
+        if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
+        else if (drop_p > 0.f) v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
+        return v;
+    }
+};
+
+// The end of a wave's NT 32 x 32 tiles of one row tile: bias, activation and dropout, the L2 norm of the complete output rows,
+// and the stores of carry (un-normalised, feeds the next layer; may be null) and norm (the normalised all_E block).
+// row0 is the first row of the tile and col0 = cw * NT * 32 the wave's first column; bias(t, col) is the bias of the wave's tile t, column
+// col = col0 + t*32 + li (a load by col in the staged kernel, a register by t where it was read ahead).
+// CW waves side by side share a row and exchange their partial sums through ssq ([32][CW] floats for this row tile; unused
+// when CW == 1) - every wave of the workgroup must arrive.  `full`: every row and column of the tile lies inside the matrix
+// (the caller decides for what unit), and the stores need no per-element tests.  EVAL_ARM: a second copy of the first loop
+// without the per-element tests of the dropout form, taken in eval mode (the direct kernel has one loop).
+// The order of every sum is part of the contract (the fp32 kernels and row_scale_kernel are bit-identical): the squares of a
+// lane's columns as an fma chain from 0 in tile order (t outer, r inner), the xor butterfly 1, 2, 4, 8, 16 over the 32 lanes of
+// a row, the waves in q order.
+struct WaveTile {      // where a wave's NT tiles lie, and the lane in them
+    int64_t row0;      // first row of the row tile
+    int col0, cw;      // the wave's first column (cw * NT * 32) and its place among the CW waves that share the rows
+    int li, lh;        // lane & 31 (column within a tile), lane >> 5 (see tile_row)
+};
+template <int CW, int NT, bool EVAL_ARM, class Bias>
+__device__ __forceinline__ void dense_epilogue(f32x16 (&acc)[NT], Bias bias, const DenseAct &act, const WaveTile &w, float *ssq,
+                                               bool full, float *carry, int64_t ldc, float *norm, int64_t ldn)
+{
+    const int64_t row0 = w.row0;
+    const int col0 = w.col0, cw = w.cw, li = w.li, lh = w.lh;
+    float rowss[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
+    if (EVAL_ARM && !act.drop_mask && !(act.drop_p > 0.f)) {   // eval mode / no message dropout
+        const float leaky = act.leaky;
+        // the same loop without the per-element tests of the dropout form
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int col = col0 + t * 32 + li;
+            const float bz = bias(t, col);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = acc[t][r] + bz;
+                v = v >= 0.f ? v : leaky * v;
+                acc[t][r] = v;
+                rowss[r] = fmaf(v, v, rowss[r]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int col = col0 + t * 32 + li;
+            const float bz = bias(t, col);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = act(acc[t][r] + bz, tile_row(row0, r, lh), col);
+                acc[t][r] = v;
+                rowss[r] = fmaf(v, v, rowss[r]);
+            }
+        }
+    }
+    // reduce over the 32 lanes that share a row (lanes li = 0..31 within each half)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float s = rowss[r];
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        s += __shfl_xor(s, 4);
+        s += __shfl_xor(s, 8);
+        s += __shfl_xor(s, 16);
+        rowss[r] = s;
+    }
+    if constexpr (CW > 1) {
+        if (li == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ssq[tile_row(0, r, lh) * CW + cw] = rowss[r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float s = 0.f;
+#pragma unroll
+            for (int q = 0; q < CW; ++q) s += ssq[tile_row(0, r, lh) * CW + q];
+            rowss[r] = s;
+        }
+    }
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
+            float *nrow = norm + tile_row(row0, r, lh) * ldn + col0 + li;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) nrow[t * 32] = acc[t][r] * inv;
+        }
+        if (carry) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float *crow = carry + tile_row(row0, r, lh) * ldc + col0 + li;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) crow[t * 32] = acc[t][r];
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int64_t grow = tile_row(row0, r, lh);
+        if (grow >= act.n_rows) continue;
+        const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int col = col0 + t * 32 + li;
+            if (col < act.d_out) {
+                const float v = acc[t][r];
+                if (carry) carry[grow * ldc + col] = v;
+                norm[grow * ldn + col] = v * inv;
+            }
+        }
+    }
+}
+
+// A lane's two 16-byte pieces of LE and of E at columns ca and cb of its row.  Columns past d_in (d4 = d_in rounded up to 4) are
+// re-read from the row's last float4, so the loads are unconditional, and zero_tail() turns them into zeros at USE: zeroed here,
+// the loads would be waited for right where they are issued.
+__device__ __forceinline__ void fetch_pieces(const float *le_row, const float *e_row, int ca, int cb, int d4, f32x4 &la, f32x4 &lb,
+                                             f32x4 &ea, f32x4 &eb)
+{
+    const int cca = ca < d4 ? ca : d4 - 4, ccb = cb < d4 ? cb : d4 - 4;
+    la = *reinterpret_cast<const f32x4 *>(le_row + cca);
+    ea = *reinterpret_cast<const f32x4 *>(e_row + cca);
+    lb = *reinterpret_cast<const f32x4 *>(le_row + ccb);
+    eb = *reinterpret_cast<const f32x4 *>(e_row + ccb);
+}
+__device__ __forceinline__ void zero_tail(int ca, int cb, int d_in, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb)   // ca < cb
+{
+    if (cb + 4 > d_in) {                          // only the last chunk of a width that is not a multiple of 16
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (ca + q >= d_in) la[q] = 0.f, ea[q] = 0.f;
+            if (cb + q >= d_in) lb[q] = 0.f, eb[q] = 0.f;
+        }
+    }
+}
 
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float *__restrict__ W1, const float *__restrict__ b1,
                                                            const float *__restrict__ W2, const float *__restrict__ b2, int d_in,
@@ -48,9 +237,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float *__restri
         const int kl = idx / 32, w = idx % 32;
         Wt[((int64_t)chunk * NGCF_KC + kl) * DOP + g * 32 + w] = tile[kl][w];
     }
-    if (blockIdx.x == 0)
-        for (int j = threadIdx.x; j < DOP; j += 256)
-            bias2[j] = j < d_out ? (b1[j] + b1[j]) + b2[j] : 0.f;   // b1 is added twice, NGCF.py:131,133
+    if (blockIdx.x == 0) pack_bias2(b1, b2, d_out, DOP, bias2);
 }
 
 #ifndef NGCF_DENSE_WAVES_PER_EU
@@ -216,6 +403,10 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
         }
     }
 
+    // This kernel keeps its OWN COPY of dense_epilogue (same sums in the same order), which compiles to the parent's code.
+    // Through the shared function, and with tile_row() still adding the base outside, the 32- and 64-column shapes at 1 M
+    // rows measured 2.6 % and 2.4 % slower (122.2 against 119.1 us, 273.5 against 267.1 us, outside the spread:
+    // profiles/r06_dense_shared_epilogue.txt); the shared function with the present tile_row() has not been timed here.
     // ---- epilogue: bias, LeakyReLU, dropout, row sum of squares
     const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
     const uint32_t drop_thr = msg_drop_thr(drop_p);
@@ -241,15 +432,15 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
         for (int t = 0; t < NT; ++t) {
             const int col = (cw * NT + t) * 32 + li;
             const float bz = bias2[col];
-    #pragma unroll
+#pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = acc[t][r] + bz;
                 v = v >= 0.f ? v : leaky * v;
                 if (drop_mask) {       // "reference" mode: the noise tensor nn.Dropout drew on the host (0 or 1/(1-p)), NGCF.py:142
-                    const int64_t grow = row0 + rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int64_t grow = tile_row(row0 + rw * 32, r, lh);
                     v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
                 } else if (drop_p > 0.f) {
-                    const int64_t grow = row0 + rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int64_t grow = tile_row(row0 + rw * 32, r, lh);
                     v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
                 }
                 acc[t][r] = v;
@@ -272,14 +463,14 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
         if (li == 0) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int lr = rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int lr = tile_row(rw * 32, r, lh);
                 ssq[lr * CW + cw] = rowss[r];
             }
         }
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int lr = rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int lr = tile_row(rw * 32, r, lh);
             float s = 0.f;
 #pragma unroll
             for (int q = 0; q < CW; ++q) s += ssq[lr * CW + q];
@@ -291,7 +482,7 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
     if (row0 + BM <= n_rows && d_out == WCOLS) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t grow = row0 + rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int64_t grow = tile_row(row0 + rw * 32, r, lh);
             const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
             float *nrow = norm + grow * ldn + cw * NT * 32 + li;
 #pragma unroll
@@ -300,7 +491,7 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
         if (carry) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t grow = row0 + rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int64_t grow = tile_row(row0 + rw * 32, r, lh);
                 float *crow = carry + grow * ldc + cw * NT * 32 + li;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) crow[t * 32] = acc[t][r];
@@ -310,7 +501,7 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t grow = row0 + rw * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int64_t grow = tile_row(row0 + rw * 32, r, lh);
         if (grow >= n_rows) continue;
         const float nrm = fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
         const float inv = 1.f / nrm;
@@ -338,205 +529,6 @@ __global__ __launch_bounds__(256, NGCF_DENSE_WAVES_PER_EU) void layer_dense_kern
 // ---------------------------------------------------------------------------------------------
 constexpr int kResWaves = 8, kResWGs = 256;
 
-__global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident_kernel(
-    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
-    const float *__restrict__ Wt, const float *__restrict__ bias2, int n_chunks, float leaky, float drop_p, uint64_t drop_seed_in,
-    const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc, float *__restrict__ norm, int64_t ldn)
-{
-    const uint64_t drop_seed = drop_p > 0.f ? resolve_seed(drop_seed_in) : drop_seed_in;
-    constexpr int NT = 4, WCOLS = 128;
-    extern __shared__ float Wres[];                 // [n_chunks * 32][128], the layout of pack_weights_kernel
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int li = lane & 31, lh = lane >> 5;
-    {   // prologue: the whole packed weight matrix, once per workgroup
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(Wt);
-        f32x4 *dst = reinterpret_cast<f32x4 *>(Wres);
-        const int n4 = n_chunks * NGCF_KC * WCOLS / 4;
-        for (int i = tid; i < n4; i += kResWaves * 64) dst[i] = src[i];
-    }
-    __syncthreads();
-    const int64_t n_tiles = (n_rows + 31) / 32;
-    const int d4 = (d_in + 3) & ~3;
-    const float *W = Wres + li * NT;
-    float bz[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) bz[t] = bias2[t * 32 + li];
-    // Stores and loads share one in-order counter (vmcnt), so a wave that stores its finished tile and THEN asks for the first
-    // chunks of its next tile waits for all 256 stores to be acknowledged before its first MFMA: the per-tile cost that no
-    // staggering of the waves could hide.  The first two chunks of the next tile are therefore requested BEFORE the epilogue of
-    // the current one; by the time anything younger than the stores is waited for, two chunks of MFMAs have passed.
-    const int last = n_chunks - 1;
-    const int64_t tile_step = (int64_t)gridDim.x * kResWaves;
-    auto row_of = [&](int64_t t) {                 // the lane's row of tile t (rows past the end re-read the last row, never stored)
-        int64_t g = t * 32 + li;
-        return g < n_rows ? g : n_rows - 1;
-    };
-    // the lane's four 16-byte pieces of a chunk: LE and E at columns c*16 + lh*4 (a) and c*16 + 8 + lh*4 (b); columns past
-    // d_in are re-read from the row's last float4 and zeroed
-    auto fetch = [&](const float *le_row, const float *e_row, int c, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {
-        const int ca = c * NGCF_DC + lh * 4, cb = ca + 8;
-        const int cca = ca < d4 ? ca : d4 - 4, ccb = cb < d4 ? cb : d4 - 4;
-        la = *reinterpret_cast<const f32x4 *>(le_row + cca);
-        ea = *reinterpret_cast<const f32x4 *>(e_row + cca);
-        lb = *reinterpret_cast<const f32x4 *>(le_row + ccb);
-        eb = *reinterpret_cast<const f32x4 *>(e_row + ccb);
-    };
-    // Two chunks of look-ahead in two fixed register sets (no rotation copies - a copy of a register that is still being
-    // loaded is a wait): the sums and products of a chunk are formed first, which frees its set for the chunk after next.
-    // Every prefetch is UNCONDITIONAL (past the end the last chunk is read again and never used): behind a branch the
-    // compiler cannot count the loads in flight and waits for all of them (s_waitcnt vmcnt(0)) at the next use - the
-    // look-ahead then exists in the source only.  The odd last chunk is peeled off the loop for the same reason.
-    f32x4 la0, lb0, ea0, eb0, la1, lb1, ea1, eb1;
-    int64_t tile = (int64_t)blockIdx.x * kResWaves + wave;
-    {
-        const int64_t g0 = row_of(tile < n_tiles ? tile : 0);
-        fetch(LE + g0 * ldLE, Es + g0 * ldE, 0, la0, lb0, ea0, eb0);
-        fetch(LE + g0 * ldLE, Es + g0 * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
-    }
-    for (; tile < n_tiles; tile += tile_step) {
-        const int64_t row0 = tile * 32;
-        const int64_t grow_l = row_of(tile);
-        const float *le_row = LE + grow_l * ldLE, *e_row = Es + grow_l * ldE;
-        f32x16 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        // sums and products of a chunk from its raw pieces; the zeroing of the columns past d_in happens HERE, at use - in
-        // fetch() it would make the loads wait right where they are issued
-        auto form = [&](int c, f32x4 la, f32x4 lb, f32x4 ea, f32x4 eb, f32x4 (&a4)[4]) {
-            const int ca = c * NGCF_DC + lh * 4, cb = ca + 8;
-            if (cb + 4 > d_in) {                      // only the last chunk of an odd width
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (ca + q >= d_in) la[q] = 0.f, ea[q] = 0.f;
-                    if (cb + q >= d_in) lb[q] = 0.f, eb[q] = 0.f;
-                }
-            }
-            a4[0] = la + ea, a4[1] = lb + eb, a4[2] = la * ea, a4[3] = lb * eb;   // k-blocks: sum 0-7, sum 8-15, product 0-7, product 8-15
-        };
-        auto chunk_mfma = [&](int c, const f32x4 (&a4)[4]) {
-            const float *wc = W + (int64_t)c * NGCF_KC * WCOLS;
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-                for (int sx = 0; sx < 4; ++sx) {
-                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(wc + (kb * 8 + lh * 4 + sx) * WCOLS);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kb][sx], bv.x, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kb][sx], bv.y, acc[1], 0, 0, 0);
-                    acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kb][sx], bv.z, acc[2], 0, 0, 0);
-                    acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kb][sx], bv.w, acc[3], 0, 0, 0);
-                }
-            }
-        };
-        int c = 0;
-        for (; c + 1 < n_chunks; c += 2) {
-            {
-                f32x4 a4[4];
-                form(c, la0, lb0, ea0, eb0, a4);
-                fetch(le_row, e_row, c + 2 < last ? c + 2 : last, la0, lb0, ea0, eb0);   // in flight under two chunks of MFMAs
-                __builtin_amdgcn_sched_barrier(0);      // (left alone the compiler sinks these loads to just before their use)
-                chunk_mfma(c, a4);
-            }
-            {
-                f32x4 a4[4];
-                form(c + 1, la1, lb1, ea1, eb1, a4);
-                fetch(le_row, e_row, c + 3 < last ? c + 3 : last, la1, lb1, ea1, eb1);
-                __builtin_amdgcn_sched_barrier(0);
-                chunk_mfma(c + 1, a4);
-            }
-        }
-        if (c < n_chunks) {
-            f32x4 a4[4];
-            form(c, la0, lb0, ea0, eb0, a4);
-            chunk_mfma(c, a4);
-        }
-        {   // the next tile's first two chunks, ahead of this tile's stores (the last tile of a wave re-reads its own)
-            const int64_t gn = row_of(tile + tile_step < n_tiles ? tile + tile_step : tile);
-            fetch(LE + gn * ldLE, Es + gn * ldE, 0, la0, lb0, ea0, eb0);
-            fetch(LE + gn * ldLE, Es + gn * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- epilogue (wave-local): bias, LeakyReLU, dropout, row norm, stores
-        const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-        const uint32_t drop_thr = msg_drop_thr(drop_p);
-        float rowss[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
-        const bool any_drop = drop_mask || drop_p > 0.f;
-        if (!any_drop) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = acc[t][r] + bz[t];
-                    v = v >= 0.f ? v : leaky * v;
-                    acc[t][r] = v;
-                    rowss[r] = fmaf(v, v, rowss[r]);
-                }
-        } else {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = t * 32 + li;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = acc[t][r] + bz[t];
-                    v = v >= 0.f ? v : leaky * v;
-                    const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-                    else v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
-                    acc[t][r] = v;
-                    rowss[r] = fmaf(v, v, rowss[r]);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float s2 = rowss[r];
-            s2 += __shfl_xor(s2, 1);
-            s2 += __shfl_xor(s2, 2);
-            s2 += __shfl_xor(s2, 4);
-            s2 += __shfl_xor(s2, 8);
-            s2 += __shfl_xor(s2, 16);
-            rowss[r] = s2;
-        }
-        if (row0 + 32 <= n_rows && d_out == WCOLS) {          // full tile: no per-element tests
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
-                float *nrow = norm + grow * ldn + li;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) nrow[t * 32] = acc[t][r] * inv;
-            }
-            if (carry) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float *crow = carry + (row0 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ldc + li;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) crow[t * 32] = acc[t][r];
-                }
-            }
-            continue;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (grow >= n_rows) continue;
-            const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = t * 32 + li;
-                if (col < d_out) {
-                    const float v = acc[t][r];
-                    if (carry) carry[grow * ldc + col] = v;
-                    norm[grow * ldn + col] = v * inv;
-                }
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // The same layer on the bf16 matrix cores with an exact three-way split (r05, dense_resident = 4, the default).
 // layer_dense_resident_kernel keeps the fp32 matrix pipe ~71 % busy and is bound by it: v_mfma_f32_32x32x2_f32 runs at 1/16 of
@@ -552,7 +544,7 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident_kernel(
 // ahead.  64-column output panels would fit as well, but a row would then be split over two workgroups and the row norm of the
 // epilogue would need a second pass over the output.  A lane reads the 8 input columns c*16 + 8h .. +7 of its row for both
 // k-steps of a chunk (k-step 0: the sums, against W1; k-step 1: the products, against W2) and splits them in registers.
-// The row loop, look-ahead, epilogue and stores are those of layer_dense_resident_kernel.
+// The row loop, look-ahead, epilogue and stores are those of layer_dense_resident_kernel: dense_persistent_tiles<SPLIT>.
 // ---------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -586,59 +578,80 @@ __global__ __launch_bounds__(256) void pack_weights_split_kernel(const float *__
         Whm[(frag * 2 + 1) * 64 + lane] = m;
         Wl[idx] = l;
     }
-    if (blockIdx.x == 0)
-        for (int j = threadIdx.x; j < 128; j += 256)
-            bias2[j] = j < d_out ? (b1[j] + b1[j]) + b2[j] : 0.f;   // b1 is added twice, NGCF.py:131,133
+    if (blockIdx.x == 0) pack_bias2(b1, b2, d_out, 128, bias2);
 }
 
-__global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
-    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
-    const bf16x8 *__restrict__ Whm, const bf16x8 *__restrict__ Wl, const float *__restrict__ bias2, int n_chunks, float leaky,
-    float drop_p, uint64_t drop_seed_in, const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc,
-    float *__restrict__ norm, int64_t ldn)
+// ---------------------------------------------------------------------------------------------
+// The persistent row-tile loop of layer_dense_resident_kernel (SPLIT = false) and layer_dense_split_kernel (SPLIT = true).
+// Shared: the copy of the LDS-resident weights, row clamping, the two-set look-ahead, the paired chunk loop, the next-tile
+// prefetch and the epilogue.  Per operand form: the lane's columns of a chunk, the A fragments, the MFMAs, and the split
+// kernel's extra stream (part l of the weights, from global memory).
+//   w_lds: what stays in LDS, n_chunks * 16 KB - fp32: [n_chunks * 32][128] floats, the layout of pack_weights_kernel;
+//          split: parts h and m of every chunk, [n_chunks * 2 * 4 * 2][64] bf16x8
+//   Wl:    split only, part l: fragment (k-step s, column tile t) of chunk c at (c*8 + s*4 + t) * 64 + lane
+// ---------------------------------------------------------------------------------------------
+template <bool SPLIT>
+__device__ __forceinline__ void dense_persistent_tiles(const float *LE, int64_t ldLE, const float *Es, int64_t ldE, int64_t n_rows,
+                                                       int d_in, int d_out, const f32x4 *w_lds, const bf16x8 *Wl, const float *bias2,
+                                                       int n_chunks, float leaky, float drop_p, uint64_t drop_seed_in,
+                                                       const float *drop_mask, int64_t ldm, float *carry, int64_t ldc, float *norm,
+                                                       int64_t ldn)
 {
     const uint64_t drop_seed = drop_p > 0.f ? resolve_seed(drop_seed_in) : drop_seed_in;
     constexpr int NT = 4, WCOLS = 128;
-    extern __shared__ bf16x8 Wsh[];                 // parts h and m of every chunk: [n_chunks * 2 * 4 * 2][64]
+    // the lane's input columns of chunk c start at c*16 + lh*CA (pieces a) and CB further (pieces b).  fp32: lh*4 + {0..3} and
+    // 8 + lh*4 + {0..3}, the MFMA A layout of 32x32x2; split: 8h + {0..3} and 8h + {4..7}, both k-steps of 32x32x16
+    constexpr int CA = SPLIT ? 8 : 4, CB = SPLIT ? 4 : 8;
+    using AFrag = std::conditional_t<SPLIT, bf16x8[2][3], f32x4[4]>;   // split: [k-step: sums, products][h, m, l]
+    // part-l fragments per chunk.  fp32 has none: NL = 1 only gives bl0 / bl1 a legal size - they are never written or read
+    // there (fetch_l is empty, chunk_mfma ignores them), which keeps the loop below one text for both forms
+    constexpr int NL = SPLIT ? 8 : 1;
+    extern __shared__ f32x4 Wres[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int li = lane & 31, lh = lane >> 5;
-    for (int i = tid; i < n_chunks * 1024; i += kResWaves * 64) Wsh[i] = Whm[i];
+    for (int i = tid; i < n_chunks * 1024; i += kResWaves * 64) Wres[i] = w_lds[i];   // once per workgroup
     __syncthreads();
     const int64_t n_tiles = (n_rows + 31) / 32;
     const int d4 = (d_in + 3) & ~3;
     float bz[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) bz[t] = bias2[t * 32 + li];
+    // Stores and loads share one in-order counter (vmcnt), so a wave that stores its finished tile and THEN asks for the first
+    // chunks of its next tile waits for all 256 stores to be acknowledged before its first MFMA: the per-tile cost that no
+    // staggering of the waves could hide.  The first two chunks of the next tile are therefore requested BEFORE the epilogue of
+    // the current one; by the time anything younger than the stores is waited for, two chunks of MFMAs have passed.
     const int last = n_chunks - 1;
     const int64_t tile_step = (int64_t)gridDim.x * kResWaves;
-    auto row_of = [&](int64_t t) {
+    auto row_of = [&](int64_t t) {                 // the lane's row of tile t (rows past the end re-read the last row, never stored)
         int64_t g = t * 32 + li;
         return g < n_rows ? g : n_rows - 1;
     };
-    // the lane's 8 input columns of a chunk, c*16 + 8h + {0..3} (a) and {4..7} (b), of LE and E; columns past d_in are re-read
-    // from the row's last float4 and zeroed at use
     auto fetch = [&](const float *le_row, const float *e_row, int c, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {
-        const int ca = c * NGCF_DC + lh * 8, cb = ca + 4;
-        const int cca = ca < d4 ? ca : d4 - 4, ccb = cb < d4 ? cb : d4 - 4;
-        la = *reinterpret_cast<const f32x4 *>(le_row + cca);
-        ea = *reinterpret_cast<const f32x4 *>(e_row + cca);
-        lb = *reinterpret_cast<const f32x4 *>(le_row + ccb);
-        eb = *reinterpret_cast<const f32x4 *>(e_row + ccb);
+        const int ca = c * NGCF_DC + lh * CA;
+        fetch_pieces(le_row, e_row, ca, ca + CB, d4, la, lb, ea, eb);
     };
-    // part l of the weights of a chunk: fragment (k-step s, column tile t) at s*4 + t
-    auto fetch_l = [&](int c, bf16x8 (&bl)[8]) {
+    auto fetch_l = [&](int c, bf16x8 (&bl)[NL]) {
+        if constexpr (SPLIT) {
 #pragma unroll
-        for (int f = 0; f < 8; ++f) bl[f] = Wl[(c * 8 + f) * 64 + lane];
+            for (int f = 0; f < 8; ++f) bl[f] = Wl[(c * 8 + f) * 64 + lane];
+        }
     };
+    // Two chunks of look-ahead in two fixed register sets (no rotation copies - a copy of a register that is still being
+    // loaded is a wait): the A fragments of a chunk are formed first, which frees its set for the chunk after next.  Chunk c
+    // uses set c & 1 of the raw operands (two chunks ahead) and, in the split kernel, of part l (one chunk ahead).
+    // Every prefetch is UNCONDITIONAL (past the end the last chunk is read again and never used): behind a branch the
+    // compiler cannot count the loads in flight and waits for all of them (s_waitcnt vmcnt(0)) at the next use - the
+    // look-ahead then exists in the source only.  The odd last chunk is peeled off the loop for the same reason.
     f32x4 la0, lb0, ea0, eb0, la1, lb1, ea1, eb1;
-    bf16x8 bl0[8], bl1[8];                           // part l of chunks 0, 2, 4, .. and 1, 3, 5, ..
+    bf16x8 bl0[NL], bl1[NL];                         // part l of chunks 0, 2, 4, .. and 1, 3, 5, ..
+    auto fetch_tile = [&](int64_t t) {               // the first two chunks of tile t (and its chunk 0 of part l)
+        const int64_t g = row_of(t);
+        fetch(LE + g * ldLE, Es + g * ldE, 0, la0, lb0, ea0, eb0);
+        fetch(LE + g * ldLE, Es + g * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
+    };
     fetch_l(0, bl0);
     int64_t tile = (int64_t)blockIdx.x * kResWaves + wave;
-    {
-        const int64_t g0 = row_of(tile < n_tiles ? tile : 0);
-        fetch(LE + g0 * ldLE, Es + g0 * ldE, 0, la0, lb0, ea0, eb0);
-        fetch(LE + g0 * ldLE, Es + g0 * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
-    }
+    fetch_tile(tile < n_tiles ? tile : 0);
     for (; tile < n_tiles; tile += tile_step) {
         const int64_t row0 = tile * 32;
         const int64_t grow_l = row_of(tile);
@@ -648,52 +661,62 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        // the A fragments of a chunk: sums (k-step 0) and products (k-step 1), each split into h, m, l
-        auto form = [&](int c, f32x4 la, f32x4 lb, f32x4 ea, f32x4 eb, bf16x8 (&a)[2][3]) {
-            const int ca = c * NGCF_DC + lh * 8, cb = ca + 4;
-            if (cb + 4 > d_in) {                      // only the last chunk of a width that is not a multiple of 16
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (ca + q >= d_in) la[q] = 0.f, ea[q] = 0.f;
-                    if (cb + q >= d_in) lb[q] = 0.f, eb[q] = 0.f;
-                }
-            }
+        // the A fragments of a chunk from its raw pieces (taken by value: the zeroing is of the copies)
+        auto form = [&](int c, f32x4 la, f32x4 lb, f32x4 ea, f32x4 eb, AFrag &a) {
+            const int ca = c * NGCF_DC + lh * CA;
+            zero_tail(ca, ca + CB, d_in, la, lb, ea, eb);
             const f32x4 sa = la + ea, sb = lb + eb, pa = la * ea, pb = lb * eb;
-            split3(__builtin_shufflevector(sa, sb, 0, 1, 2, 3, 4, 5, 6, 7), a[0][0], a[0][1], a[0][2]);
-            split3(__builtin_shufflevector(pa, pb, 0, 1, 2, 3, 4, 5, 6, 7), a[1][0], a[1][1], a[1][2]);
+            if constexpr (SPLIT) {       // sums (k-step 0) and products (k-step 1), each split into h, m, l
+                split3(__builtin_shufflevector(sa, sb, 0, 1, 2, 3, 4, 5, 6, 7), a[0][0], a[0][1], a[0][2]);
+                split3(__builtin_shufflevector(pa, pb, 0, 1, 2, 3, 4, 5, 6, 7), a[1][0], a[1][1], a[1][2]);
+            } else {
+                a[0] = sa, a[1] = sb, a[2] = pa, a[3] = pb;   // k-blocks: sum 0-7, sum 8-15, product 0-7, product 8-15
+            }
         };
-        // the 48 MFMAs of a chunk
-        auto chunk_mfma = [&](int c, const bf16x8 (&a)[2][3], const bf16x8 (&bl)[8]) {
-            const bf16x8 *wc = Wsh + c * 1024 + lane;
+        auto chunk_mfma = [&](int c, const AFrag &a, const bf16x8 (&bl)[NL]) {
+            if constexpr (SPLIT) {       // 48 MFMAs
+                const bf16x8 *wc = reinterpret_cast<const bf16x8 *>(Wres) + c * 1024 + lane;
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const bf16x8 &ah = a[s][0], &am = a[s][1], &al = a[s][2];
+                for (int s = 0; s < 2; ++s) {
+                    const bf16x8 &ah = a[s][0], &am = a[s][1], &al = a[s][2];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {          // one accumulation chain per tile (32x32x16 needs no interleaving)
-                    const bf16x8 bh = wc[((s * 4 + t) * 2 + 0) * 64], bm = wc[((s * 4 + t) * 2 + 1) * 64];
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s * 4 + t], acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
+                    for (int t = 0; t < NT; ++t) {          // one accumulation chain per tile (32x32x16 needs no interleaving)
+                        const bf16x8 bh = wc[((s * 4 + t) * 2 + 0) * 64], bm = wc[((s * 4 + t) * 2 + 1) * 64];
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s * 4 + t], acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
+                    }
+                }
+            } else {                     // 64 MFMAs
+                const float *wc = reinterpret_cast<const float *>(Wres) + li * NT + (int64_t)c * NGCF_KC * WCOLS;
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+                    for (int sx = 0; sx < 4; ++sx) {
+                        const f32x4 bv = *reinterpret_cast<const f32x4 *>(wc + (kb * 8 + lh * 4 + sx) * WCOLS);
+                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kb][sx], bv.x, acc[0], 0, 0, 0);
+                        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kb][sx], bv.y, acc[1], 0, 0, 0);
+                        acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kb][sx], bv.z, acc[2], 0, 0, 0);
+                        acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kb][sx], bv.w, acc[3], 0, 0, 0);
+                    }
                 }
             }
         };
-        // chunk c uses set c & 1 of the raw operands (two chunks ahead) and of part l (one chunk ahead), both unconditional: past
-        // the end the last chunk is re-read; the next tile's chunk 0 of part l is requested with its first rows
         int c = 0;
         for (; c + 1 < n_chunks; c += 2) {
             {
-                bf16x8 a[2][3];
+                AFrag a;
                 form(c, la0, lb0, ea0, eb0, a);
-                fetch(le_row, e_row, c + 2 < last ? c + 2 : last, la0, lb0, ea0, eb0);
+                fetch(le_row, e_row, c + 2 < last ? c + 2 : last, la0, lb0, ea0, eb0);   // in flight under two chunks of MFMAs
                 fetch_l(c + 1, bl1);
-                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);      // (left alone the compiler sinks these loads to just before their use)
                 chunk_mfma(c, a, bl0);
             }
             {
-                bf16x8 a[2][3];
+                AFrag a;
                 form(c + 1, la1, lb1, ea1, eb1, a);
                 fetch(le_row, e_row, c + 3 < last ? c + 3 : last, la1, lb1, ea1, eb1);
                 fetch_l(c + 2 < last ? c + 2 : last, bl0);
@@ -702,95 +725,125 @@ __global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
             }
         }
         if (c < n_chunks) {
-            bf16x8 a[2][3];
+            AFrag a;
             form(c, la0, lb0, ea0, eb0, a);
             chunk_mfma(c, a, bl0);
         }
-        {   // the next tile's first two chunks, ahead of this tile's stores (the last tile of a wave re-reads its own)
-            const int64_t gn = row_of(tile + tile_step < n_tiles ? tile + tile_step : tile);
-            fetch(LE + gn * ldLE, Es + gn * ldE, 0, la0, lb0, ea0, eb0);
-            fetch(LE + gn * ldLE, Es + gn * ldE, last < 1 ? last : 1, la1, lb1, ea1, eb1);
-            fetch_l(0, bl0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- epilogue (wave-local): bias, LeakyReLU, dropout, row norm, stores - as layer_dense_resident_kernel
-        const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-        const uint32_t drop_thr = msg_drop_thr(drop_p);
-        float rowss[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
-        const bool any_drop = drop_mask || drop_p > 0.f;
-        if (!any_drop) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = acc[t][r] + bz[t];
-                    v = v >= 0.f ? v : leaky * v;
-                    acc[t][r] = v;
-                    rowss[r] = fmaf(v, v, rowss[r]);
-                }
+        // the next tile's first two chunks, ahead of this tile's stores (the last tile of a wave re-reads its own)
+        fetch_tile(tile + tile_step < n_tiles ? tile + tile_step : tile);
+        fetch_l(0, bl0);
+        __builtin_amdgcn_sched_barrier(0);
+        // wave-local: a wave owns its 32 rows outright
+        if constexpr (!SPLIT) {
+            // DenseAct is built here, per tile, on purpose: built once above the loop, the split instantiation spilled 25
+            // VGPRs instead of 24 (the compiler hoists the division by itself)
+            const DenseAct act(leaky, drop_p, drop_seed, drop_mask, ldm, n_rows, d_out);
+            const WaveTile w{row0, 0, 0, li, lh};
+            const bool full = row0 + 32 <= n_rows && d_out == WCOLS;
+            dense_epilogue<1, NT, true>(acc, [&](int t, int) { return bz[t]; }, act, w, nullptr, full, carry, ldc, norm, ldn);
         } else {
+            // The split kernel keeps its OWN COPY of dense_epilogue<1, NT, true> (same sums in the same order).  Through the
+            // shared function its schedule after the next-tile prefetch changed and the C3 forward (three layers on this kernel,
+            // eval arm) was slower than the parent in 7 of 8 alternated runs, by 0.09 - 0.18 ms of 10.7 ms
+            // (profiles/r06_dense_shared_epilogue.txt); with the text here the fp32 instantiation in turn spilled 2 VGPRs,
+            // hence the two forms.
+            const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+            const uint32_t drop_thr = msg_drop_thr(drop_p);
+            float rowss[16];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = t * 32 + li;
+            for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
+            const bool any_drop = drop_mask || drop_p > 0.f;
+            if (!any_drop) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = acc[t][r] + bz[t];
-                    v = v >= 0.f ? v : leaky * v;
-                    const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-                    else v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
-                    acc[t][r] = v;
-                    rowss[r] = fmaf(v, v, rowss[r]);
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = acc[t][r] + bz[t];
+                        v = v >= 0.f ? v : leaky * v;
+                        acc[t][r] = v;
+                        rowss[r] = fmaf(v, v, rowss[r]);
+                    }
+            } else {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const int col = t * 32 + li;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = acc[t][r] + bz[t];
+                        v = v >= 0.f ? v : leaky * v;
+                        const int64_t grow = tile_row(row0, r, lh);
+                        if (drop_mask) v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
+                        else v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
+                        acc[t][r] = v;
+                        rowss[r] = fmaf(v, v, rowss[r]);
+                    }
                 }
             }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float s2 = rowss[r];
-            s2 += __shfl_xor(s2, 1);
-            s2 += __shfl_xor(s2, 2);
-            s2 += __shfl_xor(s2, 4);
-            s2 += __shfl_xor(s2, 8);
-            s2 += __shfl_xor(s2, 16);
-            rowss[r] = s2;
-        }
-        if (row0 + 32 <= n_rows && d_out == WCOLS) {          // full tile: no per-element tests
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
-                float *nrow = norm + grow * ldn + li;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) nrow[t * 32] = acc[t][r] * inv;
+                float s2 = rowss[r];
+                s2 += __shfl_xor(s2, 1);
+                s2 += __shfl_xor(s2, 2);
+                s2 += __shfl_xor(s2, 4);
+                s2 += __shfl_xor(s2, 8);
+                s2 += __shfl_xor(s2, 16);
+                rowss[r] = s2;
             }
-            if (carry) {
+            if (row0 + 32 <= n_rows && d_out == WCOLS) {          // full tile: no per-element tests
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    float *crow = carry + (row0 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ldc + li;
+                    const int64_t grow = tile_row(row0, r, lh);
+                    const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
+                    float *nrow = norm + grow * ldn + li;
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) crow[t * 32] = acc[t][r];
+                    for (int t = 0; t < NT; ++t) nrow[t * 32] = acc[t][r] * inv;
                 }
+                if (carry) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float *crow = carry + tile_row(row0, r, lh) * ldc + li;
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) crow[t * 32] = acc[t][r];
+                    }
+                }
+                continue;
             }
-            continue;
-        }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (grow >= n_rows) continue;
-            const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
+            for (int r = 0; r < 16; ++r) {
+                const int64_t grow = tile_row(row0, r, lh);
+                if (grow >= n_rows) continue;
+                const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int col = t * 32 + li;
-                if (col < d_out) {
-                    const float v = acc[t][r];
-                    if (carry) carry[grow * ldc + col] = v;
-                    norm[grow * ldn + col] = v * inv;
+                for (int t = 0; t < NT; ++t) {
+                    const int col = t * 32 + li;
+                    if (col < d_out) {
+                        const float v = acc[t][r];
+                        if (carry) carry[grow * ldc + col] = v;
+                        norm[grow * ldn + col] = v * inv;
+                    }
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(kResWaves * 64) void layer_dense_resident_kernel(
+    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
+    const float *__restrict__ Wt, const float *__restrict__ bias2, int n_chunks, float leaky, float drop_p, uint64_t drop_seed_in,
+    const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc, float *__restrict__ norm, int64_t ldn)
+{
+    dense_persistent_tiles<false>(LE, ldLE, Es, ldE, n_rows, d_in, d_out, reinterpret_cast<const f32x4 *>(Wt), nullptr, bias2,
+                                  n_chunks, leaky, drop_p, drop_seed_in, drop_mask, ldm, carry, ldc, norm, ldn);
+}
+
+__global__ __launch_bounds__(kResWaves * 64) void layer_dense_split_kernel(
+    const float *__restrict__ LE, int64_t ldLE, const float *__restrict__ Es, int64_t ldE, int64_t n_rows, int d_in, int d_out,
+    const bf16x8 *__restrict__ Whm, const bf16x8 *__restrict__ Wl, const float *__restrict__ bias2, int n_chunks, float leaky,
+    float drop_p, uint64_t drop_seed_in, const float *__restrict__ drop_mask, int64_t ldm, float *__restrict__ carry, int64_t ldc,
+    float *__restrict__ norm, int64_t ldn)
+{
+    dense_persistent_tiles<true>(LE, ldLE, Es, ldE, n_rows, d_in, d_out, reinterpret_cast<const f32x4 *>(Whm), Wl, bias2, n_chunks,
+                                 leaky, drop_p, drop_seed_in, drop_mask, ldm, carry, ldc, norm, ldn);
 }
 
 // Two resident variants (two row tiles per wave; stores under the next tile's K loop) were slower: profiles/r03_dense_il_lab.txt
@@ -832,28 +885,18 @@ __global__ __launch_bounds__(CW * 64) void layer_dense_direct_kernel(
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    auto fetch_a = [&](int c, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {
-        const int ca = c * NGCF_DC + lh * 4, cb = ca + 8;
-        const int cca = ca < d4 ? ca : d4 - 4, ccb = cb < d4 ? cb : d4 - 4;
-        la = *reinterpret_cast<const f32x4 *>(le_row + cca);
-        ea = *reinterpret_cast<const f32x4 *>(e_row + cca);
-        lb = *reinterpret_cast<const f32x4 *>(le_row + ccb);
-        eb = *reinterpret_cast<const f32x4 *>(e_row + ccb);
+    auto fetch_a = [&](int c, f32x4 &la, f32x4 &lb, f32x4 &ea, f32x4 &eb) {    // columns c*16 + lh*4 and 8 further, as the fp32 resident kernel
+        const int ca = c * NGCF_DC + lh * 4;
+        fetch_pieces(le_row, e_row, ca, ca + 8, d4, la, lb, ea, eb);
     };
     auto fetch_b = [&](int c, BV (&b)[16]) {
         const float *wc = Wl + (int64_t)c * NGCF_KC * WCOLS;
 #pragma unroll
         for (int q = 0; q < 16; ++q) b[q] = *reinterpret_cast<const BV *>(wc + ((q >> 2) * 8 + (q & 3)) * WCOLS);
     };
-    auto form = [&](int c, f32x4 la, f32x4 lb, f32x4 ea, f32x4 eb, f32x4 (&a4)[4]) {   // zeroing of the columns past d_in at use
-        const int ca = c * NGCF_DC + lh * 4, cb = ca + 8;
-        if (cb + 4 > d_in) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (ca + q >= d_in) la[q] = 0.f, ea[q] = 0.f;
-                if (cb + q >= d_in) lb[q] = 0.f, eb[q] = 0.f;
-            }
-        }
+    auto form = [&](int c, f32x4 la, f32x4 lb, f32x4 ea, f32x4 eb, f32x4 (&a4)[4]) {
+        const int ca = c * NGCF_DC + lh * 4;
+        zero_tail(ca, ca + 8, d_in, la, lb, ea, eb);
         a4[0] = la + ea, a4[1] = lb + eb, a4[2] = la * ea, a4[3] = lb * eb;
     };
     auto chunk_mfma = [&](const f32x4 (&a4)[4], const BV (&b)[16]) {
@@ -866,7 +909,7 @@ __global__ __launch_bounds__(CW * 64) void layer_dense_direct_kernel(
                 for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kb][sx], bv[t], acc[t], 0, 0, 0);
             }
     };
-    // every prefetch unconditional, the odd last chunk peeled off (see layer_dense_resident_kernel)
+    // every prefetch unconditional, the odd last chunk peeled off (see dense_persistent_tiles)
     const int last = n_chunks - 1;
     f32x4 la0, lb0, ea0, eb0, la1, lb1, ea1, eb1;
     BV b0[16], b1[16];
@@ -900,69 +943,13 @@ __global__ __launch_bounds__(CW * 64) void layer_dense_direct_kernel(
         form(c, la0, lb0, ea0, eb0, a4);
         chunk_mfma(a4, b0);
     }
-    // ---- epilogue: bias, LeakyReLU, dropout, row sum of squares (as layer_dense_kernel with RW = 1)
-    const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    const uint32_t drop_thr = msg_drop_thr(drop_p);
-    float rowss[16];
+    // one activation loop and no full-tile store path here, as this kernel always had
+    const DenseAct act(leaky, drop_p, drop_seed, drop_mask, ldm, n_rows, d_out);
+    float bz[NT];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) rowss[r] = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = (cw * NT + t) * 32 + li;
-        const float bz = bias2[col];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = acc[t][r] + bz;
-            v = v >= 0.f ? v : leaky * v;
-            if (drop_mask) {           // "reference" mode: the noise tensor nn.Dropout drew on the host, NGCF.py:142
-                const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                v *= (grow < n_rows && col < d_out) ? drop_mask[grow * ldm + col] : 0.f;
-            } else if (drop_p > 0.f) {
-                const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                v = msg_drop(v, drop_seed, grow, col, drop_thr, keep_scale);
-            }
-            acc[t][r] = v;
-            rowss[r] = fmaf(v, v, rowss[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float s = rowss[r];
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        s += __shfl_xor(s, 4);
-        s += __shfl_xor(s, 8);
-        s += __shfl_xor(s, 16);
-        rowss[r] = s;
-    }
-    if (li == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ssq[((r & 3) + 8 * (r >> 2) + 4 * lh) * CW + cw] = rowss[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < CW; ++q) s += ssq[lr * CW + q];
-        rowss[r] = s;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int64_t grow = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (grow >= n_rows) continue;
-        const float inv = 1.f / fmaxf(sqrtf(rowss[r]), 1e-12f);   // F.normalize eps, NGCF.py:144
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int col = (cw * NT + t) * 32 + li;
-            if (col < d_out) {
-                const float v = acc[t][r];
-                if (carry) carry[grow * ldc + col] = v;
-                norm[grow * ldn + col] = v * inv;
-            }
-        }
-    }
+    for (int t = 0; t < NT; ++t) bz[t] = bias2[(cw * NT + t) * 32 + li];
+    const WaveTile w{row0, cw * NT * 32, cw, li, lh};
+    dense_epilogue<CW, NT, false>(acc, [&](int t, int) { return bz[t]; }, act, w, ssq, /*full=*/false, carry, ldc, norm, ldn);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1002,9 +989,7 @@ __global__ __launch_bounds__(256) void pack_weights_tall_kernel(const float *__r
         const int sx = idx & 3, li = (idx >> 2) & 31, lh = (idx >> 7) & 1, kb = idx >> 8;
         dst[idx] = tile[kb * 8 + lh * 4 + sx][li];
     }
-    if (blockIdx.x == 0)
-        for (int j = threadIdx.x; j < DOP; j += 256)
-            bias2[j] = j < d_out ? (b1[j] + b1[j]) + b2[j] : 0.f;   // b1 is added twice, NGCF.py:131,133
+    if (blockIdx.x == 0) pack_bias2(b1, b2, d_out, DOP, bias2);
 }
 
 __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
@@ -1137,6 +1122,8 @@ __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
     }
     if (c < n_chunks) step(c, buf, b0, x0);
     // ---- epilogue: bias, LeakyReLU, dropout; the activated value goes to both outputs (row_scale_kernel finishes `norm`)
+    // (its own text, not DenseAct, which compiles to the parent's code: with DenseAct and tile_row() adding the base outside,
+    // 100 000 x 512 -> 512 measured 1 042.3 against 1 036.9 us, spread 1.8; DenseAct with the present tile_row() was not timed)
     const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
     const uint32_t drop_thr = msg_drop_thr(drop_p);
     const int col = ct * 32 + li;
@@ -1146,7 +1133,7 @@ __global__ __launch_bounds__(256) void layer_dense_tall_kernel(
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t grow = row0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int64_t grow = tile_row(row0 + m * 32, r, lh);
             if (grow >= n_rows) continue;
             float v = acc[m][r] + bz;
             v = v >= 0.f ? v : leaky * v;
@@ -1231,25 +1218,48 @@ extern "C" int64_t ngcf_dense_workspace_bytes(int d_in, int d_out)
     return align_up(std::max(fp32_packed, split_packed), 256) + 256;
 }
 
-template <int RW, int CW, int NT>
-static int launch_dense(bool al, int64_t n_rows, const float *LE, int64_t ldLE, const float *Es, int64_t ldE, int d_in,
-                        int d_out, const float *Wt, const float *bias2, int n_chunks, float leaky, float drop_p,
-                        uint64_t seed, const float *drop_mask, int64_t ldm, float *carry, int64_t ldc, float *norm, int64_t ldn,
-                        hipStream_t stream)
+// The arguments every forward kernel takes, around the kernel's own weight arguments w... (the kernels keep plain parameter
+// lists: a struct would change every kernel's argument loads).
+struct DenseCall {
+    const float *LE;
+    int64_t ldLE;
+    const float *Es;
+    int64_t ldE, n_rows;
+    int d_in, d_out;
+    float leaky, drop_p;
+    uint64_t drop_seed;
+    const float *drop_mask;
+    int64_t ldm;
+    float *carry;
+    int64_t ldc;
+    float *norm;
+    int64_t ldn;
+    hipStream_t stream;
+    template <class Kernel, class... W> void launch(Kernel kernel, int64_t grid, int block, size_t lds, W... w) const
+    {
+        kernel<<<dim3((unsigned)grid), block, lds, stream>>>(LE, ldLE, Es, ldE, n_rows, d_in, d_out, w..., leaky, drop_p, drop_seed, drop_mask,
+                                                             ldm, carry, ldc, norm, ldn);
+    }
+};
+
+// The persistent kernels keep up to 160 KiB of weights in dynamic LDS: the attribute is per kernel and device, set once.
+template <auto kernel> static hipError_t allow_full_lds()
 {
-    const int64_t blocks = (n_rows + 32 * RW - 1) / (32 * RW);
-    if (blocks == 0) return NGCF_OK;
-    if (al && ldLE >= align_up(d_in, 4) && ldE >= align_up(d_in, 4) && d_in >= 4)   // padded, aligned rows (any d_in)
-        layer_dense_kernel<RW, CW, NT, true, true><<<dim3((unsigned)blocks), 256, 0, stream>>>(
-            LE, ldLE, Es, ldE, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, seed, drop_mask, ldm, carry, ldc, norm, ldn);
-    else if (al)
-        layer_dense_kernel<RW, CW, NT, true, false><<<dim3((unsigned)blocks), 256, 0, stream>>>(
-            LE, ldLE, Es, ldE, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, seed, drop_mask, ldm, carry, ldc, norm, ldn);
-    else
-        layer_dense_kernel<RW, CW, NT, false, false><<<dim3((unsigned)blocks), 256, 0, stream>>>(
-            LE, ldLE, Es, ldE, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, seed, drop_mask, ldm, carry, ldc, norm, ldn);
-    LAUNCH_CHECK();
-    return NGCF_OK;
+    static bool set[kMaxDevices] = {};
+    const int dev_i = current_device_slot();
+    if (set[dev_i]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set[dev_i] = e == hipSuccess;
+    return e;
+}
+
+template <int RW, int CW, int NT>   // the staged kernel; padded: 16-byte aligned rows padded to a multiple of 4 floats (any d_in)
+static void launch_staged(const DenseCall &k, bool al, bool padded, const float *Wt, const float *bias2, int n_chunks)
+{
+    const int64_t blocks = (k.n_rows + 32 * RW - 1) / (32 * RW);
+    if (padded) k.launch(layer_dense_kernel<RW, CW, NT, true, true>, blocks, 256, 0, Wt, bias2, n_chunks);
+    else if (al) k.launch(layer_dense_kernel<RW, CW, NT, true, false>, blocks, 256, 0, Wt, bias2, n_chunks);
+    else k.launch(layer_dense_kernel<RW, CW, NT, false, false>, blocks, 256, 0, Wt, bias2, n_chunks);
 }
 
 extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *Es, int64_t ldEs, int64_t n_rows,
@@ -1283,6 +1293,7 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     const bool al = (ldLE % 4 == 0) && (ldEs % 4 == 0) && aligned16(LE) && aligned16(Es);
     // 16-byte aligned rows padded to a multiple of 4 floats: what the tall, resident, split and direct kernels read
     const bool padded = al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4;
+    const DenseCall call{LE, ldLE, Es, ldEs, n_rows, d_in, d_out, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream};
 
     // 256 / 512 output columns as 96-row x 128-column workgroups, three row tiles per wave, the row norm in a second kernel
     // (layer_dense_tall_kernel): 248 workgroups for the Seoul graph's 5 940 rows where the direct kernel has 186.  Measured
@@ -1298,9 +1309,7 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         pack_weights_tall_kernel<<<dim3((unsigned)(n_chunks * n_ct)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, dop, Wt, bias2);
         LAUNCH_CHECK();
         const int64_t groups = (n_rows + kTallRows - 1) / kTallRows;
-        layer_dense_tall_kernel<<<dim3((unsigned)(groups * (n_ct / 4))), 256, 0, stream>>>(
-            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, n_ct, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
-            norm, ldn);
+        call.launch(layer_dense_tall_kernel, groups * (n_ct / 4), 256, 0, Wt, bias2, n_chunks, n_ct);
         LAUNCH_CHECK();
         if (dop == 256) row_scale_kernel<2><<<dim3((unsigned)((n_rows + 3) / 4)), 256, 0, stream>>>(norm, ldn, n_rows, d_out);
         else row_scale_kernel<4><<<dim3((unsigned)((n_rows + 3) / 4)), 256, 0, stream>>>(norm, ldn, n_rows, d_out);
@@ -1323,22 +1332,14 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     };
     if (resident_fits && resident == 4) {
         // bias at the start of the workspace, then parts h + m of every chunk (the LDS image), then part l
-        static bool split_set[kMaxDevices] = {};      // the attribute is per device
-        const int dev_i = current_device_slot();
-        if (!split_set[dev_i]) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_split_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            split_set[dev_i] = true;
-        }
+        HIP_TRY(allow_full_lds<layer_dense_split_kernel>());
         float *sbias = Wt;
         bf16x8 *whm = reinterpret_cast<bf16x8 *>(Wt + 128);
         bf16x8 *wl = whm + (int64_t)n_chunks * 1024;
         pack_weights_split_kernel<<<dim3((unsigned)(n_chunks * 2)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks,
                                                                                       whm, wl, sbias);
         LAUNCH_CHECK();
-        layer_dense_split_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)n_chunks * 16 * 1024, stream>>>(
-            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, whm, wl, sbias, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask,
-            carry, ldc, norm, ldn);
+        call.launch(layer_dense_split_kernel, kResWGs, kResWaves * 64, (size_t)n_chunks * 16 * 1024, whm, wl, sbias, n_chunks);
         LAUNCH_CHECK();
         return NGCF_OK;
     }
@@ -1346,16 +1347,8 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         // four column tiles per lane, also where small_rows picked 32-row tiles for the staged kernel (a dense_resident_min_rows
         // at or below 16 384 rows)
         HIP_TRY(pack_fp32(4));
-        static bool attr_set[kMaxDevices] = {};
-        const int dev_i = current_device_slot();
-        if (!attr_set[dev_i]) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(layer_dense_resident_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev_i] = true;
-        }
-        layer_dense_resident_kernel<<<dim3(kResWGs), kResWaves * 64, (size_t)lds_bytes, stream>>>(
-            LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
-            norm, ldn);
+        HIP_TRY(allow_full_lds<layer_dense_resident_kernel>());
+        call.launch(layer_dense_resident_kernel, kResWGs, kResWaves * 64, (size_t)lds_bytes, Wt, bias2, n_chunks);
         LAUNCH_CHECK();
         return NGCF_OK;
     }
@@ -1369,32 +1362,26 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     const int direct_env = ngcf_opts().dense_direct;
     if (direct_env && dop >= 256 && padded && (n_rows <= 8192 || direct_env == 2)) {
         const int64_t blocks = (n_rows + 31) / 32;
-        if (dop == 256)
-            layer_dense_direct_kernel<2, 4><<<dim3((unsigned)blocks), 128, 0, stream>>>(
-                LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
-                norm, ldn);
-        else
-            layer_dense_direct_kernel<4, 4><<<dim3((unsigned)blocks), 256, 0, stream>>>(
-                LE, ldLE, Es, ldEs, n_rows, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc,
-                norm, ldn);
+        if (dop == 256) call.launch(layer_dense_direct_kernel<2, 4>, blocks, 128, 0, Wt, bias2, n_chunks);
+        else call.launch(layer_dense_direct_kernel<4, 4>, blocks, 256, 0, Wt, bias2, n_chunks);
         LAUNCH_CHECK();
         return NGCF_OK;
     }
 
     // the staged kernel (layer_dense_kernel)
-#define NGCF_DENSE(RW, CW, NT) \
-    return launch_dense<RW, CW, NT>(al, n_rows, LE, ldLE, Es, ldEs, d_in, d_out, Wt, bias2, n_chunks, leaky, drop_p, \
-                                    drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream)
+#define NGCF_DENSE(RW, CW, NT) launch_staged<RW, CW, NT>(call, al, padded, Wt, bias2, n_chunks)
     if (small_rows) NGCF_DENSE(1, 4, 1);
-    switch (dop) {
-    case 32: NGCF_DENSE(4, 1, 1);
-    case 64: NGCF_DENSE(4, 1, 2);
-    case 96: NGCF_DENSE(4, 1, 3);
-    case 128: NGCF_DENSE(4, 1, 4);
-    case 256: NGCF_DENSE(2, 2, 4);
+    else switch (dop) {
+    case 32: NGCF_DENSE(4, 1, 1); break;
+    case 64: NGCF_DENSE(4, 1, 2); break;
+    case 96: NGCF_DENSE(4, 1, 3); break;
+    case 128: NGCF_DENSE(4, 1, 4); break;
+    case 256: NGCF_DENSE(2, 2, 4); break;
     default: NGCF_DENSE(1, 4, 4);
     }
 #undef NGCF_DENSE
+    LAUNCH_CHECK();
+    return NGCF_OK;
 }
 
 extern "C" int64_t ngcf_layer_workspace_bytes(const ngcf_csr_t *c, int d_in, int d_out)
