@@ -67,7 +67,7 @@ struct NgcfOptions {
     int dense_resident_min_rows = 106496;  // NGCF_DENSE_RESIDENT_MIN_ROWS: rows from which the weights-resident kernel runs (65 536 = one round of its 2 048 waves; measured cross-over, profiles/r04_dense_rows_lab.txt)
     int dense_small_tiles = 1;     // NGCF_DENSE_SMALL_TILES: 32-row tiles for <= 128 output columns on <= 16 384 rows
     int dense_tall = 1;            // NGCF_DENSE_TALL: 256 / 512 output columns as 96-row x 128-column workgroups: 0 never, 1 where measured faster, 2 always
-    // backward.hip
+    // spmm_t_rows.hip, bwd_dense.hip
     int t_rows_bitmap = 1;         // NGCF_T_ROWS_BITMAP: 0 keeps the row-sparse transposed product on the slot-table kernel at every size
     int bwd_input_resident = 1;    // NGCF_BWD_INPUT_RESIDENT: 0 keeps the staged input-gradient kernel at every size
     // csr.hip
@@ -97,6 +97,17 @@ inline int current_device_slot()
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
     return dev % kMaxDevices;
+}
+
+// A kernel that keeps up to 160 KiB (all of a CU's LDS) in dynamic LDS: the attribute is per kernel and device, set once.
+template <auto kernel> static hipError_t allow_full_lds(int bytes = 160 * 1024)
+{
+    static bool set[kMaxDevices] = {};
+    const int dev_i = current_device_slot();
+    if (set[dev_i]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    set[dev_i] = e == hipSuccess;
+    return e;
 }
 
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }

@@ -1242,17 +1242,6 @@ struct DenseCall {
     }
 };
 
-// The persistent kernels keep up to 160 KiB of weights in dynamic LDS: the attribute is per kernel and device, set once.
-template <auto kernel> static hipError_t allow_full_lds()
-{
-    static bool set[kMaxDevices] = {};
-    const int dev_i = current_device_slot();
-    if (set[dev_i]) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    set[dev_i] = e == hipSuccess;
-    return e;
-}
-
 template <int RW, int CW, int NT>   // the staged kernel; padded: 16-byte aligned rows padded to a multiple of 4 floats (any d_in)
 static void launch_staged(const DenseCall &k, bool al, bool padded, const float *Wt, const float *bias2, int n_chunks)
 {

@@ -509,13 +509,7 @@ int launch_spmm(const SpmmArgs &a)
             rpw = std::min<int64_t>(std::max<int64_t>((rpw + kLdsTabWaves - 1) / kLdsTabWaves * kLdsTabWaves, kLdsTabWaves), 64 * kLdsTabWaves);
             const int64_t rb = (n_rows_g + rpw - 1) / rpw;
             const size_t lds = ((size_t)n_tab + 1) * 256;
-            static bool attr_set[kMaxDevices] = {};      // the attribute is per device
-            const int dev_i = current_device_slot();
-            if (!attr_set[dev_i]) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(spmm_ldstab_kernel<4>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (kLdsTableRows + 1) * 256));
-                attr_set[dev_i] = true;
-            }
+            HIP_TRY(allow_full_lds<spmm_ldstab_kernel<4>>((kLdsTableRows + 1) * 256));
             spmm_ldstab_kernel<4><<<dim3((unsigned)rb, (unsigned)n_slices), kLdsTabWaves * 64, lds, gs>>>(
                 c->rowptr, c->colidx, c->vals, grp.begin, grp.end, (int)rpw, c->seg_len, a.E, a.ldE, a.d, grp.col_lo, n_tab, a.out,
                 a.ldo, a.dr);

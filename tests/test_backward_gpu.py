@@ -195,7 +195,7 @@ def test_bpr_backward_of_a_broadcast_operand_is_a_sum_in_row_order(which, dev):
                                                         # first layers) run on the narrow kernel: 2, 3 and 1 remainder columns, ragged row count
                                                         (70001, 130, 128, False), (66000, 515, 96, True), (65537, 129, 128, False)])
 def test_weight_gradient_kernel_matches_fp64(n_rows, d_in, d_out, strided, dev):
-    """gW = dM^T . [LE+E | LE*E] and gb = column sums of dM (MFMA kernel, csrc/backward.hip) against fp64 from the definition (NGCF.py:131-136),
+    """gW = dM^T . [LE+E | LE*E] and gb = column sums of dM (MFMA kernel, csrc/bwd_dense.hip) against fp64 from the definition (NGCF.py:131-136),
     incl. widths that are not multiples of 32 or 4, a row count that is not a multiple of the block, strided operands
     and the empty case.  Summation order differs from any reference GEMM: tolerance, relative to the result's scale."""
     from seoul_tourism_recommendation_ngcf_amd import autograd, engine
