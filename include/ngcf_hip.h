@@ -43,7 +43,7 @@ const char *ngcf_last_error(void);
 const char *ngcf_target_arch(void);
 /* ABI version of this header.  ngcf_version() returns the value the library was built with; the Python mirror refuses to bind
  * a library whose version differs (a stale .so would otherwise receive shifted arguments). */
-#define NGCF_ABI_VERSION 9
+#define NGCF_ABI_VERSION 10
 int ngcf_version(void);
 
 /* Tunables of the kernel dispatch (thresholds, switches).  The library reads its NGCF_* environment variables ONCE, in
@@ -384,6 +384,32 @@ int ngcf_rank_topk_f32(const float *users, int64_t ldu, const int64_t *user_ids,
 int ngcf_rank_metrics(const int64_t *top_idx, int64_t B, int k, const int64_t *user_ids, int64_t n_user_rows,
                       const int64_t *truth_rowptr, const int32_t *truth_colidx, int64_t truth_col_offset,
                       const int32_t *ks_host, int n_ks, float *per_user, double *sums, int32_t *status, void *stream);
+
+/* Candidate-list evaluation, the reference's own test protocol (experiment.py:66-119) for T cases x C candidates in one launch
+ * (DESIGN 4.3).  Case t scores user r = user_ids[t] (users[r*ldu + 0..D)) against the items cand[t*ldc + 0..C) (rows of `items`,
+ * ldi); column 0 is the held-out item.  s_j = <u, item[cand_j]> in fp32 in a summation order that depends on D alone: the same
+ * (user row, item row) pair gives the same bits whatever T, C, the case order, the column or the tables' alignment, so duplicated
+ * candidates tie exactly.  position[t] = the number of columns that sort above column 0 in the order of ngcf_topk_rows_f32 (value
+ * descending, equal values lowest column first - column 0 wins every tie -, NaN above +inf).  Per case, added into sums
+ * (device, [n_ks + 4]) = [hits, ndcg@ks[0..n_ks), bpr, abs_err, cases]:
+ *   hits    position < hit_k                                      (experiment.py:104-106; the reference's hit_k is 3)
+ *   ndcg@K  position < K ? 1/log2(position + 2) : 0               (experiment.py:109-111,121-128)
+ *   bpr     BPR.forward (bprloss.py:15-22, the abs included) on u repeated user_repeat times (1 or C: only the weight of |u|^2 in
+ *           the regulariser), pos = item[cand_0], neg = item[cand_1.., cand_{C-1}, cand_1] (experiment.py:96-100; C rows for
+ *           C >= 2, none for C = 1), divided by batch_size
+ *   abs_err |s_0 - ratings[t]| (what the reference's sqrt(MSE) of two scalars is, experiment.py:114-116); 0 when ratings is NULL
+ *   cases   1
+ * in a fixed order (per-workgroup partials, then one workgroup; no float atomics): bit-identical from run to run, and a case set
+ * can be evaluated in chunks and across years into one `sums` (the grouping then differs: equal to fp64 rounding).
+ * scores [T, C] and position int32[T] may be NULL.  Every id of a case is checked before any of its rows is loaded: a case with a
+ * user id outside [0, n_user_rows) or a candidate outside [0, n_items) sets *status, adds nothing to sums and gets position -1
+ * (its row of scores: NaN).  ks_host: HOST int32[n_ks], 0 <= n_ks <= 8; 1 <= hit_k, ks[i] <= C <= 1024 (a k above C is an error,
+ * as torch.topk raises there); any D >= 1, any alignment (float4 loads where `items` and ldi allow them). */
+int ngcf_eval_candidates_f32(const float *users, int64_t ldu, int64_t n_user_rows, const float *items, int64_t ldi,
+                             int64_t n_items, int D, const int64_t *user_ids, const int64_t *cand, int64_t ldc, int64_t T, int C,
+                             const float *ratings, const int32_t *ks_host, int n_ks, int hit_k, float weight_decay,
+                             float batch_size, int user_repeat, float *scores, int32_t *position, double *sums, int32_t *status,
+                             void *stream);
 
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*

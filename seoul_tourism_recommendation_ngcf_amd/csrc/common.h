@@ -373,5 +373,16 @@ __device__ inline float wave_sum(float x)
     return x;
 }
 
+__device__ inline float log_sigmoid(float x)       // F.logsigmoid (bprloss.py:19)
+{
+    return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
+}
+
+__device__ inline uint32_t float_key(float x)      // monotone map float -> uint32 (larger float = larger key, NaN above +inf)
+{
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 
 #endif  // NGCF_COMMON_H

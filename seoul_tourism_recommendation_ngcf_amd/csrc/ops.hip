@@ -278,11 +278,6 @@ extern "C" int ngcf_gather_rows3_f32(const float *table, int64_t ld, int d, cons
 // ---------------------------------------------------------------------------------------------
 // BPR, bprloss.py:15-22
 // ---------------------------------------------------------------------------------------------
-__device__ inline float log_sigmoid(float x)
-{
-    return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
-}
-
 // one wave per row r < R; block partials: part[2*block + 0] = -sum logsigmoid, part[2*block + 1] = sum of squares
 __global__ __launch_bounds__(256) void bpr_rows_kernel(const float *__restrict__ u, int64_t Bu, const float *__restrict__ p,
                                                        int64_t Bp, const float *__restrict__ n, int64_t Bn, int64_t R,
@@ -412,12 +407,6 @@ extern "C" int ngcf_shard_plan(const int64_t *rowptr, int64_t row_begin, int64_t
 // descending (equal values: lowest column first).  The score matrix itself is a plain GEMM (u . items^T).
 // =============================================================================================
 #define NGCF_TOPK_MAX 1024
-
-__device__ inline uint32_t float_key(float x)      // monotone map float -> uint32 (larger float = larger key)
-{
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct TopkShared {
     uint32_t hist[256];

@@ -662,3 +662,103 @@ def metrics_from_sums(sums: torch.Tensor, ks: Sequence[int]) -> dict:
             out[f"{name}@{K}"] = s[4 * q + j] / n if n else 0.0
     out["users"] = n
     return out
+
+
+# ---- candidate-list evaluation, the reference's test protocol (ngcf_eval_candidates_f32, csrc/eval_candidates.hip) ----------------
+CAND_MAX = 1024
+
+
+def _cand_cutoffs(ks: Sequence[int], hit_k: int, C: int):
+    ks, hit_k = [int(x) for x in ks], int(hit_k)
+    if len(ks) > 8:
+        raise ValueError(f"eval_candidates: at most 8 NDCG cut-offs, got {len(ks)}")
+    for k in ks + [hit_k]:
+        if k < 1 or k > C:
+            raise RuntimeError(f"selected index k out of range (k={k}, row length {C})")
+    return ks, hit_k
+
+
+def eval_candidates(user_emb: torch.Tensor, item_emb: torch.Tensor, user_ids: torch.Tensor, candidates: torch.Tensor,
+                    ratings: Optional[torch.Tensor] = None, ks: Sequence[int] = (10,), hit_k: int = 3, weight_decay: float = 0.0,
+                    batch_size: float = 1.0, user_repeat: Optional[int] = None, sums: Optional[torch.Tensor] = None,
+                    status: Optional[torch.Tensor] = None, return_scores: bool = False, return_position: bool = True):
+    """The reference's test protocol (experiment.py:92-116) for T cases x C candidates in one launch (ngcf_eval_candidates_f32):
+    case t scores user_emb[user_ids[t]] against item_emb[candidates[t, :]], column 0 the held-out item.  `user_ids` int64 [T],
+    `candidates` int64 [T, C] (C <= 1024), `ratings` float32 [T] or None, all on the embeddings' device; strided views (rows of
+    all_E) are taken as they are.  Adds [hits@hit_k, ndcg@ks.., bpr sum, |s_0 - rating| sum, cases] into `sums` (float64,
+    len(ks) + 4 slots; a fresh one if None) in a fixed order - see `candidate_metrics_from_sums`.  `user_repeat` (1 or C, default C)
+    is how often the user row counts in the BPR regulariser.  Returns (sums, position int32 [T] or None, scores [T, C] or None);
+    position = the number of candidates that sort above column 0 (ties: column 0 wins), -1 for a case with an id out of range.
+    Such a case adds nothing; it raises IndexError (one host sync), or with a caller's int32 `status` word is only flagged there."""
+    lib = _lib.load()
+    # shapes, types and limits first (they hold on any device), then where the tensors live
+    if user_emb.dim() != 2 or item_emb.dim() != 2 or user_emb.shape[1] != item_emb.shape[1]:
+        raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({tuple(user_emb.shape)} and {tuple(item_emb.t().shape)})")
+    for t, nm in ((user_ids, "user_ids"), (candidates, "candidates")):
+        if t.dtype != torch.int64:
+            raise TypeError(f"eval_candidates: {nm} must be int64, got {t.dtype}")
+    if user_ids.dim() != 1 or candidates.dim() != 2 or candidates.shape[0] != user_ids.shape[0]:
+        raise ValueError(f"eval_candidates: user_ids [T] and candidates [T, C] expected, got {tuple(user_ids.shape)} and {tuple(candidates.shape)}")
+    T, n_cand = int(candidates.shape[0]), int(candidates.shape[1])
+    if n_cand < 1 or n_cand > CAND_MAX:
+        raise ValueError(f"eval_candidates: C={n_cand} candidates per case outside [1, {CAND_MAX}]")
+    ks, hit_k = _cand_cutoffs(ks, hit_k, n_cand)
+    user_repeat = n_cand if user_repeat is None else int(user_repeat)
+    if user_repeat not in (1, n_cand):
+        raise ValueError(f"eval_candidates: user_repeat={user_repeat} is neither 1 nor C={n_cand}")
+    if float(batch_size) == 0.0:
+        raise ValueError("eval_candidates: batch_size must not be 0")
+    if ratings is not None and (ratings.dim() != 1 or int(ratings.numel()) != T):
+        raise ValueError(f"eval_candidates: {tuple(ratings.shape)} ratings for {T} cases")
+    _f32c(user_emb, "user_emb"), _f32c(item_emb, "item_emb")
+    dev = user_emb.device
+    if ratings is not None:
+        ratings = _f32c(ratings, "ratings").contiguous()
+    for t, nm in ((user_ids, "user_ids"), (candidates, "candidates"), (ratings, "ratings")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"eval_candidates: {nm} is on {t.device}, the embeddings on {dev}")
+    user_emb = user_emb if user_emb.stride(1) == 1 else user_emb.contiguous()
+    item_emb = item_emb if item_emb.stride(1) == 1 else item_emb.contiguous()
+    user_ids = user_ids.contiguous()
+    candidates = candidates if candidates.stride(1) == 1 else candidates.contiguous()
+    n_slots = len(ks) + 4
+    if sums is None:
+        sums = torch.zeros(n_slots, dtype=torch.float64, device=dev)
+    elif sums.dtype != torch.float64 or sums.numel() != n_slots or sums.device != dev or not sums.is_contiguous():
+        raise ValueError(f"eval_candidates: sums must be a contiguous float64 tensor of {n_slots} slots on {dev}")
+    check_status = status is None
+    if check_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.device != dev:
+        raise ValueError(f"eval_candidates: status must be an int32 tensor on {dev}")
+    scores = torch.empty((T, n_cand), dtype=torch.float32, device=dev) if return_scores else None
+    position = torch.empty((T,), dtype=torch.int32, device=dev) if return_position else None
+    ks_arr = (C.c_int32 * max(len(ks), 1))(*ks)
+    with _on(dev):
+        _lib.check(lib.ngcf_eval_candidates_f32(
+            _ptr(user_emb), _row_major_ld(user_emb, "user_emb"), int(user_emb.shape[0]), _ptr(item_emb),
+            _row_major_ld(item_emb, "item_emb"), int(item_emb.shape[0]), int(user_emb.shape[1]), _ptr(user_ids), _ptr(candidates),
+            _row_major_ld(candidates, "candidates"), T, n_cand, _ptr(ratings), ks_arr, len(ks), hit_k, float(weight_decay),
+            float(batch_size), user_repeat, _ptr(scores), _ptr(position), _ptr(sums), _ptr(status), _stream()))
+    if check_status and int(status.item()) != 0:
+        raise IndexError(f"eval_candidates: a user id lies outside [0, {int(user_emb.shape[0])}) or a candidate outside "
+                         f"[0, {int(item_emb.shape[0])})")
+    return sums, position, scores
+
+
+def candidate_metrics_from_sums(sums, ks: Sequence[int], hit_k: int = 3) -> dict:
+    """The means of an `eval_candidates` slot vector [hits, ndcg@ks.., bpr, abs_err, cases] (one read-back): {"bpr", "hr@<hit_k>",
+    "ndcg@K".., "rmse", "cases"}, every entry its sum over `cases` - the reference's mean over len(test_dataloader),
+    experiment.py:119 ("rmse" is the mean of the per-case sqrt(MSE) of two scalars, i.e. of |s_0 - rating|)."""
+    ks = [int(x) for x in ks]
+    s = torch.as_tensor(sums).double().cpu().tolist()
+    if len(s) != len(ks) + 4:
+        raise ValueError(f"candidate_metrics_from_sums: {len(s)} slots for {len(ks)} cut-offs ({len(ks) + 4} expected)")
+    n = int(round(s[-1]))
+    mean = lambda x: x / n if n else 0.0   # noqa: E731
+    out = {"bpr": mean(s[len(ks) + 1]), f"hr@{int(hit_k)}": mean(s[0])}
+    for q, K in enumerate(ks):
+        out[f"ndcg@{K}"] = mean(s[1 + q])
+    out["rmse"] = mean(s[len(ks) + 2])
+    out["cases"] = n
+    return out

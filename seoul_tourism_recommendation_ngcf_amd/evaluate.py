@@ -4,6 +4,10 @@ top lists against held-out items (Recall / NDCG / precision / hit rate @K).
 The reference ranks with `torch.topk(torch.mm(u, all_items_emb.T), k)` (demo.py:233-235) and computes its metrics as host-side
 bookkeeping (experiment.py:66-133); here both run on the device (engine.rank_topk, engine.ranking_metrics) and the host reads one
 vector back at the end.
+
+The reference's own test protocol - one user against a short candidate list whose first entry is the held-out item, Test-BPR / HR@3 /
+NDCG@ks / RMSE (Experiment.eval, experiment.py:66-119) - is `candidate_ranking`: one propagation per year and one launch per chunk
+of cases (engine.eval_candidates) in place of a forward, a mm, two topk and five read-backs per case.
 """
 from __future__ import annotations
 
@@ -55,5 +59,97 @@ def full_ranking(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), ye
             if int(status.item()) != 0:
                 raise IndexError(f"full_ranking: a user id lies outside [0, {n_user})")
             return engine.metrics_from_sums(sums, ks)
+    finally:
+        model.train(was_training)
+
+
+def candidate_ranking(model, user_ids: torch.Tensor, candidates: torch.Tensor, *, year=None, features=None,
+                      ratings: Optional[torch.Tensor] = None, criterion=None, ks: Sequence[int] = (10,), hit_k: int = 3,
+                      user_repeat: Optional[int] = None, case_chunk: int = 65536, return_scores: bool = False):
+    """`Experiment.eval` (experiment.py:66-119) for T test cases at once.  Case t is user `user_ids[t]` against the items
+    `candidates[t, :]` ([T, C], C <= 1024), column 0 the held-out item - one batch of the reference's test_dataloader, whose u_id
+    repeats the user C times and whose pos_item is the candidate list.  Returns {"bpr", "hr@<hit_k>", "ndcg@K" for K in ks, "rmse",
+    "cases"}: the four values `Experiment.eval` returns (means over the cases) and the case count; with `return_scores` the tuple
+    (that dict, scores [T, C] = the reference's `pred_ratings[0]` per case, position int32 [T] = the rank of the held-out item).
+
+      year       None (Laplacian slice 0), one year, or one year per case (tensor, list or array; expected on the host - a device
+                 tensor costs one more read-back, before the launches); a case uses slice `model._year_index` of its year
+                 (year % 18, NGCF.py:117; while a GraphedTrainStep holds the model, the slice that step was captured for, for
+                 every case).  The model propagates once per distinct slice, not once per case.
+      features   (age, sex, month, day, dow), one entry per case, or None: no injection.
+      ratings    [T] the held-out rating of every case ("rmse" is 0 without).
+      criterion  the test BPR module; its weight_decay and batch_size enter the loss.  None: no "bpr" entry.
+      user_repeat  rows of the user in the loss's regulariser: C (default - the reference's batch) or 1.
+      case_chunk   cases per launch.
+
+    The model runs in eval mode under no_grad; the caller's mode is restored.  The host reads back once, at the end; an id out of
+    range (user, candidate or feature) raises IndexError then.
+
+    One deviation from the reference's sequential loop.  The reference injects the features of case i right before case i's
+    forward (NGCF.py:103-115), so case i sees the injections of cases <= i only, and with emb_ratio != 1 a user that occurs in n
+    cases is blended n times.  Here every case is injected ONCE, up front, in one `engine.feature_inject` call (a user that occurs
+    in several cases: the last one wins, one blend), and every case is scored against that table.  The two agree exactly whenever
+    the injected rows are already in the table - with emb_ratio = 1 and features that are a function of the user id (the
+    reference's data) from the second epoch on; equivalently this function equals the SECOND pass of the reference's loop over the
+    same cases."""
+    ks = [int(x) for x in ks]
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            dev = model._dev()
+            user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+            candidates = candidates.to(device=dev, dtype=torch.int64)
+            T = int(user_ids.numel())
+            if candidates.dim() != 2 or int(candidates.shape[0]) != T:
+                raise ValueError(f"candidate_ranking: candidates must be [T = {T}, C], got {tuple(candidates.shape)}")
+            C = int(candidates.shape[1])
+            if ratings is not None:
+                ratings = ratings.reshape(-1).to(device=dev, dtype=torch.float32)
+            wd, bs = (float(criterion.weight_decay), float(criterion.batch_size)) if criterion is not None else (0.0, 1.0)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            if features is not None:                                   # NGCF.py:103-115, all cases at once
+                if len(features) != 5:
+                    raise ValueError("candidate_ranking: features = (age, sex, month, day, dow)")
+                keep = engine.feature_inject(
+                    model.user_embedding.weight.data,
+                    (model.age_emb.weight.data, model.sex_emb.weight.data, model.month_emb.weight.data,
+                     model.day_emb.weight.data, model.dow_emb.weight.data),
+                    features, user_ids, model.emb_ratio, model._scratch_buf(dev), status)
+                model._e0_cache.touch(user_ids)
+                del keep
+            # cases by Laplacian slice
+            year_h = None if year is None else torch.as_tensor(year).reshape(-1).cpu()
+            if year_h is None or int(year_h.numel()) == 1:
+                groups = [(0 if year_h is None else model._year_index(year_h), None)]
+            else:
+                if int(year_h.numel()) != T:
+                    raise ValueError(f"candidate_ranking: {int(year_h.numel())} years for {T} cases")
+                idx_of = {int(v): model._year_index(torch.tensor([int(v)])) for v in torch.unique(year_h).tolist()}
+                case_idx = torch.tensor([idx_of[int(v)] for v in year_h.tolist()], dtype=torch.int64)
+                groups = [(y, (case_idx == y).nonzero().flatten().to(dev)) for y in sorted(set(idx_of.values()))]
+            sums = torch.zeros(len(ks) + 4, dtype=torch.float64, device=dev)
+            scores = torch.empty((T, C), dtype=torch.float32, device=dev) if return_scores else None
+            position = torch.empty((T,), dtype=torch.int32, device=dev) if return_scores else None
+            for y, sel in groups:
+                model.propagate(y)
+                U, I = model.all_users_emb, model.all_items_emb
+                uid, cand, rat = ((user_ids, candidates, ratings) if sel is None else
+                                  (user_ids[sel], candidates[sel], None if ratings is None else ratings[sel]))
+                for c0 in range(0, int(uid.numel()), int(case_chunk)):
+                    sl = slice(c0, c0 + int(case_chunk))
+                    _, pos, sc = engine.eval_candidates(U, I, uid[sl], cand[sl], None if rat is None else rat[sl], ks, hit_k, wd, bs,
+                                                        user_repeat, sums=sums, status=status, return_scores=return_scores,
+                                                        return_position=return_scores)
+                    if return_scores:
+                        dst = sl if sel is None else sel[sl]
+                        scores[dst], position[dst] = sc, pos
+            host = torch.cat((sums, status.double())).cpu()            # the one read-back
+            if int(host[-1]) != 0:
+                raise IndexError("candidate_ranking: a user id, a candidate or a feature id is out of range")
+            out = engine.candidate_metrics_from_sums(host[:-1], ks, hit_k)
+            if criterion is None:
+                del out["bpr"]
+            return (out, scores, position) if return_scores else out
     finally:
         model.train(was_training)
