@@ -43,7 +43,7 @@ const char *ngcf_last_error(void);
 const char *ngcf_target_arch(void);
 /* ABI version of this header.  ngcf_version() returns the value the library was built with; the Python mirror refuses to bind
  * a library whose version differs (a stale .so would otherwise receive shifted arguments). */
-#define NGCF_ABI_VERSION 10
+#define NGCF_ABI_VERSION 11
 int ngcf_version(void);
 
 /* Tunables of the kernel dispatch (thresholds, switches).  The library reads its NGCF_* environment variables ONCE, in
@@ -410,6 +410,34 @@ int ngcf_eval_candidates_f32(const float *users, int64_t ldu, int64_t n_user_row
                              const float *ratings, const int32_t *ks_host, int n_ks, int hit_k, float weight_decay,
                              float batch_size, int user_repeat, float *scores, int32_t *position, double *sums, int32_t *status,
                              void *stream);
+
+/* Rank-point blending, the reference's recommender after its topk (demo.py:285-292, 315-334, 378-398) for R request
+ * rows in G columns in one launch.  Request row r has up to three lists of Pl <= P items each, best first: its preference list
+ * pref[r*ld_pref + 0..Pl) (a top list of ngcf_rank_topk_f32), the congestion list con[con_slot[r]*ld_con + ..) of its day and the
+ * distance list dis[dis_slot[r]*ld_dis + ..) of its departure point (top lists of ngcf_topk_rows_f32 over the negated values; con
+ * or con_slot NULL: no congestion points, the same for distance).  The item at position j of a list gets P - j points of that
+ * kind, every other item 0; an entry of -1 is an empty slot; the items of a list are distinct.  Column g is the set of rows
+ * col_rows[col_rowptr[g] .. col_rowptr[g+1]) (a row may be in several columns, at most once in each); with sp, sc, sd the exact
+ * int32 sums of the three kinds over the column's rows,
+ *   rating[g, i] = ((double)sp * w_pref + (double)sc * w_con) + (double)sd * w_dis
+ * in fp64, left to right, every operation rounded on its own (no FMA): numpy's result bit for bit, independent of the order of rows,
+ * columns and workgroups.  out_items / out_rating [G, top]: the `top` items with item_mask[i] != 0 (uint8 [n_items]; NULL: all),
+ * rating descending, equal ratings (-0.0 = +0.0) lowest item first; slots past the eligible items are (-1, -inf); a column without
+ * rows rates every item 0.0.  table (may be NULL; tests and small catalogues): [G, n_items] the ratings of all items, masked or not.
+ * One workgroup per (column, tile of tile_items items; 0 = the default, at most 4096), the tile's sums in LDS; with more than one
+ * tile the tiles' lists pass through the workspace (ngcf_blend_workspace_bytes; 0 for one tile, -1 for arguments out of range) and a
+ * second kernel merges them per column: the result does not depend on tile_items.  No float atomics.  Every id is checked before
+ * use: a row index outside [0, R), a slot outside [0, S_con) / [0, S_dis), a list entry outside [0, n_items) other than -1 or a
+ * column range outside col_rows (n_col_rows entries) sets *status and contributes nothing (ngcf_gather_rows_f32's rule).
+ * Argument errors, before any launch: top outside [1, 256], P outside [1, 1024], Pl outside [1, P], R * P >= 2^31 (the bound that
+ * keeps the int32 sums exact), n_items outside [1, 2^31). */
+int64_t ngcf_blend_workspace_bytes(int64_t G, int64_t n_items, int top, int tile_items);
+int ngcf_blend_points(const int64_t *pref, int64_t ld_pref, int64_t R, int Pl, const int64_t *con, int64_t ld_con, int64_t S_con,
+                      const int64_t *con_slot, const int64_t *dis, int64_t ld_dis, int64_t S_dis, const int64_t *dis_slot,
+                      const int64_t *col_rowptr, const int64_t *col_rows, int64_t n_col_rows, int64_t G, int P, int64_t n_items,
+                      double w_pref, double w_con, double w_dis, const uint8_t *item_mask, int top, int tile_items,
+                      int64_t *out_items, double *out_rating, double *table, int32_t *status, void *workspace,
+                      int64_t workspace_bytes, void *stream);
 
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*

@@ -9,5 +9,6 @@ from .bprloss import BPR
 from .graphed import GraphedForward, GraphedTrainStep
 from . import engine, graphs
 from . import evaluate
+from . import recommend
 
-__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate"]
+__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend"]

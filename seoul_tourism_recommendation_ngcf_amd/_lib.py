@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must be loaded before libngcf_hip.so, see module do
 from . import _build
 
 OK, ERR_ARG, ERR_HIP, ERR_INDEX, ERR_WORKSPACE = 0, 1, 2, 3, 4
-ABI_VERSION = 10         # NGCF_ABI_VERSION of include/ngcf_hip.h these prototypes were written against
+ABI_VERSION = 11         # NGCF_ABI_VERSION of include/ngcf_hip.h these prototypes were written against
 
 _vp, _i64, _i32, _f32, _u64 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint64
 
@@ -87,6 +87,9 @@ PROTOTYPES = {
     "ngcf_rank_metrics": (C.c_int, [_vp, _i64, C.c_int, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i32), C.c_int, _vp, _vp, _vp, _vp]),
     "ngcf_eval_candidates_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _i64, _i64, C.c_int, _vp, C.POINTER(_i32),
                                            C.c_int, C.c_int, _f32, _f32, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "ngcf_blend_workspace_bytes": (_i64, [_i64, _i64, C.c_int, C.c_int]),
+    "ngcf_blend_points": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, C.c_int, _i64,
+                                    C.c_double, C.c_double, C.c_double, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ngcf_shard_plan": (C.c_int, [C.POINTER(_i64), _i64, _i64, C.c_int, C.POINTER(_i64)]),
     "ngcf_allgather_rows": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "ngcf_comm_size": (C.c_int, [_vp, C.POINTER(C.c_int)]),

@@ -762,3 +762,97 @@ def candidate_metrics_from_sums(sums, ks: Sequence[int], hit_k: int = 3) -> dict
     out["rmse"] = mean(s[len(ks) + 2])
     out["cases"] = n
     return out
+
+
+# ---- rank-point blending, the reference's recommender after its topk (ngcf_blend_points, csrc/blend.hip) ---------------------------
+BLEND_TOP_MAX = 256
+BLEND_POINTS_MAX = 1024
+
+
+def blend_points(pref: torch.Tensor, col_rowptr: torch.Tensor, col_rows: torch.Tensor, n_items: int, *, points: int = 100,
+                 weights: Sequence[float] = (1.0, 0.0, 0.0), con: Optional[torch.Tensor] = None,
+                 con_slot: Optional[torch.Tensor] = None, dis: Optional[torch.Tensor] = None,
+                 dis_slot: Optional[torch.Tensor] = None, item_mask: Optional[torch.Tensor] = None, top: int = 10,
+                 tile_items: int = 0, return_table: bool = False, status: Optional[torch.Tensor] = None):
+    """The rank-point blending of demo.py:285-292, 315-334, 378-398 for R request rows in G columns in one launch
+    (ngcf_blend_points).  `pref` int64 [R, Pl]: the preference list of every request row, best first (`rank_topk`'s indices; -1 =
+    empty slot); `con` int64 [S_con, Pl] with `con_slot` int64 [R] (the list of row r is con[con_slot[r]]) and `dis` / `dis_slot`
+    likewise, or None for no points of that kind (`topk_rows(-values, Pl)`'s indices).  Position j of a list is worth `points` - j.
+    Column g is the set of rows col_rows[col_rowptr[g]:col_rowptr[g + 1]] (int64 CSR).  Per column and item the three kinds of
+    points are summed over the rows (int32, exact) and rating = (sp * w_pref + sc * w_con) + sd * w_dis in fp64 without FMA - the
+    bits numpy gives.  Returns (items int64 [G, top], rating float64 [G, top]): per column the best `top` items with
+    `item_mask[i] != 0` (uint8 / bool [n_items], None: all), rating descending, ties lowest item first, (-1, -inf) past the
+    eligible items; with `return_table` also the dense float64 [G, n_items] ratings (tests and small catalogues only).  The result
+    does not depend on `tile_items` (items per workgroup, 0 = default).  An id out of range (row index, slot, list entry, column
+    range) adds nothing and raises IndexError (one host sync); with a caller's int32 `status` word it is only flagged there."""
+    lib = _lib.load()
+    # shapes, types and limits first (they hold on any device), then where the tensors live
+    top, points, n_items, tile_items = int(top), int(points), int(n_items), int(tile_items)
+    if top < 1 or top > BLEND_TOP_MAX:
+        raise ValueError(f"blend_points: top={top} outside [1, {BLEND_TOP_MAX}]")
+    if points < 1 or points > BLEND_POINTS_MAX:
+        raise ValueError(f"blend_points: points={points} outside [1, {BLEND_POINTS_MAX}]")
+    if n_items < 1 or n_items >= 2 ** 31:
+        raise ValueError(f"blend_points: n_items={n_items} outside [1, 2^31)")
+    if len(weights) != 3:
+        raise ValueError("blend_points: weights = (w_pref, w_con, w_dis)")
+    if (con is None) != (con_slot is None) or (dis is None) != (dis_slot is None):
+        raise ValueError("blend_points: a context list table and its slot vector come together")
+    ints = (("pref", pref), ("col_rowptr", col_rowptr), ("col_rows", col_rows), ("con", con), ("con_slot", con_slot), ("dis", dis),
+            ("dis_slot", dis_slot))
+    for nm, t in ints:
+        if t is not None and t.dtype != torch.int64:
+            raise TypeError(f"blend_points: {nm} must be int64, got {t.dtype}")
+    if item_mask is not None and item_mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"blend_points: item_mask must be uint8 or bool, got {item_mask.dtype}")
+    if pref.dim() != 2 or pref.shape[1] < 1 or pref.shape[1] > points:
+        raise ValueError(f"blend_points: pref must be [R, Pl] with 1 <= Pl <= points = {points}, got {tuple(pref.shape)}")
+    R, Pl = int(pref.shape[0]), int(pref.shape[1])
+    if R * points >= 2 ** 31:
+        raise ValueError(f"blend_points: R * points = {R} * {points} >= 2^31: the int32 point sums could overflow")
+    for nm, lists, slot in (("con", con, con_slot), ("dis", dis, dis_slot)):
+        if lists is not None and (lists.dim() != 2 or int(lists.shape[1]) != Pl):
+            raise ValueError(f"blend_points: {nm} must be [S, Pl = {Pl}], got {tuple(lists.shape)}")
+        if slot is not None and (slot.dim() != 1 or int(slot.numel()) != R):
+            raise ValueError(f"blend_points: {nm}_slot must be [R = {R}], got {tuple(slot.shape)}")
+    if col_rowptr.dim() != 1 or col_rowptr.numel() < 1 or col_rows.dim() != 1:
+        raise ValueError(f"blend_points: col_rowptr [G + 1] and col_rows [nnz] expected, got {tuple(col_rowptr.shape)} and {tuple(col_rows.shape)}")
+    if item_mask is not None and (item_mask.dim() != 1 or int(item_mask.numel()) != n_items):
+        raise ValueError(f"blend_points: item_mask must be [n_items = {n_items}], got {tuple(item_mask.shape)}")
+    G = int(col_rowptr.numel()) - 1
+    nb = int(lib.ngcf_blend_workspace_bytes(G, n_items, top, tile_items))
+    if nb < 0:
+        raise ValueError(f"blend_points: tile_items={tile_items} outside [0, 4096] or too many tiles for {G} columns")
+    _require_device(pref, "pref")
+    dev = pref.device
+    for nm, t in ints + (("item_mask", item_mask),):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"blend_points: {nm} is on {t.device}, pref on {dev}")
+    check_status = status is None
+    if check_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.device != dev:
+        raise ValueError(f"blend_points: status must be an int32 tensor on {dev}")
+    pref = pref if pref.stride(1) == 1 else pref.contiguous()
+    con = None if con is None else (con if con.stride(1) == 1 else con.contiguous())
+    dis = None if dis is None else (dis if dis.stride(1) == 1 else dis.contiguous())
+    con_slot = None if con_slot is None else con_slot.contiguous()
+    dis_slot = None if dis_slot is None else dis_slot.contiguous()
+    col_rowptr, col_rows = col_rowptr.contiguous(), col_rows.contiguous()
+    if item_mask is not None:
+        item_mask = item_mask.contiguous().view(torch.uint8)
+    items = torch.empty((G, top), dtype=torch.int64, device=dev)
+    rating = torch.empty((G, top), dtype=torch.float64, device=dev)
+    table = torch.empty((G, n_items), dtype=torch.float64, device=dev) if return_table else None
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    ld = lambda t, nm: 0 if t is None else _row_major_ld(t, nm)   # noqa: E731
+    with _on(dev):
+        _lib.check(lib.ngcf_blend_points(
+            _ptr(pref), ld(pref, "pref"), R, Pl, _ptr(con), ld(con, "con"), 0 if con is None else int(con.shape[0]), _ptr(con_slot),
+            _ptr(dis), ld(dis, "dis"), 0 if dis is None else int(dis.shape[0]), _ptr(dis_slot), _ptr(col_rowptr), _ptr(col_rows),
+            int(col_rows.numel()), G, points, n_items, float(weights[0]), float(weights[1]), float(weights[2]), _ptr(item_mask), top,
+            tile_items, _ptr(items), _ptr(rating), _ptr(table), _ptr(status), _ptr(ws), nb, _stream()))
+    if check_status and int(status.item()) != 0:
+        raise IndexError(f"blend_points: a row index lies outside [0, {R}), a slot outside its table, a list entry outside "
+                         f"[0, {n_items}) or a column range outside col_rows")
+    return (items, rating, table) if return_table else (items, rating)
