@@ -439,6 +439,26 @@ int ngcf_blend_points(const int64_t *pref, int64_t ld_pref, int64_t R, int Pl, c
                       int64_t *out_items, double *out_rating, double *table, int32_t *status, void *workspace,
                       int64_t workspace_bytes, void *stream);
 
+/* Unseen items per case, the reference's TourDataset._negative_sampling (utils.py:213-275) for T cases in one launch.
+ * Case `row` belongs to user user_ids[row], whose seen items are seen_colidx[seen_rowptr[u] .. seen_rowptr[u+1]) - col_offset,
+ * ascending and distinct, in [0, n_items) (the arrays of ngcf_rank_topk_f32's exclusion sets).  The case draws m of the user's
+ * n = n_items - (length of that row) unseen items, uniformly and without replacement, as a pure function of (seed, t = case_offset +
+ * row, the seen row), all arithmetic unsigned 64-bit:
+ *   fmix(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+ *   a = fmix(seed ^ (t * 0x9E3779B97F4A7C15))
+ *   for j in 0 .. m-1:  x = j + mulhi64(fmix(a + (j + 1) * 0xD1B54A32D192ED03), n - j)
+ *                       r_j = map(x); map(x) = map(j)           (map: the identity at j = 0 - a partial Fisher-Yates shuffle)
+ * and slot j gets the r_j-th unseen item in ascending order, r_j + #{k : c_k - k <= r_j} for the seen row c_0 < c_1 < ...  A case
+ * set drawn in chunks with case_offset = the chunk's first case equals the set drawn at once.  out[row*ld_out + ..]: first[row]
+ * (when `first` is given: the held-out item of a candidate list), then the m items; ld_out >= m + (first != NULL).  *status is
+ * OR-ed into, never cleared: 1 = a user id outside [0, n_rows), 2 = a user with fewer than m unseen items (np.random.choice raises
+ * there); the drawn slots of such a case are -1, its first[row] is still written.  Argument errors, before any launch: m outside
+ * [1, 1023] (m + 1 <= 1024, the limit of ngcf_eval_candidates_f32), n_items outside [1, 2^31), ld_out too small, a null pointer
+ * (`first` may be NULL); T == 0 is not an error. */
+int ngcf_sample_unseen(const int64_t *seen_rowptr, const int32_t *seen_colidx, int64_t col_offset, int64_t n_rows, int64_t n_items,
+                       const int64_t *user_ids, int64_t T, int64_t case_offset, int m, uint64_t seed, const int64_t *first,
+                       int64_t *out, int64_t ld_out, int32_t *status, void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

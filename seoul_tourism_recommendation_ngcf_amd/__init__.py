@@ -10,5 +10,6 @@ from .graphed import GraphedForward, GraphedTrainStep
 from . import engine, graphs
 from . import evaluate
 from . import recommend
+from . import sampling
 
-__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend"]
+__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling"]

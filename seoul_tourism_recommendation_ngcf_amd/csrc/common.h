@@ -216,16 +216,17 @@ int build_swept_plan(ngcf_csr *c, hipStream_t stream);         // spmm_swept.hip
 bool swept_usable(const ngcf_csr *c, int64_t ldE, int d);       // spmm_swept.hip: can this call use the parts?
 void prof_mark(hipStream_t stream, int which);                 // spmm.hip: hipEvent around the SpMM launches
 
-// counter-based hash: the keep masks of node and message dropout are pure functions of (seed, index)
-__device__ inline uint32_t mix32(uint64_t x)
+// counter-based hash: the keep masks of node and message dropout and the draws of sample.hip are pure functions of (seed, index)
+__host__ __device__ inline uint64_t fmix64(uint64_t x)
 {
     x ^= x >> 33;
     x *= 0xff51afd7ed558ccdULL;
     x ^= x >> 33;
     x *= 0xc4ceb9fe1a85ec53ULL;
     x ^= x >> 33;
-    return (uint32_t)x;
+    return x;
 }
+__device__ inline uint32_t mix32(uint64_t x) { return (uint32_t)fmix64(x); }
 
 // Device-side message dropout (nn.Dropout on a layer's activated output, NGCF.py:142): element (row, col) is dropped iff its
 // hash is below msg_drop_thr(p); a kept one is scaled by keep_scale = 1/(1-p).  The forward dense kernels and the backward's
@@ -365,6 +366,14 @@ __device__ inline float4 vshfl_xor(float4 a, int m)
 __device__ inline float vshfl_xor(float a, int m) { return __shfl_xor(a, m); }
 __device__ inline float4 vadd(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ inline float vadd(float a, float b) { return a + b; }
+
+// A wave's LDS region is its own and its ds operations complete in order: between a phase whose lanes write and one whose other
+// lanes read, only the compiler has to be held back.
+__device__ inline void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 __device__ inline float wave_sum(float x)
 {

@@ -55,14 +55,6 @@ template <bool VEC> __device__ inline float4 cand_quad(const float *row, int q, 
 // LDS floats of one wave: the user row (whole quads), C scores, C squared norms; a multiple of 4, so every wave's row is 16-byte aligned
 __host__ __device__ inline int cand_wave_floats(int Dp, int C) { return Dp + ((2 * C + 3) & ~3); }
 
-// A wave's LDS region is its own and its ds operations complete in order: between a phase whose lanes write and one whose other
-// lanes read, only the compiler has to be held back.
-__device__ inline void cand_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __device__ inline float group16_sum(float x)
 {
 #pragma unroll
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kerne
 
     double *acc = sh[wave];                                      // the wave's running sums; lane 0 alone touches them (no registers held)
     if (lane < NGCF_CAND_SLOTS) acc[lane] = 0.0;
-    cand_wave_sync();
+    wave_lds_sync();
 
     const int64_t n_waves = (int64_t)gridDim.x * NGCF_CAND_WAVES;
     for (int64_t t = (int64_t)blockIdx.x * NGCF_CAND_WAVES + wave; t < T; t += n_waves) {
@@ -124,7 +116,7 @@ __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kerne
             uu = fmaf(v, v, uu);
         }
         uu = wave_sum(uu);
-        cand_wave_sync();
+        wave_lds_sync();
 
         for (int c0 = 0; c0 < C; c0 += 8) {
             const int ca = c0 + grp, cb = c0 + 4 + grp;
@@ -154,7 +146,7 @@ __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kerne
             }
         }
 
-        cand_wave_sync();
+        wave_lds_sync();
         // position of column 0 and the BPR terms of bprloss.py:15-22 on (u x user_repeat, item[cand_0], item[cand_1.., cand_1])
         const float s0 = sc[0];
         const uint32_t k0 = float_key(s0);
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kerne
             if (ratings) acc[NGCF_CAND_KS + 2] += fabs((double)s0 - (double)ratings[t]);
             acc[NGCF_CAND_KS + 3] += 1.0;
         }
-        cand_wave_sync();                                        // the next case overwrites the region
+        wave_lds_sync();                                        // the next case overwrites the region
     }
     __syncthreads();
     if (threadIdx.x < NGCF_CAND_SLOTS) {
