@@ -459,6 +459,25 @@ int ngcf_sample_unseen(const int64_t *seen_rowptr, const int32_t *seen_colidx, i
                        const int64_t *user_ids, int64_t T, int64_t case_offset, int m, uint64_t seed, const int64_t *first,
                        int64_t *out, int64_t ld_out, int32_t *status, void *stream);
 
+/* Per-segment quantile floor, the numeric core of the reference's Preprocess.scale_implicit (utils.py:103-122) for every
+ * user in one call.  Segment u is the entries order[rowptr[u] .. rowptr[u+1]), positions into x and out (both double [T]); order ==
+ * NULL is the identity: x is already grouped.  With z(v) = ((v - mean) / scale) + shift (0, 1, 0: the identity) and, for the n values
+ * of the segment sorted ascending s[0 .. n-1],
+ *   lo = ((n-1)*q4) / 4;  t = (((n-1)*q4) % 4) * 0.25;  a = z(s[lo]);  b = z(s[min(lo+1, n-1)]);  d = b - a
+ *   quant[u] = t < 0.5 ? a + d*t : b - d*(1-t)            (numpy's percentile(method="linear"), pandas' quantile(q4/4))
+ *   out[p]   = z(x[p]) < quant[u] ? 0.0 : z(x[p])
+ * every operation an individually rounded fp64 one (no FMA), so the result is bit-equal to numpy's; the sign of a zero is not part
+ * of the contract.  quant[u] of an empty segment is NaN.  out may alias x: a segment is read completely before any of it is written,
+ * and segments are disjoint.  q4 in {1, 2, 3}.  Segments of up to wave_max values (0: the default, 64; [0, 64]) are ranked by one
+ * wave, longer ones by a radix select of one workgroup; the result does not depend on it.  *status is OR-ed into, never cleared:
+ * 1 = a rowptr that decreases or leaves [0, T], or an order entry outside [0, T): that segment writes nothing to out, its quant is NaN;
+ * 2 = a NaN in a segment: its quant is NaN and its values pass through as z(x), unfloored (a comparison with NaN is false).
+ * Argument errors, before any launch: q4 outside [1, 3], wave_max outside [0, 64], scale not > 0 or not finite, a negative count,
+ * a null pointer (`order` may be NULL); T == 0 or n_rows == 0 is not an error and writes nothing. */
+int ngcf_segment_quantile_floor_f64(const int64_t *rowptr, int64_t n_rows, const int64_t *order, const double *x, int64_t T,
+                                    double mean, double scale, double shift, int q4, int wave_max,
+                                    double *quant, double *out, int32_t *status, void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

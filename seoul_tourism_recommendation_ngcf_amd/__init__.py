@@ -11,5 +11,6 @@ from . import engine, graphs
 from . import evaluate
 from . import recommend
 from . import sampling
+from . import preprocess
 
-__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling"]
+__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling", "preprocess"]

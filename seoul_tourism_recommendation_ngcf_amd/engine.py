@@ -829,6 +829,98 @@ def sample_unseen(seen: ItemSets, user_ids: torch.Tensor, m: int, seed: int, *, 
     return out[:, :width]
 
 
+# ---- per-segment quantile floor, the core of the reference's Preprocess.scale_implicit (ngcf_segment_quantile_floor_f64, csrc/quantile.hip)
+QUANTILE_WAVE_MAX = 64
+
+
+def segments_from_ids(ids: torch.Tensor, n_rows: int):
+    """Group positions by id: `(rowptr int64 [n_rows + 1], order int64 [T])` with segment u = order[rowptr[u] : rowptr[u + 1]], the
+    positions t with ids[t] == u in ascending order - the `rowptr` / `order` of `segment_quantile_floor`.  One stable `torch.sort`
+    plus `bincount` and `cumsum` on the ids' device (set-up, as `ItemSets.from_pairs`); an id with no position gets an empty
+    segment.  An id outside [0, n_rows) raises IndexError."""
+    if ids.dim() != 1:
+        raise ValueError(f"segments_from_ids: ids must be [T], got {tuple(ids.shape)}")
+    if ids.dtype != torch.int64:
+        raise TypeError(f"segments_from_ids: ids must be int64, got {ids.dtype}")
+    n_rows = int(n_rows)
+    if n_rows < 0:
+        raise ValueError(f"segments_from_ids: n_rows={n_rows}")
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_rows):
+        raise IndexError(f"segments_from_ids: an id lies outside [0, {n_rows})")
+    order = torch.sort(ids, stable=True).indices
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=ids.device)
+    if n_rows:
+        rowptr[1:] = torch.cumsum(torch.bincount(ids, minlength=n_rows), 0)
+    return rowptr, order
+
+
+def segment_quantile_floor(rowptr: torch.Tensor, x: torch.Tensor, *, order: Optional[torch.Tensor] = None, mean: float = 0.0,
+                           scale: float = 1.0, shift: float = 0.0, q: float = 0.25, wave_max: int = 0,
+                           out: Optional[torch.Tensor] = None, quant: Optional[torch.Tensor] = None,
+                           status: Optional[torch.Tensor] = None):
+    """Per segment u = order[rowptr[u] : rowptr[u + 1]] (positions into `x`; `order` None: x is already grouped): the `q` quantile
+    of z = ((x - mean) / scale) + shift the way pandas' `quantile(q)` / numpy's `percentile(method="linear")` compute it, and every
+    z below it set to 0 (ngcf_segment_quantile_floor_f64; the formulae are in include/ngcf_hip.h).  fp64 throughout, every operation
+    rounded once: bit-equal to numpy up to the sign of a zero.  `rowptr` int64 [n_rows + 1], `x` float64 [T], `order` int64 [T] on one
+    device.  Returns `(out float64 [T] in the order of x, quant float64 [n_rows])`; the quantile of an empty segment is NaN.  `out`
+    may be `x` itself.  `q` is 0.25, 0.5 or 0.75.  `wave_max` (0: the default, 64) moves the switch between the kernel's two tiers
+    and never the result.  A NaN in a segment sets status bit 2: the segment's quantile is NaN and its z pass through unfloored.
+    A rowptr that decreases or leaves [0, T], or an order entry outside [0, T), sets bit 1 and leaves that segment's `out`
+    unwritten: IndexError after one host sync - or, with a caller's int32 `status` word, the bits are only OR-ed into it and the
+    call neither syncs nor raises."""
+    lib = _lib.load()
+    q4 = {0.25: 1, 0.5: 2, 0.75: 3}.get(float(q))
+    if q4 is None:
+        raise ValueError(f"segment_quantile_floor: q={q} is not one of 0.25, 0.5, 0.75")
+    wave_max = int(wave_max)
+    if wave_max < 0 or wave_max > QUANTILE_WAVE_MAX:
+        raise ValueError(f"segment_quantile_floor: wave_max={wave_max} outside [0, {QUANTILE_WAVE_MAX}]")
+    mean, scale, shift = float(mean), float(scale), float(shift)
+    if not (0.0 < scale < float("inf")):
+        raise ValueError(f"segment_quantile_floor: scale={scale} is not a finite positive number")
+    for t, nm in ((rowptr, "rowptr"), (order, "order")):
+        if t is not None and t.dtype != torch.int64:
+            raise TypeError(f"segment_quantile_floor: {nm} must be int64, got {t.dtype}")
+    for t, nm in ((x, "x"), (out, "out"), (quant, "quant")):
+        if t is not None and t.dtype != torch.float64:
+            raise TypeError(f"segment_quantile_floor: {nm} must be float64, got {t.dtype}")
+    if rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError(f"segment_quantile_floor: rowptr must be [n_rows + 1], got {tuple(rowptr.shape)}")
+    if x.dim() != 1:
+        raise ValueError(f"segment_quantile_floor: x must be [T], got {tuple(x.shape)}")
+    n_rows, T = int(rowptr.numel()) - 1, int(x.numel())
+    for t, nm, n, sym in ((order, "order", T, "T"), (out, "out", T, "T"), (quant, "quant", n_rows, "n_rows")):
+        if t is not None and (t.dim() != 1 or int(t.numel()) != n):
+            raise ValueError(f"segment_quantile_floor: {nm} must be [{sym} = {n}], got {tuple(t.shape)}")
+    _require_device(x, "x")
+    dev = x.device
+    for t, nm in ((rowptr, "rowptr"), (order, "order"), (out, "out"), (quant, "quant"), (status, "status")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"segment_quantile_floor: {nm} is on {t.device}, x on {dev}")
+    if status is not None and status.dtype != torch.int32:
+        raise ValueError(f"segment_quantile_floor: status must be an int32 tensor on {dev}")
+    for t, nm in ((x, "x"), (out, "out"), (quant, "quant")):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"segment_quantile_floor: {nm} must be contiguous")
+    rowptr = rowptr.contiguous()
+    order = None if order is None else order.contiguous()
+    if out is None:
+        out = torch.empty(T, dtype=torch.float64, device=dev)
+    if quant is None:
+        quant = torch.empty(n_rows, dtype=torch.float64, device=dev)
+    if T == 0:
+        quant.fill_(float("nan"))                  # the library does nothing without values: every segment is empty
+    check_status = status is None
+    if check_status:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(lib.ngcf_segment_quantile_floor_f64(_ptr(rowptr), n_rows, _ptr(order), _ptr(x), T, mean, scale, shift, q4, wave_max,
+                                                       _ptr(quant), _ptr(out), _ptr(status), _stream()))
+    if check_status and T and n_rows and int(status.item()) & 1:
+        raise IndexError(f"segment_quantile_floor: a segment's row pointers or order entries lie outside the {T} values")
+    return out, quant
+
+
 # ---- rank-point blending, the reference's recommender after its topk (ngcf_blend_points, csrc/blend.hip) ---------------------------
 BLEND_TOP_MAX = 256
 BLEND_POINTS_MAX = 1024
