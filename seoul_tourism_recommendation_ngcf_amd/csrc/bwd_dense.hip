@@ -100,7 +100,7 @@ __global__ void add_rows_kernel(float *__restrict__ out, int64_t ldo, const floa
 extern "C" int ngcf_add_rows_f32(float *out, int64_t ldo, const float *add, int64_t lda, int64_t n_rows, int d, void *stream_)
 {
     if (n_rows == 0) return NGCF_OK;
-    if (!out || !add || d <= 0) return fail(NGCF_ERR_ARG, "add_rows: bad argument");
+    if (!out || !add || d <= 0 || n_rows < 0 || ldo < d || lda < d) return fail(NGCF_ERR_ARG, "add_rows: bad argument");
     if (d % 4 == 0 && ldo % 4 == 0 && lda % 4 == 0 && aligned16(out) && aligned16(add))
         add_rows_kernel<4><<<grid_for(n_rows * (d / 4), 256), 256, 0, (hipStream_t)stream_>>>(out, ldo, add, lda, n_rows, d / 4);
     else
