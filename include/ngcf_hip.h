@@ -478,6 +478,37 @@ int ngcf_segment_quantile_floor_f64(const int64_t *rowptr, int64_t n_rows, const
                                     double mean, double scale, double shift, int q4, int wave_max,
                                     double *quant, double *out, int32_t *status, void *stream);
 
+/* Yeo-Johnson power transform, the numeric core of sklearn's PowerTransformer() that the reference's Preprocess.scale_implicit runs with
+ * args.scaler == 'power' (utils.py:107-112).  With eps = 2^-52,
+ *   psi(x, l) = log1p(x)                            x >= 0 (-0.0 included), |l| < eps
+ *             = (pow(x + 1, l) - 1) / l             x >= 0, otherwise
+ *             = -log1p(-x)                          x <  0, |l - 2| <= eps
+ *             = -(pow(-x + 1, 2 - l) - 1) / (2 - l) x <  0, otherwise
+ *             = x                                   x a NaN
+ * sklearn 1.7's _yeo_johnson_transform operation for operation: x + 1, pow, - 1, / l (and 2 - l, -x + 1, the final negation) are
+ * each an individually rounded fp64 operation (no FMA); what differs from numpy's result is the last bits of pow and log1p
+ * themselves, the device's libm against the host's.
+ * ngcf_yeo_johnson_f64: out[t] = psi(x[t], lambda) for t in [0, T); out may alias x.
+ * ngcf_yeo_johnson_moments_f64: one evaluation of the likelihood that fits lambda, over the rows whose x is not a NaN (sklearn drops
+ * NaNs before the fit), result[0..3] on the device:
+ *   n    = the number of such rows
+ *   mean = (sum psi(x, lambda)) / n
+ *   M2   = sum (psi(x, lambda) - mean)^2
+ *   c    = sum sign(x) * log1p(|x|)                 (it does not depend on lambda)
+ * so that the negative log-likelihood is n/2 * log(M2 / n) - (lambda - 1) * c.  Each thread keeps a running (n, mean, M2) in
+ * Welford's form over a grid-stride slice; partials are merged with Chan's formula in a fixed tree (wave, workgroup, one partial
+ * per workgroup in the workspace, a second launch of one workgroup for the rest): no floating-point atomics, and a grid that depends
+ * on T alone, so the four doubles are bit-identical from run to run.  ngcf_yeo_johnson_moments_launch reports that grid: the
+ * workgroups of the first launch for T rows, the threads of a workgroup, and the cap on the workgroups (any pointer may be NULL).
+ * workspace: ngcf_yeo_johnson_workspace_bytes(T) bytes, 8-byte aligned (-1 for T < 0).  Argument errors, before any launch: negative
+ * T, a NaN lambda, a null pointer, a workspace that is too small (NGCF_ERR_WORKSPACE).  T == 0 is not an error: the transform writes
+ * nothing, the moments are n = 0, mean = M2 = c = 0, and x and workspace may be NULL. */
+int ngcf_yeo_johnson_f64(const double *x, int64_t T, double lambda, double *out, void *stream);
+int64_t ngcf_yeo_johnson_workspace_bytes(int64_t T);
+int ngcf_yeo_johnson_moments_launch(int64_t T, int *blocks, int *threads, int *max_blocks);
+int ngcf_yeo_johnson_moments_f64(const double *x, int64_t T, double lambda, double *result, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

@@ -93,6 +93,10 @@ PROTOTYPES = {
     "ngcf_sample_unseen": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, C.c_int, _u64, _vp, _vp, _i64, _vp, _vp]),
     "ngcf_segment_quantile_floor_f64": (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp,
                                                  _vp, _vp]),
+    "ngcf_yeo_johnson_f64": (C.c_int, [_vp, _i64, C.c_double, _vp, _vp]),
+    "ngcf_yeo_johnson_workspace_bytes": (_i64, [_i64]),
+    "ngcf_yeo_johnson_moments_launch": (C.c_int, [_i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ngcf_yeo_johnson_moments_f64": (C.c_int, [_vp, _i64, C.c_double, _vp, _vp, _i64, _vp]),
     "ngcf_shard_plan": (C.c_int, [C.POINTER(_i64), _i64, _i64, C.c_int, C.POINTER(_i64)]),
     "ngcf_allgather_rows": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "ngcf_comm_size": (C.c_int, [_vp, C.POINTER(C.c_int)]),

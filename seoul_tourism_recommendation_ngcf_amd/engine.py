@@ -921,6 +921,67 @@ def segment_quantile_floor(rowptr: torch.Tensor, x: torch.Tensor, *, order: Opti
     return out, quant
 
 
+# ---- Yeo-Johnson power transform, the core of the reference's scaler='power' (ngcf_yeo_johnson_*_f64, csrc/yeo_johnson.hip) ----------
+def yeo_johnson_launch(T: int):
+    """`(blocks, threads, max_blocks)` of the moments kernel's first launch for a column of T rows (a function of T alone, which is
+    what makes the reduction reproducible): a grid stride is blocks * threads rows, the workspace one partial per block."""
+    blocks, threads, cap = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().ngcf_yeo_johnson_moments_launch(int(T), C.byref(blocks), C.byref(threads), C.byref(cap)))
+    return blocks.value, threads.value, cap.value
+
+
+def _yeo_johnson_args(fn: str, x: torch.Tensor, lam) -> float:
+    lam = float(lam)
+    if lam != lam:
+        raise ValueError(f"{fn}: lam is NaN")
+    if x.dtype != torch.float64:
+        raise TypeError(f"{fn}: x must be float64, got {x.dtype}")
+    if x.dim() != 1:
+        raise ValueError(f"{fn}: x must be [T], got {tuple(x.shape)}")
+    _require_device(x, "x")
+    if not x.is_contiguous():
+        raise ValueError(f"{fn}: x must be contiguous")
+    return lam
+
+
+def yeo_johnson(x: torch.Tensor, lam: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """psi(x, lam) elementwise, sklearn's `_yeo_johnson_transform` operation for operation in fp64 (ngcf_yeo_johnson_f64; the
+    formulae are in include/ngcf_hip.h): `x` float64 [T] on the device, the result float64 [T].  `out` may be `x` itself.  A NaN
+    passes through."""
+    lib = _lib.load()
+    lam = _yeo_johnson_args("yeo_johnson", x, lam)
+    T = int(x.numel())
+    if out is None:
+        out = torch.empty(T, dtype=torch.float64, device=x.device)
+    else:
+        if out.dtype != torch.float64:
+            raise TypeError(f"yeo_johnson: out must be float64, got {out.dtype}")
+        if out.dim() != 1 or int(out.numel()) != T:
+            raise ValueError(f"yeo_johnson: out must be [T = {T}], got {tuple(out.shape)}")
+        if out.device != x.device:
+            raise RuntimeError(f"yeo_johnson: out is on {out.device}, x on {x.device}")
+        if not out.is_contiguous():
+            raise ValueError("yeo_johnson: out must be contiguous")
+    with _on(x.device):
+        _lib.check(lib.ngcf_yeo_johnson_f64(_ptr(x), T, lam, _ptr(out), _stream()))
+    return out
+
+
+def yeo_johnson_moments(x: torch.Tensor, lam: float) -> torch.Tensor:
+    """One evaluation of the likelihood that fits the Yeo-Johnson lambda, in one fused pass over `x` (float64 [T] on the device):
+    a float64 [4] tensor on the device holding, over the rows that are not NaN, their count n, the mean of psi(x, lam),
+    M2 = sum (psi - mean)^2 and c = sum sign(x) log1p|x| (ngcf_yeo_johnson_moments_f64).  Bit-identical from call to call."""
+    lib = _lib.load()
+    lam = _yeo_johnson_args("yeo_johnson_moments", x, lam)
+    T = int(x.numel())
+    result = torch.empty(4, dtype=torch.float64, device=x.device)
+    nbytes = int(lib.ngcf_yeo_johnson_workspace_bytes(T))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
+    with _on(x.device):
+        _lib.check(lib.ngcf_yeo_johnson_moments_f64(_ptr(x), T, lam, _ptr(result), _ptr(ws), nbytes, _stream()))
+    return result
+
+
 # ---- rank-point blending, the reference's recommender after its topk (ngcf_blend_points, csrc/blend.hip) ---------------------------
 BLEND_TOP_MAX = 256
 BLEND_POINTS_MAX = 1024

@@ -9,14 +9,20 @@ order: given the same (mean, scale, shift) the ratings are bit-equal to the refe
 With it the chain runs on one device with no host loop: counts -> `scale_implicit` -> `matrix.laplacian_slices` / `positives` ->
 `sampling.train_triplets` -> training step -> `evaluate.candidate_ranking` -> `recommend.blended_ranking`.
 
-Not here: `scaler='power'` (Yeo-Johnson: its lambda needs an optimiser), `load_preprocess_data` and `map_ids` (pandas string keys,
-host work), `split_train_test` (`graphs.holdout_split` exists), and the reference's index-alignment quirk when year-20 rows are
-filtered before the scaler's output is assigned back.
+The reference's other scaler, `args.scaler == 'power'` (sklearn's PowerTransformer(): Yeo-Johnson, then the same standardisation),
+is `fit_power`: lambda by Brent's method on the host, every evaluation of the likelihood one fused pass on the device
+(engine.yeo_johnson_moments), and `scale_implicit(..., scaler=fit_power(visitors))` floors the transformed column.
+
+Not here: the string `scaler='power'` as an alias of that (it stays refused, with a message that says what to pass, until a change
+that may edit the test pinning the refusal), Box-Cox and `inverse_transform`, `load_preprocess_data` and `map_ids` (pandas string
+keys, host work), `split_train_test` (`graphs.holdout_split` exists), and the reference's index-alignment quirk when year-20 rows
+are filtered before the scaler's output is assigned back.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -60,28 +66,181 @@ def standard_stats(x: torch.Tensor):
     return mean, scale, shift
 
 
-def scale_implicit(users: torch.Tensor, visitors: torch.Tensor, *, n_user: int, scaler: Optional[str] = "standard", q: float = 0.25,
-                   stats: Optional[Sequence[float]] = None):
+# ---- the reference's scaler='power': sklearn's PowerTransformer() = Yeo-Johnson with standardize=True ------------------------------
+_GOLD = 1.618034               # the classic constants of bracketing and of Brent's golden step, as scipy's `brent` has them
+_CGOLD = 0.3819660
+_TINY = 2.2250738585072014e-308
+
+
+def _bracket(f, xa: float, xb: float, grow: float = 110.0, maxiter: int = 1000):
+    """Downhill from (xa, xb) in golden-ratio steps, with a parabolic guess where it lands inside the allowed stretch, until three
+    points xa, xb, xc with f(xb) below both ends bracket a minimum.  Returns (xa, xb, xc, fa, fb, fc)."""
+    fa, fb = f(xa), f(xb)
+    if fa < fb:
+        xa, xb, fa, fb = xb, xa, fb, fa
+    xc = xb + _GOLD * (xb - xa)
+    fc = f(xc)
+    it = 0
+    while fc < fb:
+        t1 = (xb - xa) * (fb - fc)
+        t2 = (xb - xc) * (fb - fa)
+        val = t2 - t1
+        denom = 2.0 * (1e-21 if abs(val) < 1e-21 else val)
+        w = xb - ((xb - xc) * t2 - (xb - xa) * t1) / denom
+        wlim = xb + grow * (xc - xb)
+        if it > maxiter:
+            raise RuntimeError("yeo_johnson_lambda: no bracket of a minimum found")
+        it += 1
+        if (w - xc) * (xb - w) > 0.0:                      # the parabola's vertex lies between xb and xc
+            fw = f(w)
+            if fw < fc:
+                return xb, w, xc, fb, fw, fc
+            if fw > fb:
+                return xa, xb, w, fa, fb, fw
+            w = xc + _GOLD * (xc - xb)
+            fw = f(w)
+        elif (w - wlim) * (wlim - xc) >= 0.0:              # beyond the limit: step to the limit
+            w = wlim
+            fw = f(w)
+        elif (w - wlim) * (xc - w) > 0.0:                  # between xc and the limit
+            fw = f(w)
+            if fw < fc:
+                xb, xc, fb, fc = xc, w, fc, fw
+                w = xc + _GOLD * (xc - xb)
+                fw = f(w)
+        else:
+            w = xc + _GOLD * (xc - xb)
+            fw = f(w)
+        xa, xb, xc, fa, fb, fc = xb, xc, w, fb, fc, fw
+    return xa, xb, xc, fa, fb, fc
+
+
+def _brent(f, brack, tol: float, maxiter: int) -> float:
+    """Brent's minimiser (Brent 1973, ch. 5): parabolic interpolation through the three best points where the step is acceptable,
+    a golden-section step otherwise; stops when the interval around x is within 2 * tol1, tol1 = tol * |x| + 1e-11."""
+    xa, xb, xc, _, fb, _ = _bracket(f, float(brack[0]), float(brack[1]))
+    x = w = v = xb
+    fx = fw = fv = fb
+    a, b = (xa, xc) if xa < xc else (xc, xa)
+    deltax, rat = 0.0, 0.0
+    for _ in range(maxiter):
+        tol1 = tol * abs(x) + 1e-11
+        tol2 = 2.0 * tol1
+        xmid = 0.5 * (a + b)
+        if abs(x - xmid) < tol2 - 0.5 * (b - a):
+            break
+        golden = abs(deltax) <= tol1
+        if not golden:
+            t1 = (x - w) * (fx - fv)
+            t2 = (x - v) * (fx - fw)
+            p = (x - v) * t2 - (x - w) * t1
+            t2 = 2.0 * (t2 - t1)
+            if t2 > 0.0:
+                p = -p
+            t2 = abs(t2)
+            before, deltax = deltax, rat
+            if p > t2 * (a - x) and p < t2 * (b - x) and abs(p) < abs(0.5 * t2 * before):
+                rat = p / t2
+                u = x + rat
+                if u - a < tol2 or b - u < tol2:
+                    rat = tol1 if xmid - x >= 0 else -tol1
+            else:
+                golden = True
+        if golden:
+            deltax = (a - x) if x >= xmid else (b - x)
+            rat = _CGOLD * deltax
+        if abs(rat) < tol1:
+            u = x + tol1 if rat >= 0 else x - tol1
+        else:
+            u = x + rat
+        fu = f(u)
+        if fu > fx:
+            if u < x:
+                a = u
+            else:
+                b = u
+            if fu <= fw or w == x:
+                v, w, fv, fw = w, u, fw, fu
+            elif fu <= fv or v == x or v == w:
+                v, fv = u, fu
+        else:
+            if u >= x:
+                a = x
+            else:
+                b = x
+            v, w, x, fv, fw, fx = w, x, u, fw, fx, fu
+    return x
+
+
+def yeo_johnson_lambda(x: torch.Tensor, *, brack: Tuple[float, float] = (-2.0, 2.0), tol: float = 1.48e-8, maxiter: int = 500) -> float:
+    """The maximum-likelihood lambda of the Yeo-Johnson transform of the column `x` (any real dtype, [T], on the device), the
+    `lambdas_[0]` of sklearn's PowerTransformer: Brent's method on the host from the bracket `brack`, with scipy's `brent` defaults
+    (`tol`, tol1 = tol * |lambda| + 1e-11), minimising f(lambda) = n/2 * log(M2 / n) - (lambda - 1) * c, +inf where M2 / n is below
+    the smallest normal double.  Every evaluation is one `engine.yeo_johnson_moments` launch and one 32-byte read-back; NaN rows are
+    left out.  A column without a finite row raises ValueError."""
+    if x.dim() != 1:
+        raise ValueError(f"yeo_johnson_lambda: x must be [T], got {tuple(x.shape)}")
+    engine._require_device(x, "x")
+    xd = x.to(torch.float64).contiguous()
+    if not bool(torch.isfinite(xd).any()):
+        raise ValueError("yeo_johnson_lambda: the column has no finite row")
+
+    def f(lam: float) -> float:
+        n, _, m2, c = engine.yeo_johnson_moments(xd, lam).tolist()
+        var = m2 / n
+        if var < _TINY:
+            return math.inf
+        return n / 2 * math.log(var) - (lam - 1) * c
+    return _brent(f, brack, float(tol), int(maxiter))
+
+
+@dataclass(frozen=True)
+class PowerScaler:
+    """A fitted PowerTransformer(): the Yeo-Johnson `lam`, and the `(mean, scale, shift)` of `standard_stats` over the transformed
+    column - sklearn's internal StandardScaler followed by the reference's `+ |min|`."""
+    lam: float
+    mean: float
+    scale: float
+    shift: float
+
+
+def fit_power(x: torch.Tensor) -> PowerScaler:
+    """The reference's `args.scaler == 'power'` fitted on the column `x` ([T], on the device): `lam = yeo_johnson_lambda(x)`, then
+    `standard_stats` of psi(x, lam).  Pass the result as `scale_implicit(..., scaler=...)`."""
+    lam = yeo_johnson_lambda(x)
+    mean, scale, shift = standard_stats(engine.yeo_johnson(x.to(torch.float64).contiguous(), lam))
+    return PowerScaler(lam, mean, scale, shift)
+
+
+def scale_implicit(users: torch.Tensor, visitors: torch.Tensor, *, n_user: int, scaler: Union[str, PowerScaler, None] = "standard",
+                   q: float = 0.25, stats: Optional[Sequence[float]] = None):
     """The ratings of `Preprocess.scale_implicit`: row t belongs to user `users[t]` (int64 [T], ids in [0, n_user)) and carries the
     raw count `visitors[t]` (any real dtype, [T], same device).  Returns `(ratings float64 [T] in input order, quartiles float64
     [n_user])`: z = ((visitors - mean) / scale) + shift, floored to 0 below the user's `q` quantile (pandas' `quantile(q)`) of z
     over all of the user's rows; the quartile of a user without rows is NaN.  `scaler="standard"` takes (mean, scale, shift) from
     `standard_stats(visitors)`, or from `stats` when given - then the result is a pure function of its inputs, bit-equal to numpy's;
-    `scaler=None` floors the raw values.  `scaler="power"` (the reference's PowerTransformer option) raises NotImplementedError: the
-    Yeo-Johnson lambda needs an optimiser this package does not have yet.  `q` is 0.25 (the reference), 0.5 or 0.75.  A user id
+    `scaler=None` floors the raw values.  A `PowerScaler` (from `fit_power(visitors)`: the reference's PowerTransformer option)
+    writes psi(visitors, lam) into a fresh fp64 buffer and floors that with the scaler's own (mean, scale, shift); `stats` beside it
+    is a ValueError.  The string `scaler="power"` still raises NotImplementedError (Yeo-Johnson: pass `fit_power(visitors)`); making
+    it an alias waits for a change that may edit the test that pins the refusal.  `q` is 0.25 (the reference), 0.5 or 0.75.  A user id
     outside [0, n_user) raises IndexError.  A NaN count leaves its user's ratings unfloored (the comparison with a NaN quartile is
     false, as in pandas)."""
-    if scaler == "power":
-        raise NotImplementedError("scale_implicit: scaler='power' (PowerTransformer, Yeo-Johnson) is not implemented: its lambda is "
-                                  "fitted by an optimiser; use scaler='standard' or transform the counts beforehand and pass scaler=None")
-    if scaler not in ("standard", None):
-        raise ValueError(f"scale_implicit: scaler={scaler!r} is neither 'standard', 'power' nor None")
+    power = scaler if isinstance(scaler, PowerScaler) else None
+    if power is None and scaler == "power":
+        raise NotImplementedError("scale_implicit: the string scaler='power' (PowerTransformer, Yeo-Johnson) is not an option yet: "
+                                  "fit the transform and pass it, scaler=preprocess.fit_power(visitors)")
+    if power is None and scaler not in ("standard", None):
+        raise ValueError(f"scale_implicit: scaler={scaler!r} is neither 'standard', a PowerScaler, 'power' nor None")
+    if power is not None and stats is not None:
+        raise ValueError("scale_implicit: a PowerScaler carries its own (mean, scale, shift); stats cannot be passed with it")
     if users.dim() != 1 or visitors.dim() != 1 or users.numel() != visitors.numel():
         raise ValueError(f"scale_implicit: users [T] and visitors [T] expected, got {tuple(users.shape)} and {tuple(visitors.shape)}")
     engine._require_device(users, "users")
     if visitors.device != users.device:
         raise RuntimeError(f"scale_implicit: visitors is on {visitors.device}, users on {users.device}")
-    if scaler is None:
+    if power is not None:
+        mean, scale, shift = power.mean, power.scale, power.shift
+    elif scaler is None:
         if stats is not None:
             raise ValueError("scale_implicit: stats are the standard scaler's; scaler=None takes none")
         mean, scale, shift = 0.0, 1.0, 0.0
@@ -91,6 +250,8 @@ def scale_implicit(users: torch.Tensor, visitors: torch.Tensor, *, n_user: int, 
         mean, scale, shift = standard_stats(visitors)
     rowptr, order = engine.segments_from_ids(users.to(torch.int64), int(n_user))
     x = visitors.to(torch.float64).contiguous()
+    if power is not None:
+        x = engine.yeo_johnson(x, power.lam)                              # a fresh buffer
     out = x if x.data_ptr() != visitors.data_ptr() else None              # a converted copy is floored in place
     return engine.segment_quantile_floor(rowptr, x, order=order, mean=mean, scale=scale, shift=shift, q=q, out=out)
 
