@@ -509,6 +509,62 @@ int ngcf_yeo_johnson_moments_launch(int64_t T, int *blocks, int *threads, int *m
 int ngcf_yeo_johnson_moments_f64(const double *x, int64_t T, double lambda, double *result, void *workspace, int64_t workspace_bytes,
                                  void *stream);
 
+/* ---- year-slice Laplacians straight into CSR (csrc/laplacian.hip; the reference's Matrix.create_matrix, matrix.py:12-83) ----
+ * What matrix.laplacian_slices computes, with the state of R kept between years as a user-sorted CSR (rowptr int64[n_user + 1],
+ * item int32, rating fp32) instead of a sorted key list.  Years are taken in order of first appearance; within a year the last
+ * record of a (user, item) in input order wins, a newer year overrides an older one, a rating that compares == 0 (-0.0 too)
+ * deletes the edge, carried over or not; the degree of a node is the count of its state entries.  One year is five calls:
+ *   1. ngcf_laplacian_bucket   histogram of the year's T records by user (integer atomics: counts are order-free), exclusive scan
+ *        -> bptr int64[n_user + 1], scatter of (item, sequence number = position in the year's input, rating) into per-user buckets
+ *        b_item / b_seq / b_rating [T].  The order inside a bucket is arbitrary; the sequence number is what makes "last wins"
+ *        deterministic.  info int32[4]: [0] status (bit 1: an id outside [0, n_user) / [0, n_item): the record is left out of the
+ *        buckets, never read through - NGCF_ERR_INDEX is the caller's to raise after reading the word back), [1] rows of the
+ *        workgroup class, [2] rows of the long-row class (they size step 2's launches and tables).  count: int32[n_user] scratch.
+ *   2. ngcf_laplacian_resolve  per user with new records: the sorted state row merged with the bucket by (item, sequence), the last
+ *        of every item kept, == 0 dropped, written to the scratch row t_item / t_rating [old_nnz + T] at old_rowptr[u] + bptr[u];
+ *        users without records are copied through in step 3.  Three classes by candidate count (old + new), limits from
+ *        ngcf_laplacian_limits: up to the wave limit a wave per row ranks the candidates in registers with cross-lane reads; up
+ *        to the workgroup limit a workgroup sorts them in LDS (bitonic); above it a workgroup uses a table of 2 * n_item words in
+ *        long_tables (n_tables of them, one per workgroup: an integer max of the sequence numbers per item, the winners' ratings,
+ *        an ordered sweep) - right for any length, also a bucket longer than n_item.  Then deg int32[N]: users = resolved counts,
+ *        items = an integer histogram; rowptr int64[N + 1] = its exclusive scan: the slice's row pointers, and rowptr[0 .. n_user]
+ *        the new state's.  status bit 2: a state row pointer or item out of range; bit 4: a long row and no table for it.
+ *      (host: ds = float32 d^-1/2 of deg with inf -> 0, by numpy's float32 power - that routine is not correctly rounded, so its
+ *       bits cannot be reproduced here; this N-sized vector is the one read-back of a year besides the counts that size arrays.)
+ *   3. ngcf_laplacian_emit     the new state s_item / s_rating [nnz] and its users s_user [nnz]; the user rows of the slice:
+ *        colidx = n_user + item, vals = float((double(ds[u]) * double(w)) * double(ds[n_user + i])); and vals_item, the item
+ *        row's own float((double(ds[n_user + i]) * double(w)) * double(ds[u])) - two separately rounded products, no FMA.
+ *        *zeros: how many of the 2 * nnz values are 0 (a device count: the common case has none and pays no pass for them).
+ *   4. (caller: the stable order of the int32 s_item - one library sort of 32-bit keys.)
+ *      ngcf_laplacian_item_rows  colidx[e] = s_user[order[e]], vals[e] = vals_item[order[e]]: the item rows, by (item, user).
+ *   5. ngcf_laplacian_drop_zeros  only when *zeros != 0: the slice without its zero values (they stay in the state and in the
+ *        degrees): count int32[n_rows] scratch, out_rowptr int64[n_rows + 1], out_colidx / out_vals [out_nnz = nnz - zeros].
+ * The result per slice is one [N, N] CSR: rowptr int64[N + 1], colidx int32, vals fp32, the user rows followed by the item rows.
+ * workspace: ngcf_laplacian_workspace_bytes(n_user, n_item) bytes, 8-byte aligned (-1 for sizes that do not fit).  NaN ratings are
+ * undefined (a NaN is kept as an edge; nothing is read out of bounds).  No floating-point atomics: two builds give the same bytes.
+ * Argument errors, before any launch (NGCF_ERR_ARG, message "laplacian: ..."): a null pointer, a negative count,
+ * n_user + n_item >= 2^31, more than 2^31 - 1 records in one year; NGCF_ERR_WORKSPACE for a workspace that is too small.
+ */
+int ngcf_laplacian_limits(int *wave_limit, int *workgroup_limit);
+int64_t ngcf_laplacian_workspace_bytes(int64_t n_user, int64_t n_item);
+int ngcf_laplacian_bucket(const int64_t *userid, const int64_t *itemid, const float *rating, int64_t T, int64_t n_user, int64_t n_item,
+                          const int64_t *old_rowptr, int32_t *count, int64_t *bptr, int32_t *b_item, int32_t *b_seq, float *b_rating,
+                          int32_t *info, void *workspace, int64_t workspace_bytes, void *stream);
+int ngcf_laplacian_resolve(const int64_t *old_rowptr, const int32_t *old_item, const float *old_rating, int64_t old_nnz,
+                           const int64_t *bptr, const int32_t *b_item, const int32_t *b_seq, const float *b_rating, int64_t T,
+                           int64_t n_user, int64_t n_item, int64_t n_block_rows, int64_t n_long_rows, int32_t *t_item, float *t_rating,
+                           int32_t *deg, int64_t *rowptr, uint32_t *long_tables, int64_t n_tables, int32_t *status, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int ngcf_laplacian_emit(const int64_t *old_rowptr, const int32_t *old_item, const float *old_rating, int64_t old_nnz,
+                        const int64_t *bptr, int64_t T, const int32_t *t_item, const float *t_rating, int64_t n_user, int64_t n_item,
+                        const int32_t *deg, const int64_t *rowptr, const float *ds, int64_t nnz, int32_t *s_item, float *s_rating,
+                        int32_t *s_user, int32_t *colidx, float *vals, float *vals_item, uint64_t *zeros, int32_t *status, void *stream);
+int ngcf_laplacian_item_rows(const int64_t *order, const int32_t *s_user, const float *vals_item, int64_t nnz, int32_t *colidx,
+                             float *vals, int32_t *status, void *stream);
+int ngcf_laplacian_drop_zeros(const int64_t *rowptr, const int32_t *colidx, const float *vals, int64_t n_rows, int64_t nnz,
+                              int32_t *count, int64_t *out_rowptr, int32_t *out_colidx, float *out_vals, int64_t out_nnz,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

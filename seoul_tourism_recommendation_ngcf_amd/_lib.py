@@ -97,6 +97,15 @@ PROTOTYPES = {
     "ngcf_yeo_johnson_workspace_bytes": (_i64, [_i64]),
     "ngcf_yeo_johnson_moments_launch": (C.c_int, [_i64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ngcf_yeo_johnson_moments_f64": (C.c_int, [_vp, _i64, C.c_double, _vp, _vp, _i64, _vp]),
+    "ngcf_laplacian_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ngcf_laplacian_workspace_bytes": (_i64, [_i64, _i64]),
+    "ngcf_laplacian_bucket": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ngcf_laplacian_resolve": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
+                                         _vp, _vp, _i64, _vp]),
+    "ngcf_laplacian_emit": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "ngcf_laplacian_item_rows": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ngcf_laplacian_drop_zeros": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "ngcf_shard_plan": (C.c_int, [C.POINTER(_i64), _i64, _i64, C.c_int, C.POINTER(_i64)]),
     "ngcf_allgather_rows": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "ngcf_comm_size": (C.c_int, [_vp, C.POINTER(C.c_int)]),

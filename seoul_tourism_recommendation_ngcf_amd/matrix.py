@@ -12,6 +12,12 @@ fp32 `[N, N]` tensors indexed by `year % 18` - from the triplets alone, and keep
 
 Bit-exact against the reference on the golden fixtures (tests/test_matrix.py).  Same constructor arguments as the
 reference class; `total_df` is a pandas frame with the columns named in `cols`.
+
+Two builders give the same slices bit for bit.  `laplacian_slices` is torch ops on either device (sorts of 64-bit keys over
+the whole state per year, int64 COO out) and is the oracle.  `laplacian_csr_slices` (`Matrix(builder="device")`) is hand-written
+HIP (csrc/laplacian.hip) and needs a ROCm device: the state of `R` stays a user-sorted CSR, a year's records are bucketed by
+user and merged row by row, and every slice comes out as the int32 CSR the engine works on (`LaplacianSlice`).  Only the N-sized
+`d^-1/2` stays a host call in both: numpy's float32 power is not correctly rounded, so its bits cannot be had elsewhere.
 """
 from __future__ import annotations
 
@@ -22,6 +28,8 @@ from datetime import datetime
 
 import numpy as np
 import torch
+
+from . import engine
 
 
 def laplacian_slices(year, userid, itemid, rating, n_user: int, n_item: int, device="cpu"):
@@ -74,12 +82,72 @@ def laplacian_slices(year, userid, itemid, rating, n_user: int, n_item: int, dev
     return out
 
 
+class LaplacianSlice:
+    """One year slice as the [N, N] CSR the engine works on: `rowptr` int64 [N + 1], `colidx` int32 [nnz], `vals` float32 [nnz],
+    user rows followed by item rows, on the device that built them."""
+
+    def __init__(self, rowptr: torch.Tensor, colidx: torch.Tensor, vals: torch.Tensor, n: int):
+        self.rowptr, self.colidx, self.vals, self.n = rowptr, colidx, vals, int(n)
+        self._rows = None
+
+    @property
+    def nnz(self) -> int:
+        return int(self.colidx.numel())
+
+    def coo(self):
+        """`(rows int64, cols int64, vals)`: what `laplacian_slices` returns for the slice.  The rows are expanded from `rowptr`
+        on first use."""
+        if self._rows is None:
+            self._rows = torch.repeat_interleave(torch.arange(self.n, dtype=torch.int64, device=self.rowptr.device),
+                                                 self.rowptr[1:] - self.rowptr[:-1], output_size=self.nnz)
+        return self._rows, self.colidx.to(torch.int64), self.vals
+
+    def sparse_coo(self) -> torch.Tensor:
+        """The `lap_list` element (matrix.py:79-83): a sparse COO tensor, flagged un-coalesced."""
+        rows, cols, vals = self.coo()
+        return torch.sparse_coo_tensor(torch.stack([rows, cols]), vals, (self.n, self.n))
+
+    def csr(self) -> "engine.LaplacianCSR":
+        """The engine's handle on these very arrays, without a COO round trip."""
+        return engine.LaplacianCSR.from_csr_arrays(self.rowptr, self.colidx, self.vals, self.n)
+
+
+def laplacian_csr_slices(year, userid, itemid, rating, n_user: int, n_item: int, device):
+    """{year_idx: LaplacianSlice}: `laplacian_slices` by the HIP builder (`engine.build_laplacian_year`, one call per year in order of
+    first appearance), bit for bit the same entries in the same order.  `device` must be a ROCm device: there is no CPU fallback.
+    NaN ratings are undefined (the torch builder keeps them as edges; so does this one, but nothing pins it)."""
+    year = torch.as_tensor(year, dtype=torch.int64, device=device)
+    engine._require_device(year, "laplacian_csr_slices: the records")
+    userid = torch.as_tensor(userid, dtype=torch.int64, device=device)
+    itemid = torch.as_tensor(itemid, dtype=torch.int64, device=device)
+    rating = torch.as_tensor(rating, dtype=torch.float32, device=device)
+    # pandas .unique(): order of first appearance
+    uniq, inv = torch.unique(year, return_inverse=True)
+    first = torch.full((uniq.numel(),), year.numel(), dtype=torch.int64, device=year.device)
+    first.scatter_reduce_(0, inv, torch.arange(year.numel(), device=year.device), reduce="amin")
+    years = [int(uniq[k]) for k in torch.argsort(first).tolist()]
+    state = engine.empty_laplacian_state(n_user, year.device)
+    out = {}
+    for y in years:
+        sel = year == y
+        state, rowptr, colidx, vals = engine.build_laplacian_year(state, userid[sel], itemid[sel], rating[sel], n_user, n_item)
+        out[int(y) % 18] = LaplacianSlice(rowptr, colidx, vals, n_user + n_item)
+    return out
+
+
 class Matrix(torch.nn.Module):
-    """Same surface as the reference's `Matrix` (matrix.py:12-76): `create_matrix()` -> `lap_list`."""
+    """Same surface as the reference's `Matrix` (matrix.py:12-76): `create_matrix()` -> `lap_list`.  `builder="torch"` (the
+    default) builds through `laplacian_slices` on `device`; `builder="device"` through `laplacian_csr_slices`, on a ROCm device only."""
 
     def __init__(self, total_df, cols: list, rating_col: str, num_dict: dict, folder_path: str = "",
-                 save_data: bool = False, device="cpu"):
+                 save_data: bool = False, device="cpu", builder: str = "torch"):
         super().__init__()
+        if builder not in ("torch", "device"):
+            raise ValueError(f"Matrix: builder={builder!r} is neither 'torch' nor 'device'")
+        if builder == "device" and torch.device(device).type != "cuda":
+            raise RuntimeError(f"Matrix: builder='device' on '{device}': the HIP builder runs on a ROCm device only "
+                               "(hand-written HIP kernels, no CPU/PyTorch fallback); use builder='torch' or device='cuda'.")
+        self.builder = builder
         self.df = total_df[cols]
         self.rating_col = rating_col
         self.folder_path = folder_path
@@ -93,6 +161,14 @@ class Matrix(torch.nn.Module):
 
     def create_matrix(self):
         N = self.n_user + self.n_item
+        if self.builder == "device":
+            slices = laplacian_csr_slices(self.df['year'].values, self.df['userid'].values, self.df['itemid'].values,
+                                          self.df[self.rating_col].values, self.n_user, self.n_item, self.device)
+            for yi, sl in slices.items():
+                self.lap_list[yi] = sl.sparse_coo()
+            if self.save_data:                               # matrix.py:70-75
+                self.saved_path = save_lap_list(self.lap_list, self.folder_path, self.file_tag)
+            return self.lap_list
         slices = laplacian_slices(self.df['year'].values, self.df['userid'].values, self.df['itemid'].values,
                                   self.df[self.rating_col].values, self.n_user, self.n_item, self.device)
         for yi, (r, c, v) in slices.items():

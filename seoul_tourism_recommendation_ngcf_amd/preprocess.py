@@ -6,8 +6,9 @@ items, and a masked write that sets every rating below that quartile to 0 - O(us
 own rows, so here one call (engine.segment_quantile_floor) does every user at once, with the same fp64 operations in the same
 order: given the same (mean, scale, shift) the ratings are bit-equal to the reference's, up to the sign of a zero.
 
-With it the chain runs on one device with no host loop: counts -> `scale_implicit` -> `matrix.laplacian_slices` / `positives` ->
-`sampling.train_triplets` -> training step -> `evaluate.candidate_ranking` -> `recommend.blended_ranking`.
+With it the chain runs on one device with no host loop: counts -> `scale_implicit` -> `matrix.laplacian_csr_slices` (HIP kernels;
+`matrix.laplacian_slices` is the same in torch ops, and its oracle) / `positives` -> `sampling.train_triplets` -> training step ->
+`evaluate.candidate_ranking` -> `recommend.blended_ranking`.
 
 The reference's other scaler, `args.scaler == 'power'` (sklearn's PowerTransformer(): Yeo-Johnson, then the same standardisation),
 is `fit_power`: lambda by Brent's method on the host, every evaluation of the likelihood one fused pass on the device
