@@ -160,6 +160,9 @@ int ngcf_spmm_product_width(const ngcf_csr_t *csr, const float *E, int64_t ldE, 
  * L is thinned the same way: pass `transposed` != 0 when `csr` holds L^T (the backward pass), and L^T loses exactly the
  * entries L lost.  (Entries stored twice at the same (i, j) share their fate.)  The mask is a counter-based hash, not
  * torch's generator: same distribution as the reference, different stream.
+ * The threshold: `drop_p` is taken as a FLOAT (a caller's double is rounded to float first: 0.3 arrives as 0.300000011920929),
+ * and an entry is kept iff every one of its 32-bit hashes is >= (uint32_t)((double)drop_p * 2^32) - for 0.3 that is
+ * 1288490240, not the 1288490188 of the double 0.3.  A host mask must use the same number (tests/dropout_oracle.py).
  */
 int ngcf_spmm_csr_dropout_f32(const ngcf_csr_t *csr, const float *E, int64_t ldE, int d, float *LE, int64_t ldLE,
                               float drop_p, const uint64_t *seeds, int n_seeds, int transposed,
@@ -321,7 +324,8 @@ int ngcf_layer_bwd_pre_f32(const float *dN, int64_t ldn, const float *dC, int64_
  * (zero row); init: compact [R, d] or NULL, added to the rows with slot >= 0 (the direct part of the gradient).
  * out[c, :] = (slot[c] >= 0 ? init[slot[c], :] : 0) + sum over the stored entries (c, r, v) of csr_t with slot[r] >= 0 of
  * v * X[slot[r], :], in entry order: a fixed summation order, no atomics; every row of out [N, d] is written.
- * drop_p / seeds: device-side node dropout as in ngcf_spmm_csr_dropout_f32 (csr_t is walked as the transpose).
+ * drop_p / seeds: device-side node dropout as in ngcf_spmm_csr_dropout_f32 (csr_t is walked as the transpose): drop_p is taken
+ * as a float, and an entry is kept iff every one of its hashes is >= (uint32_t)((double)drop_p * 2^32).
  * workspace: ngcf_spmm_workspace_bytes(csr_t, min(d, 512)) bytes (partial sums of the cut rows). */
 int ngcf_spmm_t_rows_f32(const ngcf_csr_t *csr_t, const int32_t *slot, const float *X, int64_t ldx, int d, const float *init,
                          int64_t ldi, float *out, int64_t ldo, float drop_p, const uint64_t *seeds, int n_seeds,

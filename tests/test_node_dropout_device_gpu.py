@@ -6,32 +6,11 @@ import torch
 
 import ngcf_oracle as orc
 from conftest import load_golden
+from dropout_oracle import keep_mask        # the library's mask with the library's threshold: p is taken as a float
 from golden_util import batch_of, ctor_args, lap_list_of, layer_params, sd_of
 
 pytestmark = pytest.mark.gpu
-M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-def mix32(x):
-    x = x.astype(np.uint64)
-    x ^= x >> np.uint64(33)
-    x = (x * np.uint64(0xff51afd7ed558ccd)) & M64
-    x ^= x >> np.uint64(33)
-    x = (x * np.uint64(0xc4ceb9fe1a85ec53)) & M64
-    x ^= x >> np.uint64(33)
-    return (x & np.uint64(0xFFFFFFFF)).astype(np.uint64)
-
-
-def keep_mask(rows, cols, seeds, p):
-    """The library's mask (csrc/common.h, edge_keep): keyed by the entry's (row, column) in L."""
-    key = (np.asarray(rows).astype(np.uint64) << np.uint64(32)) | (np.asarray(cols).astype(np.uint64) & np.uint64(0xFFFFFFFF))
-    nnz = key.size
-    e = (key * np.uint64(0x9E3779B97F4A7C15)) & M64
-    thr = np.uint64(int(p * 4294967296.0))
-    keep = np.ones(nnz, bool)
-    for s in seeds:
-        keep &= mix32(np.uint64(s) ^ e) >= thr
-    return keep
+ATOL, RTOL = 2e-5, 2e-3            # forward tolerance against fp64 (tests/test_parity_gpu.py)
 
 
 def test_dropout_spmm_matches_host_mask_and_statistics():
@@ -52,6 +31,15 @@ def test_dropout_spmm_matches_host_mask_and_statistics():
         want = eng.spmm(thin, X)                                        # values are NOT rescaled
         scale = float(want.abs().max())
         assert float((got - want).abs().max()) <= 2e-6 * max(scale, 1.0)
+    # the dropped product against the host, not against the library: 64 random rows and the two longest, summed in double under the
+    # host's mask (n = 3, the last of the loop)
+    longest = torch.argsort(torch.bincount(coo["rows"], minlength=N), descending=True)[:2]
+    picked = torch.cat([torch.randint(0, N, (64,), generator=torch.Generator().manual_seed(3)).to(dev), longest])
+    rp = torch.searchsorted(coo["rows"], torch.stack([picked, picked + 1]))
+    for r, (lo, hi) in zip(picked.tolist(), rp.T.tolist()):
+        k = keep[lo:hi]
+        row = (coo["vals"][lo:hi][k].double()[:, None] * X[coo["cols"][lo:hi][k]].double()).sum(0)
+        np.testing.assert_allclose(got[r].cpu().numpy(), row.cpu().numpy(), atol=ATOL, rtol=RTOL)
 
 
 def test_dropout_on_the_swept_kernel_and_on_the_transpose():
