@@ -569,6 +569,82 @@ int ngcf_laplacian_drop_zeros(const int64_t *rowptr, const int32_t *colidx, cons
                               int32_t *count, int64_t *out_rowptr, int32_t *out_colidx, float *out_vals, int64_t out_nnz,
                               void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- group-by-sum on packed integer keys, and the decimal string code (csrc/groupby.hip; the reference's pivot_table and
+ * map_ids, utils.py:46-48, 59-97) ----
+ * K <= 8 integer key columns (int32 or int64, length T) and V in 0..4 integer value columns, described by ngcf_groupby_cols_t (a
+ * HOST struct; the kernels take it by value and read the columns themselves - no packed key array of length T exists anywhere).
+ * Column k has an offset (its minimum), a range (maximum - minimum) and a field of key_bits[k] = bit length of the range (0 for a
+ * single-valued column) at key_shift[k]; the fields are concatenated with column 0 most significant and the last column at shift 0,
+ * so the unsigned order of the packed key is the lexicographic order of the columns.  The fields together have at most 63 bits: the
+ * all-ones word means "empty slot".  A shift / bits / range triple that does not fit together is NGCF_ERR_ARG.
+ *   ngcf_groupby_insert   clears the table (table_keys uint64[capacity] to all ones, table_sums int64[V x capacity] to 0, sum v of
+ *        slot s at [v * capacity + s]) and inserts every row: home slot ngcf_groupby_hash(key) & (capacity - 1) - the 64-bit
+ *        finaliser of MurmurHash3 (fmix64) - then linear probing with wrap-around; an empty slot is claimed by a 64-bit
+ *        compare-and-swap at agent scope; the V values are added with int64 integer atomics (associative: the sums do not depend
+ *        on arrival order; they wrap modulo 2^64 as int64 arithmetic does).  capacity is a power of two <= 2^36.  With
+ *        lds_slots != 0 (a power of two in [16, max_lds_slots]) every workgroup first folds its rows - chunks of chunk_rows rows,
+ *        chunk c to workgroup c mod grid - into a table of lds_slots keys and V sums in LDS (slot: bits 32.. of the same hash, at
+ *        most lds_probes probes, 64-bit LDS atomics); a row that finds no place there goes straight to the table in memory, and
+ *        the workgroup's LDS entries are inserted at its end.  The result does not depend on lds_slots.  ngcf_groupby_limits
+ *        reports chunk_rows, lds_probes and max_lds_slots (any pointer may be NULL).
+ *   ngcf_groupby_count    occupied slots per tile, their scan into the workspace, *n_groups (device int64) = G.
+ *   ngcf_groupby_compact  keys[G] (the packed keys, as int64: they are < 2^63) and slots[G], in slot order; the workspace is the
+ *        one ngcf_groupby_count filled.
+ *      (caller: one library sort of the G keys -> sorted_keys, order.)
+ *   ngcf_groupby_unpack   key_out[k][g] = column k of sorted_keys[g] (HOST arrays of K and V device pointers, int64[G] each),
+ *        sum_out[v][g] = table_sums[v * capacity + slots[order[g]]], and, when table_rank (int64[capacity]) is not NULL,
+ *        table_rank[slots[order[g]]] = g: the group's rank in ascending (column 0, column 1, ...) order beside its slot.
+ *   ngcf_groupby_lookup   inverse[t] = table_rank[slot of row t's key], one probe sequence per row: numpy's
+ *        unique(return_inverse=True).  The table is the dictionary; there is no search per row.
+ * status (int32, sticky: bits are OR-ed in; zero it before ngcf_groupby_insert and ngcf_groupby_lookup, whose probe loops give up
+ * once their bit is set):
+ *   NGCF_GROUPBY_FULL   the table cannot hold the groups (run again with a larger capacity: a capacity >= 2 x groups never fails)
+ *   NGCF_GROUPBY_RANGE  a value outside [offset, offset + range] of its column: the row is left out (inverse -1)
+ *   NGCF_GROUPBY_LOST   arrays that do not belong together: a table changed between two calls, an order entry or slot out of range,
+ *                       a row whose key is not in the table (inverse -1).  Nothing is read or written out of bounds.
+ * workspace: ngcf_groupby_workspace_bytes(capacity) bytes, 8-byte aligned (-1 for a capacity that is no power of two <= 2^36).
+ * Argument errors, before any launch (NGCF_ERR_ARG, message "groupby: ..."): a null pointer, a negative T, K or V out of range, a
+ * bad capacity or lds_slots, n_groups outside [0, capacity]; NGCF_ERR_WORKSPACE for a workspace that is too small.
+ *
+ * ngcf_decimal_code: out[t] (int64) = the code of the string made of the decimal strings of row t's n_columns <= 8 columns (HOST
+ * arrays: device pointers, is64 flags, widths), concatenated; widths[k] = 0: the value's natural length, w > 0: zero-padded on the
+ * left to w characters.  Character c is the base-11 digit (c - '0') + 1, and the string is read as a left-aligned number of 18
+ * places with padding 0, so the code's numeric order is the strings' lexicographic order (11^18 < 2^63).  status bits: 1 a
+ * negative value, 2 a value with more digits than its fixed width, 4 more than 18 characters; such a row's code is -1.
+ */
+#define NGCF_GROUPBY_MAX_KEYS 8
+#define NGCF_GROUPBY_MAX_VALUES 4
+#define NGCF_GROUPBY_FULL 1
+#define NGCF_GROUPBY_RANGE 2
+#define NGCF_GROUPBY_LOST 4
+typedef struct ngcf_groupby_cols {
+    int32_t n_keys, n_values;
+    const void *key[NGCF_GROUPBY_MAX_KEYS];        /* device, int32 or int64 [T] */
+    const void *value[NGCF_GROUPBY_MAX_VALUES];    /* device, int32 or int64 [T] */
+    int64_t key_offset[NGCF_GROUPBY_MAX_KEYS];
+    uint64_t key_range[NGCF_GROUPBY_MAX_KEYS];
+    int32_t key_is64[NGCF_GROUPBY_MAX_KEYS];
+    int32_t key_bits[NGCF_GROUPBY_MAX_KEYS];
+    int32_t key_shift[NGCF_GROUPBY_MAX_KEYS];
+    int32_t value_is64[NGCF_GROUPBY_MAX_VALUES];
+} ngcf_groupby_cols_t;
+uint64_t ngcf_groupby_hash(uint64_t packed_key);
+int ngcf_groupby_limits(int *chunk_rows, int *lds_probes, int *max_lds_slots);
+int64_t ngcf_groupby_workspace_bytes(int64_t capacity);
+int ngcf_groupby_insert(const ngcf_groupby_cols_t *cols, int64_t T, uint64_t *table_keys, int64_t *table_sums, int64_t capacity,
+                        int lds_slots, int32_t *status, void *stream);
+int ngcf_groupby_count(const uint64_t *table_keys, int64_t capacity, int64_t *n_groups, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+int ngcf_groupby_compact(const uint64_t *table_keys, int64_t capacity, int64_t n_groups, int64_t *keys, int64_t *slots,
+                         const void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int ngcf_groupby_unpack(const ngcf_groupby_cols_t *cols, const int64_t *sorted_keys, const int64_t *order, const int64_t *slots,
+                        const int64_t *table_sums, int64_t capacity, int64_t n_groups, int64_t *const *key_out, int64_t *const *sum_out,
+                        int64_t *table_rank, int32_t *status, void *stream);
+int ngcf_groupby_lookup(const ngcf_groupby_cols_t *cols, int64_t T, const uint64_t *table_keys, const int64_t *table_rank,
+                        int64_t capacity, int64_t *inverse, int32_t *status, void *stream);
+int ngcf_decimal_code(const void *const *columns, const int32_t *is64, const int32_t *widths, int n_columns, int64_t T, int64_t *out,
+                      int32_t *status, void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

@@ -106,6 +106,15 @@ PROTOTYPES = {
                                       _vp, _vp, _vp]),
     "ngcf_laplacian_item_rows": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ngcf_laplacian_drop_zeros": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "ngcf_groupby_hash": (_u64, [_u64]),
+    "ngcf_groupby_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ngcf_groupby_workspace_bytes": (_i64, [_i64]),
+    "ngcf_groupby_insert": (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp]),
+    "ngcf_groupby_count": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
+    "ngcf_groupby_compact": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ngcf_groupby_unpack": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp]),
+    "ngcf_groupby_lookup": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ngcf_decimal_code": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.c_int, _i64, _vp, _vp, _vp]),
     "ngcf_shard_plan": (C.c_int, [C.POINTER(_i64), _i64, _i64, C.c_int, C.POINTER(_i64)]),
     "ngcf_allgather_rows": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "ngcf_comm_size": (C.c_int, [_vp, C.POINTER(C.c_int)]),

@@ -14,16 +14,25 @@ The reference's other scaler, `args.scaler == 'power'` (sklearn's PowerTransform
 is `fit_power`: lambda by Brent's method on the host, every evaluation of the likelihood one fused pass on the device
 (engine.yeo_johnson_moments), and `scale_implicit(..., scaler=fit_power(visitors))` floors the transformed column.
 
+The head of the chain is here too.  `aggregate_visits` is the pivot of `load_preprocess_data` (utils.py:46-55): the time-zone rows
+of a day folded into one row by a group-by-sum on the device (engine.group_by: the five key columns packed into one word, a hash
+table in memory, integer atomics), the rows sorted by the five keys as pivot_table returns them, plus the derived `year`, `month`,
+`day`.  `map_ids` is utils.py:59-97: `itemid` the rank of `destination` among its sorted distinct values, `userid` the rank of the
+string str(age) + str(sex) + mm + dd among the sorted distinct strings - not the numeric order: age 5 sorts between 45 and 55.  The
+string becomes an integer with the same order (engine.decimal_code: every character a base-11 digit), so the map is one more
+group-by with an inverse, and the reference's dictionaries come out of the few distinct keys on the host (`IdMaps.user_dict`,
+`IdMaps.item_dict`).  `num_dict` is the dictionary of utils.py:152-158.  Reading the CSV stays the caller's.
+
 Not here: the string `scaler='power'` as an alias of that (it stays refused, with a message that says what to pass, until a change
-that may edit the test pinning the refusal), Box-Cox and `inverse_transform`, `load_preprocess_data` and `map_ids` (pandas string
-keys, host work), `split_train_test` (`graphs.holdout_split` exists), and the reference's index-alignment quirk when year-20 rows
-are filtered before the scaler's output is assigned back.
+that may edit the test pinning the refusal), Box-Cox and `inverse_transform`, reading `Datasets_v5.0.txt` (and the reference's
+`.sample(100)` of it), `split_train_test` (`graphs.holdout_split` exists), and the reference's index-alignment quirk when year-20
+rows are filtered before the scaler's output is assigned back (`map_ids` takes the rows the caller kept).
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Optional, Sequence, Tuple, Union
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -263,3 +272,89 @@ def positives(ratings: torch.Tensor) -> torch.Tensor:
     else, floored rows included, as the reference does; `matrix.laplacian_slices` takes the ratings whole, since its rule "an
     explicit 0 removes the edge" is what the floor's zeros mean."""
     return ratings > 0
+
+
+# ---- the head of the chain: raw visit records -> pivoted rows -> user and item ids (utils.py:36-97) ---------------------------------
+@dataclass(frozen=True)
+class VisitTable:
+    """The rows of `load_preprocess_data` as int64 [G] columns on the device, sorted by (date, destination, dayofweek, sex, age):
+    `date` the integer yyyymmdd, `visitor` the sum over the day's time-zone rows, `year` (two digits), `month`, `day` derived."""
+    date: torch.Tensor
+    destination: torch.Tensor
+    dayofweek: torch.Tensor
+    sex: torch.Tensor
+    age: torch.Tensor
+    visitor: torch.Tensor
+    year: torch.Tensor
+    month: torch.Tensor
+    day: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.date.numel())
+
+
+def aggregate_visits(date: torch.Tensor, destination: torch.Tensor, dayofweek: torch.Tensor, sex: torch.Tensor, age: torch.Tensor,
+                     visitor: torch.Tensor, *, lds_slots: Optional[int] = None) -> VisitTable:
+    """`pd.pivot_table(df, index=['date', 'destination', 'dayofweek', 'sex', 'age'], aggfunc={'visitor': 'sum'}).reset_index()` of
+    utils.py:46-48 on the device, with the derived columns of utils.py:51-55.  Six int32 / int64 [T] columns on one device; `date`
+    is the integer yyyymmdd of the CSV (its order is the dates').  `visitor` must be an integer column (TypeError otherwise: see
+    `engine.group_by`).  One `engine.group_by` call; `year`, `month`, `day` are integer torch ops on the G result rows."""
+    g = engine.group_by((date, destination, dayofweek, sex, age), (visitor,), lds_slots=lds_slots)
+    d = g.keys[0]
+    return VisitTable(d, g.keys[1], g.keys[2], g.keys[3], g.keys[4], g.sums[0], (d // 10000) % 100, (d // 100) % 100, d % 100)
+
+
+USER_KEY_WIDTHS = (0, 0, 2, 2)          # str(age) + str(sex) + '%m' + '%d' (utils.py:52-54, 71)
+
+
+@dataclass(frozen=True)
+class IdMaps:
+    """`userid`, `itemid` int64 [T] of `map_ids`, and the distinct keys behind them in id order: `user_codes` int64 [n_user] (the
+    `engine.decimal_code` of the user strings) and `item_keys` int64 [n_item] (destination codes)."""
+    userid: torch.Tensor
+    itemid: torch.Tensor
+    user_codes: torch.Tensor
+    item_keys: torch.Tensor
+
+    @property
+    def n_user(self) -> int:
+        return int(self.user_codes.numel())
+
+    @property
+    def n_item(self) -> int:
+        return int(self.item_keys.numel())
+
+    def user_dict(self) -> Dict[str, int]:
+        """The reference's `user_dict` (utils.py:72): the user string -> id.  Host work on the n_user distinct keys."""
+        return {engine.decimal_string(c): i for i, c in enumerate(self.user_codes.tolist())}
+
+    def item_dict(self) -> Dict[int, int]:
+        """The reference's `item_dict` (utils.py:73): destination code -> id."""
+        return {int(d): i for i, d in enumerate(self.item_keys.tolist())}
+
+
+def map_ids(age: torch.Tensor, sex: torch.Tensor, month: torch.Tensor, day: torch.Tensor, destination: torch.Tensor, *,
+            lds_slots: Optional[int] = None) -> IdMaps:
+    """`Preprocess.map_ids` (utils.py:59-97) for five int32 / int64 [T] columns on one device: `itemid[t]` is the rank of
+    `destination[t]` among the sorted distinct destinations, `userid[t]` the rank of str(age) + str(sex) + '%02d' % month +
+    '%02d' % day among the sorted distinct strings (numpy's string sort: character by character).  The `year != 20` filter of
+    utils.py:66 is the caller's boolean index before the call.  A negative value, or a month or day of more than two digits:
+    ValueError."""
+    code = engine.decimal_code((age, sex, month, day), USER_KEY_WIDTHS)
+    users = engine.group_by((code,), inverse=True, lds_slots=lds_slots)
+    items = engine.group_by((destination,), inverse=True, lds_slots=lds_slots)
+    return IdMaps(users.inverse, items.inverse, users.keys[0], items.keys[0])
+
+
+def num_dict(ids: IdMaps, sex: torch.Tensor, age: torch.Tensor, month: torch.Tensor, day: torch.Tensor,
+             dayofweek: torch.Tensor) -> Dict[str, int]:
+    """The `num_dict` of utils.py:152-158 as Python ints: the numbers of distinct users and items, and maximum + 1 of the five
+    feature columns (one read-back of the five maxima)."""
+    cols = (sex, age, month, day, dayofweek)
+    for c, nm in zip(cols, ("sex", "age", "month", "day", "dayofweek")):
+        engine._require_device(c, nm)
+        if c.dim() != 1 or c.numel() == 0:
+            raise ValueError(f"num_dict: {nm} must be a non-empty [T] column, got {tuple(c.shape)}")
+    top = torch.stack([c.max().to(torch.int64) for c in cols]).tolist()
+    return {"user": ids.n_user, "item": ids.n_item, "sex": top[0] + 1, "age": top[1] + 1, "month": top[2] + 1, "day": top[3] + 1,
+            "dayofweek": top[4] + 1}
