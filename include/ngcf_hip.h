@@ -645,6 +645,41 @@ int ngcf_groupby_lookup(const ngcf_groupby_cols_t *cols, int64_t T, const uint64
 int ngcf_decimal_code(const void *const *columns, const int32_t *is64, const int32_t *widths, int n_columns, int64_t T, int64_t *out,
                       int32_t *status, void *stream);
 
+/* ---- exact per-group sampling (csrc/select.hip; the reference's Preprocess.split_train_test, utils.py:126-148) ----
+ * From every group g of the T rows exactly quota[g] rows are marked, uniformly among all subsets of that size: pandas'
+ * `sample(frac=, replace=False)` of a part of a frame (one group) and the per-class draws of sklearn's stratified split (one group
+ * per class) - the reference's distribution, not numpy's stream.  Row t belongs to group group[t] (int32 [T], ids in [0, G); group ==
+ * NULL: all rows in group 0, G must be 1); the groups need not be contiguous.  All arithmetic unsigned 64-bit:
+ *   fmix(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33      (as for ngcf_sample_unseen)
+ *   k_t   = fmix(seed ^ (t * 0x9E3779B97F4A7C15))                                            (ngcf_select_key, a host call)
+ *   tau_g = the quota[g]-th smallest k_t among the rows of group g                            (quota[g] > 0)
+ *   mask[t] = quota[g] > 0 && k_t <= tau_g                                                    (uint8: 0 or 1)
+ * Multiplying by an odd constant, xor with a constant and fmix are bijections on 64-bit words: the keys of distinct rows are
+ * distinct, exactly quota[g] rows of group g qualify, and there is no tie to break.  Equal (seed, group, quota) give equal masks on
+ * every run: the keys are recomputed from t in each pass and never stored, and the only atomics are integer counts.
+ * tau is found by a radix select: eight passes from the most significant byte; in a pass every row whose key agrees with its
+ * group's prefix so far counts into hist[g][next byte], and per group the bin that holds the remaining rank extends the prefix.
+ * Up to lds_groups groups (ngcf_select_limits: the 160 KiB of a CU's LDS / 1 KiB per group) the G x 256 int32 table is kept in each
+ * workgroup's LDS and flushed once per pass; above, the rows add straight into the table in memory.  The mask does not depend on the
+ * tier (option "select_no_lds": the memory tier at every G; tests and tools).
+ * thresholds (may be NULL): uint64 [G], tau_g, or 0 for a group with nothing marked.  quota: DEVICE int64 [G]; a quota <= 0 marks
+ * nothing.  *status is OR-ed into, never cleared - zero it before the call, the marking pass looks at it:
+ *   NGCF_SELECT_GROUP  a group id outside [0, G): the row counts nowhere, and the call marks no row at all
+ *   NGCF_SELECT_QUOTA  quota[g] above the row count of group g (pandas and numpy raise there): no row of that group is marked
+ *   NGCF_SELECT_LOST   the rows changed between two passes; nothing is read or written out of bounds
+ * workspace: 16-byte aligned, workspace_bytes of ngcf_select_limits(G) - the G x 256 int32 table and 16 bytes of state per group,
+ * 1 KiB + 16 B per group in both tiers (-1 for a G outside [1, 2^31)).  Argument errors, before any launch (NGCF_ERR_ARG, message
+ * "select: ..."): T outside [0, 2^31) (the bins are int32), G outside [1, 2^31), group == NULL with G != 1 and T > 0, a null pointer (mask
+ * may be NULL when T == 0), a misaligned workspace; NGCF_ERR_WORKSPACE for one that is too small.  T == 0 is not an error: a positive quota
+ * then sets NGCF_SELECT_QUOTA. */
+#define NGCF_SELECT_GROUP 1
+#define NGCF_SELECT_QUOTA 2
+#define NGCF_SELECT_LOST 4
+int ngcf_select_limits(int64_t G, int *lds_groups, int64_t *workspace_bytes);
+uint64_t ngcf_select_key(uint64_t seed, int64_t t);
+int ngcf_select_per_group(const int32_t *group, int64_t T, int64_t G, const int64_t *quota, uint64_t seed, uint8_t *mask,
+                          uint64_t *thresholds, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

@@ -70,6 +70,8 @@ struct NgcfOptions {
     // spmm_t_rows.hip, bwd_dense.hip
     int t_rows_bitmap = 1;         // NGCF_T_ROWS_BITMAP: 0 keeps the row-sparse transposed product on the slot-table kernel at every size
     int bwd_input_resident = 1;    // NGCF_BWD_INPUT_RESIDENT: 0 keeps the staged input-gradient kernel at every size
+    // select.hip
+    int select_no_lds = 0;         // NGCF_SELECT_NO_LDS: the per-group select counts in memory at every group count
     // csr.hip
     int slice_max_mb = 48;         // NGCF_SLICE_MAX_MB: largest table slice a d-sliced group may gather from
     // spmm_swept.hip (plan)

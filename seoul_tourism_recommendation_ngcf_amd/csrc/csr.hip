@@ -41,6 +41,7 @@ const OptField kOptFields[] = {
     {"dense_tall", &NgcfOptions::dense_tall, nullptr},
     {"bwd_input_resident", &NgcfOptions::bwd_input_resident, nullptr},
     {"t_rows_bitmap", &NgcfOptions::t_rows_bitmap, nullptr},
+    {"select_no_lds", &NgcfOptions::select_no_lds, nullptr},
     {"slice_max_mb", &NgcfOptions::slice_max_mb, nullptr},
     {"swept_lpe", &NgcfOptions::swept_lpe, nullptr},
     {"swept_cut", &NgcfOptions::swept_cut, nullptr},

@@ -6,9 +6,16 @@ items, and a masked write that sets every rating below that quartile to 0 - O(us
 own rows, so here one call (engine.segment_quantile_floor) does every user at once, with the same fp64 operations in the same
 order: given the same (mean, scale, shift) the ratings are bit-equal to the reference's, up to the sign of a zero.
 
-With it the chain runs on one device with no host loop: counts -> `scale_implicit` -> `matrix.laplacian_csr_slices` (HIP kernels;
-`matrix.laplacian_slices` is the same in torch ops, and its oracle) / `positives` -> `sampling.train_triplets` -> training step ->
-`evaluate.candidate_ranking` -> `recommend.blended_ranking`.
+With it the chain runs on one device with no host loop: counts -> `scale_implicit` -> `split_by_year` / `split_stratified` ->
+`matrix.laplacian_csr_slices` (HIP kernels; `matrix.laplacian_slices` is the same in torch ops, and its oracle) / `positives` ->
+`sampling.train_triplets` / `sampling.test_candidates` -> training step -> `evaluate.candidate_ranking` ->
+`recommend.blended_ranking`.
+
+The split is `Preprocess.split_train_test` (utils.py:126-148), both of its protocols: `split_by_year` is the year hold-out that
+main.py runs (all of year 18 and the unsampled 70 % of year 19 train, a uniform 30 % sample of year 19 tests), `split_stratified`
+sklearn's `train_test_split(test_size=0.3, stratify=destination)` with the per-class counts of `stratified_counts`.  Both are one
+`engine.select_per_group` call - from every group of rows exactly its quota, uniformly - and reproduce the reference's distribution,
+not numpy's or pandas' random stream.
 
 The reference's other scaler, `args.scaler == 'power'` (sklearn's PowerTransformer(): Yeo-Johnson, then the same standardisation),
 is `fit_power`: lambda by Brent's method on the host, every evaluation of the likelihood one fused pass on the device
@@ -25,8 +32,9 @@ group-by with an inverse, and the reference's dictionaries come out of the few d
 
 Not here: the string `scaler='power'` as an alias of that (it stays refused, with a message that says what to pass, until a change
 that may edit the test pinning the refusal), Box-Cox and `inverse_transform`, reading `Datasets_v5.0.txt` (and the reference's
-`.sample(100)` of it), `split_train_test` (`graphs.holdout_split` exists), and the reference's index-alignment quirk when year-20
-rows are filtered before the scaler's output is assigned back (`map_ids` takes the rows the caller kept).
+`.sample(100)` of it), the permuted row order in which the reference's split returns its parts (see `split_by_year`), and the
+reference's index-alignment quirk when year-20 rows are filtered before the scaler's output is assigned back (`map_ids` takes the
+rows the caller kept).  (`graphs.holdout_split` is another thing: a per-user leave-some-out split of the synthetic graphs.)
 """
 from __future__ import annotations
 
@@ -34,9 +42,11 @@ import math
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from . import engine
+from .sampling import fmix
 
 
 def _pairwise_sum(v: torch.Tensor) -> torch.Tensor:
@@ -358,3 +368,119 @@ def num_dict(ids: IdMaps, sex: torch.Tensor, age: torch.Tensor, month: torch.Ten
     top = torch.stack([c.max().to(torch.int64) for c in cols]).tolist()
     return {"user": ids.n_user, "item": ids.n_item, "sex": top[0] + 1, "age": top[1] + 1, "month": top[2] + 1, "day": top[3] + 1,
             "dayofweek": top[4] + 1}
+
+
+# ---- the split: Preprocess.split_train_test (utils.py:126-148) ------------------------------------------------------------------------
+def _approximate_mode(counts: np.ndarray, n_draws: int, seed: int):
+    """sklearn's `_approximate_mode` restated: the most likely outcome of drawing `n_draws` rows from classes of `counts` rows, in
+    fp64 as sklearn computes it - `counts / counts.sum() * n_draws` floored, then one more row to the classes with the largest
+    remainders until `n_draws` are placed.  Where some but not all classes of one remainder get a row sklearn draws them from its
+    random state; here they are taken in ascending order of fmix(seed ^ class).  Returns `(drawn int64 [C], cut)`: `cut` says that
+    such a tie was cut (without one the result is sklearn's for every random state)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    continuous = counts / counts.sum() * n_draws
+    floored = np.floor(continuous)
+    need = int(n_draws - floored.sum())
+    cut = False
+    if need > 0:
+        remainder = continuous - floored
+        for value in np.sort(np.unique(remainder))[::-1]:
+            inds, = np.where(remainder == value)
+            add_now = min(len(inds), need)
+            if add_now < len(inds):
+                cut = True
+                inds = np.array(sorted(inds.tolist(), key=lambda c: fmix((int(seed) & (2 ** 64 - 1)) ^ c))[:add_now], dtype=np.int64)
+            floored[inds] += 1
+            need -= add_now
+            if need == 0:
+                break
+    return floored.astype(np.int64), cut
+
+
+def stratified_counts(counts, test_size: float = 0.3, *, seed: int = 0):
+    """`(train_counts, test_counts)`, int64 numpy [C]: how many rows of every class sklearn's `train_test_split(test_size=,
+    stratify=)` puts into each part, from the class sizes `counts` alone (host, fp64).  n_test = ceil(test_size * n) and n_train =
+    n - n_test - sklearn's rule when no train size is given, floor((1 - test_size) * n) in exact arithmetic; `_approximate_mode` of
+    `counts` with n_train, then of what is left with n_test.  The one place where sklearn uses its random state for a count is a
+    tie: when some but not all classes of equal remainder receive a row, the classes are taken in ascending order of
+    fmix(seed ^ class) (class = the position in `counts`; fmix as in `sampling`) instead - class totals like the ones in the tests
+    cut no tie and give sklearn's counts for every random state.  ValueError, as sklearn raises: a `test_size` outside (0, 1), a
+    class of fewer than 2 rows, fewer train or test rows than classes."""
+    c = np.asarray(counts)
+    if c.ndim != 1 or c.size < 1 or c.dtype.kind not in "iu":
+        raise ValueError(f"stratified_counts: counts must be a non-empty 1-D integer array, got shape {c.shape} of {c.dtype}")
+    c = c.astype(np.int64)
+    test_size = float(test_size)
+    if not 0.0 < test_size < 1.0:
+        raise ValueError(f"stratified_counts: test_size={test_size} should be a float in the (0, 1) range")
+    if int(c.min()) < 2:
+        raise ValueError("stratified_counts: the least populated class has fewer than 2 rows, which is too few")
+    n, n_classes = int(c.sum()), int(c.size)
+    n_test = int(math.ceil(test_size * n))
+    n_train = n - n_test
+    if n_train < n_classes:
+        raise ValueError(f"stratified_counts: the train size {n_train} should be at least the number of classes {n_classes}")
+    if n_test < n_classes:
+        raise ValueError(f"stratified_counts: the test size {n_test} should be at least the number of classes {n_classes}")
+    train, _ = _approximate_mode(c, n_train, seed)
+    test, _ = _approximate_mode(c - train, n_test, seed)
+    return train, test
+
+
+def split_stratified(strata: torch.Tensor, *, test_size: float = 0.3, seed: int):
+    """The reference's `train_by_destination=True` split, `train_test_split(total_df, test_size=0.3, stratify=destination)`:
+    `strata` (int32 / int64 [T] on the device, non-negative class ids, e.g. `itemid`) -> `(train_idx, test_idx)`, int64 row indices
+    in ascending order.  `torch.bincount` and one read-back give the class sizes, `stratified_counts` over the classes that occur
+    (in id order, as sklearn numbers them) the test count of every class, one `engine.select_per_group` call the rows: within a class
+    every subset of that size is equally likely.  Every row goes to one of the two parts.  Deviation: sklearn returns both parts in
+    permuted order; the reference's train loader shuffles anyway, and its test loader does not, so only the batching of the test
+    cases differs.  ValueError as `stratified_counts` raises it."""
+    if strata.dim() != 1:
+        raise ValueError(f"split_stratified: strata must be [T], got {tuple(strata.shape)}")
+    if strata.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"split_stratified: strata must be int32 or int64, got {strata.dtype}")
+    test_size = float(test_size)
+    if not 0.0 < test_size < 1.0:
+        raise ValueError(f"split_stratified: test_size={test_size} should be a float in the (0, 1) range")
+    engine._require_device(strata, "strata")
+    if strata.numel() == 0:
+        raise ValueError("split_stratified: no rows to split")
+    sizes = torch.bincount(strata).cpu().numpy().astype(np.int64)          # the read-back: G counts (a negative id: torch raises)
+    if sizes.size >= 2 ** 31:
+        raise ValueError(f"split_stratified: class ids up to {sizes.size - 1}, beyond int32")
+    present = np.flatnonzero(sizes)
+    _, test = stratified_counts(sizes[present], test_size, seed=seed)
+    quota = np.zeros(sizes.size, dtype=np.int64)
+    quota[present] = test
+    mask = engine.select_per_group(strata.to(torch.int32), quota, seed=seed)
+    return torch.nonzero(mask == 0).view(-1), torch.nonzero(mask).view(-1)
+
+
+def split_by_year(year: torch.Tensor, *, train_year: int = 18, test_year: int = 19, frac: float = 0.3, seed: int):
+    """The reference's year hold-out (utils.py:133-139, 147-148; what main.py runs): `year` (int32 / int64 [T] on the device) ->
+    `(train_idx, test_idx)`, int64 row indices.  Test: a uniform sample without replacement of round(frac * n) of the n rows of
+    `test_year` - Python's round, half to even, which is pandas' `sample(frac=)` rule - in row order.  Train: all rows of
+    `train_year` in row order, then the unsampled rows of `test_year` in row order, the order of the reference's `concat`.  Rows of
+    other years are in neither part.  One read-back of n, one `engine.select_per_group` call (the test year is group 0, everything
+    else a group with quota 0).  Deviation: the reference's sample comes in permuted order; its train loader shuffles anyway, and
+    its test loader does not, so only the batching of the test cases differs."""
+    if year.dim() != 1:
+        raise ValueError(f"split_by_year: year must be [T], got {tuple(year.shape)}")
+    if year.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"split_by_year: year must be int32 or int64, got {year.dtype}")
+    train_year, test_year, frac = int(train_year), int(test_year), float(frac)
+    if train_year == test_year:
+        raise ValueError(f"split_by_year: train_year and test_year are both {train_year}")
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError(f"split_by_year: frac={frac} outside [0, 1]")
+    engine._require_device(year, "year")
+    held = year == test_year
+    quota = year_quota(int(held.sum().item()), frac)                        # the read-back: n
+    mask = engine.select_per_group((~held).to(torch.int32), [quota, 0], seed=seed).bool()
+    train = torch.cat([torch.nonzero(year == train_year).view(-1), torch.nonzero(held & ~mask).view(-1)])
+    return train, torch.nonzero(mask).view(-1)
+
+
+def year_quota(n: int, frac: float = 0.3) -> int:
+    """round(frac * n), half to even: the number of rows pandas' `sample(frac=)` takes from n."""
+    return int(round(float(frac) * int(n)))
