@@ -29,7 +29,7 @@ Transport (`NGCF_DIST_COLLECTIVES`): "p2p" (default on device tensors) - the CU-
 copies on copy-engine streams, host threads wait on shared sequence words), which leaves every CU to the L2-swept SpMM;
 "torch" - torch.distributed collectives (RCCL under "nccl"); "cabi" - `ngcf_allgather_rows` on the group's communicator.
 
-Compute is always the HIP engine (`engine.py`); nothing here has a CPU path.  The layout/exchange helpers
+Compute is always the HIP engine (the `engine` package); nothing here has a CPU path.  The layout/exchange helpers
 are backend-agnostic tensor plumbing, which is what the world_size-2 `gloo` tests exercise on CPU tensors.
 """
 from __future__ import annotations
@@ -391,13 +391,6 @@ class _SumGrads(torch.autograd.Function):
         return (None, None, *out)
 
 
-class _DevMem:
-    """`__cuda_array_interface__` carrier: a torch tensor over device memory the library allocated (the exchange buffer)."""
-
-    def __init__(self, ptr: int, n_floats: int):
-        self.__cuda_array_interface__ = {"data": (int(ptr), False), "shape": (int(n_floats),), "typestr": "<f4", "version": 2}
-
-
 class P2PExchange:
     """The CU-free exchange of include/ngcf_hip.h (`ngcf_p2p_*`): one exchange buffer per rank, peers pull from it with
     device-to-device copies on copy-engine streams, host threads do the waiting.  All ranks of `group` must live on one node
@@ -442,7 +435,7 @@ class P2PExchange:
             self.close_quietly()
             raise RuntimeError("p2p exchange could not be set up: " + "; ".join(errs))
         self.base = int(lib.ngcf_p2p_local(self._h))
-        self._mem = torch.as_tensor(_DevMem(self.base, max(self.n_floats, 64)), device=self.dev)
+        self._mem = _eng._device_view(self.base, max(self.n_floats, 64), torch.float32, self.dev)   # the exchange buffer
         assert self._mem.data_ptr() == self.base and self._mem.dtype == torch.float32
         self.seq = {}                      # slot -> last published / expected step
 
