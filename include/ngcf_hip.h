@@ -206,6 +206,13 @@ int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *E_self, int
                          const float *drop_mask, int64_t ld_mask,
                          float *carry, int64_t ldc, float *norm, int64_t ldn,
                          void *workspace, int64_t workspace_bytes, void *stream);
+/* Which forward kernel ngcf_layer_dense_f32 would launch for these sizes and operands under the current options: a read-only
+ * query answered by the host function the entry point itself dispatches through (nothing is launched, LE / E_self are not
+ * dereferenced - only their alignment counts).  A short static name: "staged<RW,CW,NT>/padded", ".../aligned" or ".../unaligned"
+ * (the tile configuration of layer_dense_kernel and its row layout: 16-byte aligned rows padded to a multiple of 4 floats,
+ * aligned rows of fewer than 4 columns, anything else), "direct<2,4>", "direct<4,4>", "tall256", "tall512", "resident" or
+ * "split".  NULL (and ngcf_last_error) for sizes ngcf_layer_dense_f32 rejects.  For tests and tools. */
+const char *ngcf_dense_path(int64_t n_rows, int d_in, int d_out, const float *LE, int64_t ldLE, const float *E_self, int64_t ldEs);
 
 /* dst[r, 0:d] = src[r, 0:d] for r < n_rows (strided copy; writes E0 into its block of all_E,
  * NGCF.py:120-121 + 147). */

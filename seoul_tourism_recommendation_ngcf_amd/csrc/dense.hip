@@ -1251,38 +1251,33 @@ static void launch_staged(const DenseCall &k, bool al, bool padded, const float 
     else k.launch(layer_dense_kernel<RW, CW, NT, false, false>, blocks, 256, 0, Wt, bias2, n_chunks);
 }
 
-extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *Es, int64_t ldEs, int64_t n_rows,
-                                    int d_in, const float *W1, const float *b1, const float *W2, const float *b2,
-                                    int d_out, float leaky, float drop_p, uint64_t drop_seed, const float *drop_mask,
-                                    int64_t ld_mask, float *carry, int64_t ldc, float *norm, int64_t ldn, void *workspace,
-                                    int64_t workspace_bytes, void *stream_)
+// Which forward kernel a call takes.  Every decision of the dispatch is made HERE, once: ngcf_layer_dense_f32 launches what this
+// returns and ngcf_dense_path reports its name, so a test that names a kernel fails when the dispatch stops sending it there.
+// Pure host code: the sizes, the alignment of the operands and the options (ngcf_opts()), nothing else.  d_out <= 512 (dop > 0).
+enum DenseKernel { kDenseTall, kDenseSplit, kDenseResident, kDenseDirect, kDenseStaged };
+struct DensePath {
+    DenseKernel kernel;
+    int dop;               // packed output columns: 32, 64, 96, 128, 256 or 512 (128 where small_rows)
+    bool small_rows;       // up to 128 output columns on at most 16 384 rows: 32-row x 128-column tiles
+    bool al;               // 16-byte aligned rows: ALIGNED of the staged kernel
+    bool padded;           // and padded to a multiple of 4 floats: FAST of the staged kernel, and what every other kernel reads
+    int tile;              // staged only: 0 = <1,4,1>, 1..4 = <4,1,1..4>, 5 = <2,2,4>, 6 = <1,4,4>
+    const char *name;
+};
+static DensePath dense_path(int64_t n_rows, int d_in, int d_out, const float *LE, int64_t ldLE, const float *Es, int64_t ldEs)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!LE || !Es || !W1 || !b1 || !W2 || !b2 || !norm) return fail(NGCF_ERR_ARG, "layer_dense: null argument");
-    if (n_rows < 0 || d_in <= 0 || d_out <= 0) return fail(NGCF_ERR_ARG, "layer_dense: bad sizes");
-    int dop = dense_dop(d_out);
-    if (dop < 0) return fail(NGCF_ERR_ARG, "layer_dense: d_out=%d > 512 is not supported", d_out);
+    DensePath p{};
+    p.dop = dense_dop(d_out);
     // Up to 128 output columns on a SMALL matrix (the Seoul graph: 5 940 rows): 128-row tiles are 47 workgroups on 256 CUs and the
     // 65 -> 65 layer of the reference's own configuration took 28-30 us; 32-row x 128-column tiles (four waves side by side, one
     // tile each) are 186 workgroups.  From 16 384 rows on (128 tiles of 128 rows) the tall tiles stay.
-    const bool small_rows = dop <= 128 && n_rows <= 16384 && ngcf_opts().dense_small_tiles;
-    if (small_rows) dop = 128;
-    if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(NGCF_ERR_ARG, "layer_dense: drop_p=%f not in [0,1)", drop_p);
-    if (ldLE < d_in || ldEs < d_in || ldn < d_out || (carry && ldc < d_out) || (drop_mask && ld_mask < d_out))
-        return fail(NGCF_ERR_ARG, "layer_dense: leading dimension too small");
-    const int64_t need = ngcf_dense_workspace_bytes(d_in, d_out);
-    if (!workspace || workspace_bytes < need)
-        return fail(NGCF_ERR_WORKSPACE, "layer_dense: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
-    // Nothing to compute, and no kernel may run: the persistent kernels' row_of() would clamp to row -1 (dense_resident_min_rows
-    // can be set to 0 or below).
-    if (n_rows == 0) return NGCF_OK;
-    const int n_chunks = (d_in + NGCF_DC - 1) / NGCF_DC;
-    float *Wt = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
-    float *bias2 = Wt + (int64_t)n_chunks * NGCF_KC * dop;
-    const bool al = (ldLE % 4 == 0) && (ldEs % 4 == 0) && aligned16(LE) && aligned16(Es);
+    p.small_rows = p.dop <= 128 && n_rows <= 16384 && ngcf_opts().dense_small_tiles;
+    if (p.small_rows) p.dop = 128;
+    const int dop = p.dop;
+    p.al = (ldLE % 4 == 0) && (ldEs % 4 == 0) && aligned16(LE) && aligned16(Es);
     // 16-byte aligned rows padded to a multiple of 4 floats: what the tall, resident, split and direct kernels read
-    const bool padded = al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4;
-    const DenseCall call{LE, ldLE, Es, ldEs, n_rows, d_in, d_out, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream};
+    p.padded = p.al && ldLE >= align_up(d_in, 4) && ldEs >= align_up(d_in, 4) && d_in >= 4;
+    const int n_chunks = (d_in + NGCF_DC - 1) / NGCF_DC;
 
     // 256 / 512 output columns as 96-row x 128-column workgroups, three row tiles per wave, the row norm in a second kernel
     // (layer_dense_tall_kernel): 248 workgroups for the Seoul graph's 5 940 rows where the direct kernel has 186.  Measured
@@ -1293,7 +1288,86 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     // dense_tall = 0: never; 2: wherever the shape allows; 1: by these numbers.
     const int tall_env = ngcf_opts().dense_tall;
     const bool tall_pays = dop == 512 ? (n_rows <= 6144 || n_rows > 8192) : (n_rows > 8192 && n_rows <= 131072);
-    if (tall_env && dop >= 256 && padded && (tall_pays || tall_env == 2)) {
+    if (tall_env && dop >= 256 && p.padded && (tall_pays || tall_env == 2)) {
+        p.kernel = kDenseTall;
+        p.name = dop == 256 ? "tall256" : "tall512";
+        return p;
+    }
+
+    // Weights resident in LDS, no barriers: large row counts at the 128-wide shapes, from two tiles per wave on.  dense_resident
+    // = 4: the bf16 three-way split (layer_dense_split_kernel); 1 (any other non-zero value): the fp32 layer_dense_resident_kernel
+    // (128 -> 128, resident / staged us: 65 536 rows 59 / 59, 98 304 rows 95 / 85, 131 072 rows 96 / 104, 262 144 rows 184 / 212,
+    // C3's 1.1 M rows 633 / 780); 0: the staged kernel.
+    const int resident = ngcf_opts().dense_resident;
+    const int64_t lds_bytes = (int64_t)n_chunks * NGCF_KC * 128 * (int64_t)sizeof(float);
+    const bool resident_fits = resident && dop == 128 && p.padded && lds_bytes <= 150 * 1024 &&
+                               n_rows >= (int64_t)ngcf_opts().dense_resident_min_rows;
+    if (resident_fits) {
+        p.kernel = resident == 4 ? kDenseSplit : kDenseResident;
+        p.name = resident == 4 ? "split" : "resident";
+        return p;
+    }
+
+    // 256 / 512 output columns and at most ONE workgroup per CU (<= 8 192 rows - the Seoul graph has 5 940): operands straight
+    // from global memory / L2, no staging (layer_dense_direct_kernel).  tools/dense_wide_lab.py: 94 vs 114 us at 5 940 x 515 -> 512,
+    // 50 vs 57 us at 256 -> 256, 97 vs 117 us at 8 192 x 512 -> 512; as soon as a CU gets a second workgroup the staged kernel
+    // (two workgroups share a CU's LDS and matrix pipe; the direct kernel runs one wave per SIMD) wins clearly: 170 vs 277 us at
+    // 12 288 rows, 1.08 vs 1.40 ms at 100 K.  NGCF_DENSE_DIRECT=0 / 2: never / at any row count.
+    const int direct_env = ngcf_opts().dense_direct;
+    if (direct_env && dop >= 256 && p.padded && (n_rows <= 8192 || direct_env == 2)) {
+        p.kernel = kDenseDirect;
+        p.name = dop == 256 ? "direct<2,4>" : "direct<4,4>";
+        return p;
+    }
+
+    // the staged kernel (layer_dense_kernel): the tile configuration by width, the row layout by alignment
+#define NGCF_STAGED_NAMES(cfg) {"staged" cfg "/unaligned", "staged" cfg "/aligned", "staged" cfg "/padded"}
+    static const char *const names[7][3] = {NGCF_STAGED_NAMES("<1,4,1>"), NGCF_STAGED_NAMES("<4,1,1>"), NGCF_STAGED_NAMES("<4,1,2>"),
+                                            NGCF_STAGED_NAMES("<4,1,3>"), NGCF_STAGED_NAMES("<4,1,4>"), NGCF_STAGED_NAMES("<2,2,4>"),
+                                            NGCF_STAGED_NAMES("<1,4,4>")};
+#undef NGCF_STAGED_NAMES
+    p.kernel = kDenseStaged;
+    p.tile = p.small_rows ? 0 : dop <= 128 ? dop / 32 : dop == 256 ? 5 : 6;
+    p.name = names[p.tile][p.padded ? 2 : p.al ? 1 : 0];
+    return p;
+}
+
+extern "C" const char *ngcf_dense_path(int64_t n_rows, int d_in, int d_out, const float *LE, int64_t ldLE, const float *Es, int64_t ldEs)
+{
+    if (n_rows < 0 || d_in <= 0 || d_out <= 0 || dense_dop(d_out) < 0 || ldLE < d_in || ldEs < d_in) {
+        fail(NGCF_ERR_ARG, "dense_path: bad sizes");
+        return nullptr;
+    }
+    return dense_path(n_rows, d_in, d_out, LE, ldLE, Es, ldEs).name;
+}
+
+extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *Es, int64_t ldEs, int64_t n_rows,
+                                    int d_in, const float *W1, const float *b1, const float *W2, const float *b2,
+                                    int d_out, float leaky, float drop_p, uint64_t drop_seed, const float *drop_mask,
+                                    int64_t ld_mask, float *carry, int64_t ldc, float *norm, int64_t ldn, void *workspace,
+                                    int64_t workspace_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!LE || !Es || !W1 || !b1 || !W2 || !b2 || !norm) return fail(NGCF_ERR_ARG, "layer_dense: null argument");
+    if (n_rows < 0 || d_in <= 0 || d_out <= 0) return fail(NGCF_ERR_ARG, "layer_dense: bad sizes");
+    if (dense_dop(d_out) < 0) return fail(NGCF_ERR_ARG, "layer_dense: d_out=%d > 512 is not supported", d_out);
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(NGCF_ERR_ARG, "layer_dense: drop_p=%f not in [0,1)", drop_p);
+    if (ldLE < d_in || ldEs < d_in || ldn < d_out || (carry && ldc < d_out) || (drop_mask && ld_mask < d_out))
+        return fail(NGCF_ERR_ARG, "layer_dense: leading dimension too small");
+    const int64_t need = ngcf_dense_workspace_bytes(d_in, d_out);
+    if (!workspace || workspace_bytes < need)
+        return fail(NGCF_ERR_WORKSPACE, "layer_dense: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
+    // Nothing to compute, and no kernel may run: the persistent kernels' row_of() would clamp to row -1 (dense_resident_min_rows
+    // can be set to 0 or below).
+    if (n_rows == 0) return NGCF_OK;
+    const DensePath path = dense_path(n_rows, d_in, d_out, LE, ldLE, Es, ldEs);   // every decision: see there
+    const int dop = path.dop;
+    const int n_chunks = (d_in + NGCF_DC - 1) / NGCF_DC;
+    float *Wt = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
+    float *bias2 = Wt + (int64_t)n_chunks * NGCF_KC * dop;
+    const DenseCall call{LE, ldLE, Es, ldEs, n_rows, d_in, d_out, leaky, drop_p, drop_seed, drop_mask, ld_mask, carry, ldc, norm, ldn, stream};
+
+    if (path.kernel == kDenseTall) {
         const int n_ct = dop / 32;
         pack_weights_tall_kernel<<<dim3((unsigned)(n_chunks * n_ct)), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, dop, Wt, bias2);
         LAUNCH_CHECK();
@@ -1306,20 +1380,13 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         return NGCF_OK;
     }
 
-    // Weights resident in LDS, no barriers: large row counts at the 128-wide shapes, from two tiles per wave on.  dense_resident
-    // = 4: the bf16 three-way split (layer_dense_split_kernel); 1 (any other non-zero value): the fp32 layer_dense_resident_kernel
-    // (128 -> 128, resident / staged us: 65 536 rows 59 / 59, 98 304 rows 95 / 85, 131 072 rows 96 / 104, 262 144 rows 184 / 212,
-    // C3's 1.1 M rows 633 / 780); 0: the staged kernel.
-    const int resident = ngcf_opts().dense_resident;
     const int64_t lds_bytes = (int64_t)n_chunks * NGCF_KC * 128 * (int64_t)sizeof(float);
-    const bool resident_fits = resident && dop == 128 && padded && lds_bytes <= 150 * 1024 &&
-                               n_rows >= (int64_t)ngcf_opts().dense_resident_min_rows;
     auto pack_fp32 = [&](int nt) {  // the fp32 kernels' packed weights, nt tiles per wave (the split kernel packs its own)
         pack_weights_kernel<<<dim3((unsigned)(n_chunks * (dop / 32))), 256, 0, stream>>>(W1, b1, W2, b2, d_in, d_out, n_chunks, dop,
                                                                                         nt, Wt, bias2);
         return hipGetLastError();
     };
-    if (resident_fits && resident == 4) {
+    if (path.kernel == kDenseSplit) {
         // bias at the start of the workspace, then parts h + m of every chunk (the LDS image), then part l
         HIP_TRY(allow_full_lds<layer_dense_split_kernel>());
         float *sbias = Wt;
@@ -1332,7 +1399,7 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         LAUNCH_CHECK();
         return NGCF_OK;
     }
-    if (resident_fits) {
+    if (path.kernel == kDenseResident) {
         // four column tiles per lane, also where small_rows picked 32-row tiles for the staged kernel (a dense_resident_min_rows
         // at or below 16 384 rows)
         HIP_TRY(pack_fp32(4));
@@ -1342,14 +1409,8 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
         return NGCF_OK;
     }
 
-    HIP_TRY(pack_fp32(small_rows ? 1 : dop <= 128 ? dop / 32 : 4));
-    // 256 / 512 output columns and at most ONE workgroup per CU (<= 8 192 rows - the Seoul graph has 5 940): operands straight
-    // from global memory / L2, no staging (layer_dense_direct_kernel).  tools/dense_wide_lab.py: 94 vs 114 us at 5 940 x 515 -> 512,
-    // 50 vs 57 us at 256 -> 256, 97 vs 117 us at 8 192 x 512 -> 512; as soon as a CU gets a second workgroup the staged kernel
-    // (two workgroups share a CU's LDS and matrix pipe; the direct kernel runs one wave per SIMD) wins clearly: 170 vs 277 us at
-    // 12 288 rows, 1.08 vs 1.40 ms at 100 K.  NGCF_DENSE_DIRECT=0 / 2: never / at any row count.
-    const int direct_env = ngcf_opts().dense_direct;
-    if (direct_env && dop >= 256 && padded && (n_rows <= 8192 || direct_env == 2)) {
+    HIP_TRY(pack_fp32(path.small_rows ? 1 : dop <= 128 ? dop / 32 : 4));
+    if (path.kernel == kDenseDirect) {
         const int64_t blocks = (n_rows + 31) / 32;
         if (dop == 256) call.launch(layer_dense_direct_kernel<2, 4>, blocks, 128, 0, Wt, bias2, n_chunks);
         else call.launch(layer_dense_direct_kernel<4, 4>, blocks, 256, 0, Wt, bias2, n_chunks);
@@ -1358,14 +1419,14 @@ extern "C" int ngcf_layer_dense_f32(const float *LE, int64_t ldLE, const float *
     }
 
     // the staged kernel (layer_dense_kernel)
-#define NGCF_DENSE(RW, CW, NT) launch_staged<RW, CW, NT>(call, al, padded, Wt, bias2, n_chunks)
-    if (small_rows) NGCF_DENSE(1, 4, 1);
-    else switch (dop) {
-    case 32: NGCF_DENSE(4, 1, 1); break;
-    case 64: NGCF_DENSE(4, 1, 2); break;
-    case 96: NGCF_DENSE(4, 1, 3); break;
-    case 128: NGCF_DENSE(4, 1, 4); break;
-    case 256: NGCF_DENSE(2, 2, 4); break;
+#define NGCF_DENSE(RW, CW, NT) launch_staged<RW, CW, NT>(call, path.al, path.padded, Wt, bias2, n_chunks)
+    switch (path.tile) {
+    case 0: NGCF_DENSE(1, 4, 1); break;
+    case 1: NGCF_DENSE(4, 1, 1); break;
+    case 2: NGCF_DENSE(4, 1, 2); break;
+    case 3: NGCF_DENSE(4, 1, 3); break;
+    case 4: NGCF_DENSE(4, 1, 4); break;
+    case 5: NGCF_DENSE(2, 2, 4); break;
     default: NGCF_DENSE(1, 4, 4);
     }
 #undef NGCF_DENSE

@@ -57,6 +57,57 @@ def test_host_only_entry_points():
         _lib.check(rc)
 
 
+def test_dense_path_names_the_kernel_the_dispatch_selects(lib_options):
+    """ngcf_dense_path is host code (sizes, operand alignment, options): the documented rules of the dense dispatch, by name."""
+    from seoul_tourism_recommendation_ngcf_amd import _lib
+    lib = _lib.load()
+    assert _lib.PROTOTYPES["ngcf_dense_path"][0] is C.c_char_p
+    lib_options(dense_small_tiles=1, dense_tall=1, dense_direct=1, dense_resident=4, dense_resident_min_rows=106496)
+    A, B = 0x10000, 0x20000                                   # 16-byte aligned addresses: never dereferenced
+
+    def path(n, d_in, d_out, ld=None, le=A, e=B, ld_e=None):
+        ld = (d_in + 3) // 4 * 4 if ld is None else ld
+        got = lib.ngcf_dense_path(n, d_in, d_out, le, ld, e, ld if ld_e is None else ld_e)
+        return None if got is None else got.decode()
+
+    # up to 128 columns: 32-row tiles up to 16 384 rows, then the 128-row tile of the width
+    assert path(16384, 64, 64) == "staged<1,4,1>/padded" and path(16385, 64, 64) == "staged<4,1,2>/padded"
+    assert [path(20000, 64, d) for d in (1, 32, 33, 64, 65, 96, 97, 128)] == [
+        f"staged<4,1,{nt}>/padded" for nt in (1, 1, 2, 2, 3, 3, 4, 4)]
+    # row layouts: padded, unaligned (a pointer, or either leading dimension), fewer than 4 columns in aligned rows
+    assert path(100, 65, 64, le=A + 4) == path(100, 65, 64, e=B + 8) == "staged<1,4,1>/unaligned"
+    assert path(100, 65, 64, ld=67) == path(100, 65, 64, ld_e=70) == "staged<1,4,1>/unaligned"
+    assert path(100, 3, 64, ld=4) == path(100, 1, 64, ld=8) == "staged<1,4,1>/aligned" and path(100, 4, 64) == "staged<1,4,1>/padded"
+    # 256 / 512 columns: tall and direct by the measured row ranges, staged beyond them or on unaligned rows
+    assert [path(n, 515, 512) for n in (5940, 6144, 6145, 8192, 8193, 200000)] == [
+        "tall512", "tall512", "direct<4,4>", "direct<4,4>", "tall512", "tall512"]
+    assert [path(n, 256, 129) for n in (5940, 8192, 8193, 131072, 131073)] == [
+        "direct<2,4>", "direct<2,4>", "tall256", "tall256", "staged<2,2,4>/padded"]
+    assert path(5940, 515, 512, ld=515) == "staged<1,4,4>/unaligned" and path(5940, 256, 256, le=A + 4) == "staged<2,2,4>/unaligned"
+    lib_options(dense_tall=0)
+    assert path(5940, 515, 512) == "direct<4,4>" and path(9000, 515, 512) == "staged<1,4,4>/padded"
+    lib_options(dense_direct=2)
+    assert path(9000, 515, 257) == "direct<4,4>"
+    lib_options(dense_tall=2, dense_direct=0)
+    assert path(7000, 515, 512) == "tall512" and path(1, 4, 200) == "tall256"
+    # 97..128 columns on many rows: the split kernel, or the fp32 resident kernel, while the weights fit in LDS
+    assert [path(n, 128, 128) for n in (106495, 106496)] == ["staged<4,1,4>/padded", "split"]
+    assert path(200000, 144, 97) == "split"
+    assert path(200000, 145, 97) == "staged<4,1,4>/padded" and path(200000, 128, 96) == "staged<4,1,3>/padded"
+    assert path(200000, 128, 128, le=A + 4) == "staged<4,1,4>/unaligned"
+    lib_options(dense_resident=1)
+    assert path(200000, 130, 100) == "resident"
+    lib_options(dense_resident_min_rows=1)
+    assert path(33, 17, 32) == "resident" and path(33, 145, 32) == "staged<1,4,1>/padded"
+    lib_options(dense_resident=0)
+    assert path(200000, 128, 128) == "staged<4,1,4>/padded"
+    # what ngcf_layer_dense_f32 rejects has no path
+    for bad in ((10, 64, 513), (10, 0, 64), (-1, 64, 64), (10, 64, 0)):
+        assert path(*bad) is None and "dense_path" in _lib.last_error()
+    assert path(10, 64, 64, ld=63) is None
+    assert path(0, 64, 64) == "staged<1,4,1>/padded"
+
+
 @pytest.mark.parametrize("name", ["fwd_sigA_small", "fwd_sigC_demo", "fwd_sigB_y19", "fwd_130_128"])
 def test_state_dict_surface_matches_reference_checkpoints(name):
     from seoul_tourism_recommendation_ngcf_amd import NGCF

@@ -7,45 +7,16 @@ pattern is the fp32 path's, bit for bit, and the rows of the normalised block ar
 The kernel runs from dense_resident_min_rows rows on; the sweep lowers that option (`lib_options`) so that its whole shape range -
 1..9 input chunks, full and partial last chunks, 97..128 output columns (and 32 / 64 on <= 16 384 rows, where the small-tile rule
 pads them to 128), 1..131 073 rows - runs at small row counts, with poisoned padding around every operand and output."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
+from dense_oracle import U32, carry_k, fp64_layer, norm_k      # the bounds and error measures live with the layer's host oracle
+
 pytestmark = pytest.mark.gpu
 
 N_ROWS = 140_001            # above dense_resident_min_rows; not a multiple of 32: a partial last tile
-U32 = 2.0 ** -24            # fp32 unit roundoff (round to nearest)
 SENT = -3.25                # sentinel in the columns around the carry / norm slices
-
-
-def carry_k(d_in):
-    """Bound on |carry - act| in units of 2^-24 * scale, scale = |A|.|B| + |bias| (A = [LE+E | LE*E] formed in fp32 as the kernel
-    forms it, so A itself carries no error; B = [W1^T ; W2^T]).
-
-    - Split: x = h + m + l EXACTLY for every fp32 operand (h = bf16(x) leaves a residual of at most 16 significant bits, m = bf16 of
-      that one of at most 8, which l holds exactly), |h| + |m| + |l| <= (1 + 2^-7)|x|.
-    - Dropped cross terms m.l, l.m, l.l: |m| <= 2^-8 (1 + 2^-8)|x|, |l| <= 2^-16 |x|, so at most (2 (1 + 2^-8) + 2^-8) 2^-24 |a||b|
-      per product: 2.01 in all.
-    - Accumulation: one fp32 accumulator per output element, six exact bf16 x bf16 products per real k (2 d_in of them: d_in sums
-      against W1, d_in products against W2; the zero columns past d_in add exact zeros).  Nothing is assumed about the order or
-      width of the MFMA's internal adder: every addition counts as one rounding, at most 12 d_in of them, each <= 2^-24 times a
-      partial sum <= (1 + 2^-7)^2 scale: 12.2 d_in, 12.5 d_in with the second-order terms.
-    - Epilogue: bias2 = (b1 + b1) + b2 (1 rounding, <= |bias|), acc + bias2 (1), LeakyReLU 0.2f * v (0.2f is 0.2 (1 + 2^-26),
-      + 1 rounding: 1.25), dropout keep scale fp32(1 / (1 - 0.3f)) or the host mask's fp32 1/0.7 (<= 2.3) times v (1): 3.3; the
-      dropout's 1/0.7 also scales `scale`.  7.6 in all.
-    k = 12.5 d_in + 2.01 + 7.6 <= 12.5 d_in + 10."""
-    return 12.5 * d_in + 10
-
-
-def norm_k(d_in, d_out):
-    """Bound on ||act|| * |norm - act/||act||| in units of 2^-24 * S, S = max over the row of scale.  The kernel's 1/||v||: sum of
-    squares in 9 roundings of non-negative terms (4 fmaf per lane, 5 shuffle adds), sqrtf (halves that, + 1), 1/x (1), v * inv
-    (1): 7.5 (+ 0.5 second order).  To first order ||act|| |n_j - a_j/||act||| <= |v_j - act_j| + |a_j/||act||| ||v - act|| +
-    8 u |act_j|, with |v_j - act_j| <= carry_k u scale_j, ||v - act|| <= carry_k u sqrt(d_out) S and |act_j| <= S:
-    k = carry_k (1 + sqrt(d_out)) + 8."""
-    return carry_k(d_in) * (1 + math.sqrt(d_out)) + 8
 
 
 @pytest.fixture(scope="module")
@@ -99,24 +70,8 @@ def _check_against_fp64(le, e, W1, b1, W2, b2, mode, keep, c32, n32, csp, nsp):
     """Errors of both kernels on the sampled rows (CPU tensors: le, e [R, d_in]; the outputs' rows [R, d_out], carries None in
     mode "last"; keep the dropout keep pattern or None) against fp64; asserts the split kernel's bounds."""
     d_in, d_out = le.shape[1], W1.shape[0]
-    A = torch.cat((le + e, le * e), 1).double()          # the operands as both kernels form them (fp32 sums and products)
-    B = torch.cat((W1.T, W2.T), 0).double()
-    bias = (b1 + b1 + b2).double()
-    pre = A @ B + bias
-    scale = A.abs() @ B.abs() + bias.abs()               # what the rounding error of the product is measured against
-    act = torch.where(pre >= 0, pre, 0.2 * pre)
-    if keep is not None:
-        act = act * keep.double() / 0.7
-        scale = scale * keep.double() / 0.7
-    rn = act.norm(dim=1, keepdim=True)
-    nrm = act / rn.clamp_min(1e-12)
-    S = scale.amax(dim=1, keepdim=True)
-
-    def err_carry(c):
-        return float(((c.double() - act).abs() / (scale + 1e-300)).max())
-
-    def err_norm(nb):
-        return float(((nb.double() - nrm).abs() * rn.clamp_min(1e-12) / (S + 1e-300)).max())
+    ref = fp64_layer(le, e, W1, b1, W2, b2, keep)
+    err_carry, err_norm = ref.err_carry, ref.err_norm
 
     out = {}
     # the fp32 kernel is the yardstick, so it is held to the same bounds (its chain is shorter: 2 d_in fp32 products and sums)
