@@ -652,6 +652,39 @@ int ngcf_groupby_lookup(const ngcf_groupby_cols_t *cols, int64_t T, const uint64
 int ngcf_decimal_code(const void *const *columns, const int32_t *is64, const int32_t *widths, int n_columns, int64_t T, int64_t *out,
                       int32_t *status, void *stream);
 
+/* ---- trip context (csrc/context.hip; the reference's congestion pivot and distance loop, demo.py:99-102, 241-248) ----
+ * ngcf_segment_kahan_sum_f64: per segment u = order[rowptr[u] .. rowptr[u+1]) (positions into the value columns; order == NULL is
+ * the identity: the rows are already grouped) and per value column k < n_values <= 4 (HOST arrays of device pointers: values[k]
+ * double [T], sums[k] double [n_rows]) the compensated sum of pandas' group_sum, its recurrence in ascending position order:
+ *   s = 0; c = 0
+ *   for each v of the segment that is not a NaN:  y = v - c;  t = s + y;  c = (t - s) - y;  if c is a NaN: c = 0;  s = t
+ *   sums[k][u] = s                                          (an empty or all-NaN segment: 0.0)
+ * every operation an individually rounded fp64 one, never re-associated: the bits are pandas' (`pivot_table(aggfunc='sum')`,
+ * `groupby().sum()`) when the positions of a segment are in row order.  Segments of fewer than wave_min rows (0: the default; any
+ * positive value) are walked by one lane each; longer ones by one wave each, which fetches 64 rows at a time, coalesced through
+ * `order`, and runs the chain on wave-uniform values read across the lanes.  Both tiers perform the same operations in the same
+ * order: the result does not depend on wave_min, and, as no sum is touched by an atomic, not on the run.  *status is OR-ed into,
+ * never cleared: 1 = a rowptr that decreases or leaves [0, T], or an order entry outside [0, T): never read through, that
+ * segment's sums are NaN.  Argument errors, before any launch: n_values outside [1, 4], a negative wave_min or count, a null
+ * pointer (`order` may be NULL; values[k] may be NULL when T == 0); n_rows == 0 is not an error.
+ *
+ * ngcf_haversine_table_f64: out[s * n_item + i] = the great-circle distance in metres between departure point s (dep double [S, 2])
+ * and item i (item double [n_item, 2]), coordinates in degrees, the FIRST one taken as the latitude - the `haversine` package's
+ * formula on the tuples the demo hands it, operation for operation:
+ *   lat1, lng1, lat2, lng2 = x * (pi / 180)                 (CPython's math.radians)
+ *   d   = sin((lat2 - lat1) * 0.5)^2 + (cos(lat1) * cos(lat2)) * sin((lng2 - lng1) * 0.5)^2
+ *   out = ((2 * 6371.0088) * asin(sqrt(d))) * 1000          (2 * 6371.0088 folded on the host)
+ * every product, sum and difference an individually rounded fp64 operation (no FMA), and sin, cos and asin the correctly rounded
+ * ones (csrc/dd_math.h: double-double arithmetic out of IEEE add, multiply, fma, divide and sqrt, the same text on host and
+ * device), so the table has the bits of a host whose maths library rounds these calls correctly - glibc does on all but a few
+ * arguments in a thousand.  A result that is a NaN (a NaN coordinate; a d
+ * that rounds above 1 at exact antipodes) is written as +inf: "missing, sorts last" to ngcf_topk_rows_f32 on the negated table.
+ * One thread per output, items fastest; lat1 and cos(lat1) once per row and workgroup, cos(lat2) once per thread.  Argument
+ * errors, before any launch: a negative count, a null pointer; S == 0 or n_item == 0 is not an error and writes nothing. */
+int ngcf_segment_kahan_sum_f64(const int64_t *rowptr, int64_t n_rows, const int64_t *order, const double *const *values, int n_values,
+                               int64_t T, int wave_min, double *const *sums, int32_t *status, void *stream);
+int ngcf_haversine_table_f64(const double *dep, int64_t S, const double *item, int64_t n_item, double *out, void *stream);
+
 /* ---- exact per-group sampling (csrc/select.hip; the reference's Preprocess.split_train_test, utils.py:126-148) ----
  * From every group g of the T rows exactly quota[g] rows are marked, uniformly among all subsets of that size: pandas'
  * `sample(frac=, replace=False)` of a part of a frame (one group) and the per-class draws of sklearn's stratified split (one group

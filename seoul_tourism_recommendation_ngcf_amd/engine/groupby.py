@@ -63,8 +63,8 @@ def groupby_packing(bounds: Sequence[Tuple[int, int]]):
     return offsets, ranges, bits, shifts
 
 
-_NO_FLOAT_SUMS = ("only integer columns are summed: pandas' float group sum is compensated, so its bits cannot be met, and "
-                  "floating-point atomics would make the result depend on arrival order")
+_NO_FLOAT_SUMS = ("only integer columns are summed here: pandas' float group sum is compensated and takes a group's rows in row order "
+                  "(engine.context.group_sum_float does), and floating-point atomics would make the result depend on arrival order")
 
 
 def _int_columns(fn: str, groups):
@@ -102,7 +102,7 @@ def group_by(columns: Sequence[torch.Tensor], values: Sequence[torch.Tensor] = (
     return_inverse=True)` plus `np.add.at` (ngcf_groupby_*; the steps are in include/ngcf_hip.h).  Returns `Groups(keys, sums,
     inverse)`: the G distinct key rows ascending by (column 0, column 1, ...) as K int64 [G] tensors, the V int64 [G] sums (exact,
     modulo 2^64), and with `inverse=True` the int64 [T] group index of every row.  Integer atomics only: the same call returns the
-    same tensors.  Floating value columns are a TypeError.  The columns' (min, max) are read back once to pack the keys into
+    same tensors.  Floating value columns are a TypeError (`context.group_sum_float` sums them).  The columns' (min, max) are read back once to pack the keys into
     <= 63 bits (more: ValueError), or taken from `bounds` (K pairs; a value outside them: ValueError); G and the status word are the
     other read-back.  `capacity` (a power of two; default: the power of two >= 2 x min(T, product of the ranges), which cannot
     overflow) is doubled and the call run again while the table turns out too small; `lds_slots` (0: off; a power of two up to

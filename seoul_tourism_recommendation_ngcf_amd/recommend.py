@@ -7,10 +7,15 @@ rank points (first place 100, then 99, ...), blends them with the traveller's we
 member and day, per day, per member, overall), filters by genre and prints the best `rec_num` destinations of every column; it
 does so in a pandas loop with some twenty data-frame re-indexings per request row.  Here: one ranking launch per chunk of rows
 (engine.rank_topk), one top list per context table (engine.topk_rows), one blend launch (engine.blend_points) and one read-back.
+
+What the reference does between loading its pickles and that loop is here too, from raw rows: `congestion_table` (the pivot of
+demo.py:96-103 and the per-day slice of demo.py:270-274), `distance_table` (the haversine loop of demo.py:241-248), `party_rows`
+(the party unrolled into request rows, demo.py:134-181), `context_slots` (the table row of every request row) and `order_table`
+(fp64 tables as dense ranks, so that the cast to fp32 inside `blended_ranking` keeps the fp64 order and its ties).
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -192,3 +197,204 @@ def blended_ranking(model, user_ids: torch.Tensor, *, features=None, year=None, 
             return out
     finally:
         model.train(was_training)
+
+
+# ---- the trip context from raw rows: what demo.py builds between its pickles and the blend -------------------------------------------
+INF = float("inf")
+MONTH_DAYS = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)           # demo.py:114, month_info: no leap year
+
+
+def congestion_table(month: torch.Tensor, day: torch.Tensor, dayofweek: torch.Tensor, item: torch.Tensor, values, *, n_item: int,
+                     by: int = 0, wave_min: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The congestion pivot of demo.py:99-102 over raw rows, laid out as `blended_ranking` takes it: `month`, `day`, `dayofweek`,
+    `item` int32 / int64 [T] (item: already the itemid) and `values`, one float64 [T] column or up to four (congestion_1,
+    congestion_2, ...), on one device.  Returns `(table float64 [S, n_item], days int64 [S, 3])`: one table row per distinct
+    (month, day, dayofweek), ascending, whose entry i is pandas' sum - its compensated sum, bit for bit - of column `by` over the
+    rows of that day and item (`engine.context.group_sum_float`), +inf where the log has no such row: the per-day slice of
+    demo.py:270-274, which `blended_ranking` sorts by that column.  The G group sums are scattered with torch indexing (distinct
+    targets).  An item outside [0, n_item): IndexError."""
+    fn = "congestion_table"
+    n_item, by = int(n_item), int(by)
+    if n_item < 1:
+        raise ValueError(f"{fn}: n_item={n_item}")
+    cols = [values] if isinstance(values, torch.Tensor) else list(values)
+    if not 0 <= by < max(len(cols), 1):
+        raise ValueError(f"{fn}: by={by} outside the {len(cols)} value columns")
+    groups = engine.context.group_sum_float((month, day, dayofweek, item), cols, wave_min=wave_min)
+    keys, dev = groups.keys, groups.keys[0].device
+    G = int(keys[0].numel())
+    if G == 0:
+        return torch.empty((0, n_item), dtype=torch.float64, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev)
+    if int(keys[3].min()) < 0 or int(keys[3].max()) >= n_item:
+        raise IndexError(f"{fn}: an item lies outside [0, {n_item})")
+    triple = torch.stack(keys[:3], 1)                                          # ascending: the groups are sorted by (month, day, dow, item)
+    first = torch.ones(G, dtype=torch.bool, device=dev)
+    first[1:] = (triple[1:] != triple[:-1]).any(1)
+    slot = torch.cumsum(first, 0) - 1
+    days = triple[first]
+    table = torch.full((int(days.shape[0]), n_item), INF, dtype=torch.float64, device=dev)
+    table[slot, keys[3]] = groups.sums[by]
+    return table, days
+
+
+def distance_table(departure_xy: torch.Tensor, item_xy: torch.Tensor) -> torch.Tensor:
+    """float64 [S, n_item]: the metres between every departure point (float64 [S, 2]) and every destination (float64 [n_item, 2]),
+    `haversine(dep, arr) * 1000` of demo.py:241-248 for all pairs in one launch (`engine.context.haversine_table`: the first
+    coordinate is the latitude to the formula, as in the reference).  A NaN coordinate gives +inf."""
+    return engine.context.haversine_table(departure_xy, item_xy)
+
+
+def order_table(values: torch.Tensor) -> torch.Tensor:
+    """float32 [S, n_item]: every entry of a context table (float [S, n_item], any device) replaced by its dense rank within its
+    row - 0 for the smallest value, equal values equal ranks; +inf stays +inf and a NaN a NaN.  `blended_ranking` casts its tables
+    to fp32, which can merge fp64 values that the reference's sort keeps apart (metres at 1e4 have an fp32 spacing of 1e-3); ranks
+    are exact in fp32 for n_item < 2^24, so the fp64 order and its ties reach `engine.topk_rows` unchanged.  Set-up code in torch
+    ops."""
+    if values.dim() != 2 or not values.dtype.is_floating_point:
+        raise ValueError(f"order_table: values must be a floating [S, n_item] table, got {values.dtype} {tuple(values.shape)}")
+    S, n = int(values.shape[0]), int(values.shape[1])
+    if n >= 2 ** 24:
+        raise ValueError(f"order_table: n_item={n}: ranks are exact in float32 below 2^24 only")
+    if n == 0:
+        return values.to(torch.float32)
+    ordered, idx = torch.sort(values, dim=1, stable=True)                      # NaNs last, after +inf
+    step = torch.zeros((S, n), dtype=torch.int64, device=values.device)
+    step[:, 1:] = ordered[:, 1:] != ordered[:, :-1]
+    rank = torch.empty((S, n), dtype=torch.float32, device=values.device)
+    rank.scatter_(1, idx, torch.cumsum(step, 1).to(torch.float32))
+    rank[values == INF] = INF
+    rank[values != values] = float("nan")
+    return rank
+
+
+class PartyRows(NamedTuple):
+    """`party_rows`' result, every field int64 [R]: the request row's party and member (its position in the input), its user id
+    (None without `user_codes`) and the five features."""
+    party: torch.Tensor
+    member: torch.Tensor
+    user_ids: Optional[torch.Tensor]
+    age: torch.Tensor
+    sex: torch.Tensor
+    month: torch.Tensor
+    day: torch.Tensor
+    dow: torch.Tensor
+
+    @property
+    def features(self):
+        """(age, sex, month, day, dow), as `blended_ranking` takes them."""
+        return (self.age, self.sex, self.month, self.day, self.dow)
+
+
+def _per_party(fn: str, x, name: str, P: int, dev) -> torch.Tensor:
+    t = torch.as_tensor(x).to(device=dev, dtype=torch.int64).reshape(-1)
+    if int(t.numel()) == 1:
+        t = t.expand(P)
+    if int(t.numel()) != P:
+        raise ValueError(f"{fn}: {name} has {int(t.numel())} entries for {P} parties")
+    return t
+
+
+def party_rows(party: torch.Tensor, age: torch.Tensor, sex: torch.Tensor, *, start_month, start_day, start_dow, duration,
+               user_codes: Optional[torch.Tensor]) -> PartyRows:
+    """The request rows of demo.py:134-181 for any number of parties.  `party`, `age` (in years), `sex` int64 [M], one entry per
+    member: party[m] in [0, P) is the member's party; `start_month`, `start_day`, `start_dow`, `duration` are one int for all
+    parties or [P] each.  Per member, in input order, one row per day k = 0 .. duration - 1 of its party's stay:
+      age   (age // 10) * 10 + 5                                    (demo.py:152)
+      date  the reference's walk from the start (a Feb 29 becomes Feb 28): a day past MONTH_DAYS[month] becomes
+            day % MONTH_DAYS[month] and the month moves on           (demo.py:135-136, 154-165)
+      dow   (start_dow + k) % 7
+      id    the position of `engine.decimal_code((age, sex, month, day), (0, 0, 2, 2))` - the string str(age) + str(sex) + mm + dd -
+            in `user_codes`, the sorted codes `preprocess.map_ids` produced (IdMaps.user_codes): `user_dict[u_feats]`.
+    A row whose string is not in the dictionary raises IndexError naming the first such row (the reference's KeyError); so does a
+    stay that walks past December (the reference reaches month 13 and fails on the same lookup) - before any device work.
+    `user_codes` None: no lookup, `user_ids` is None and the rest, torch ops only, runs on any device."""
+    fn = "party_rows"
+    for nm, t in (("party", party), ("age", age), ("sex", sex)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{fn}: {nm} must be an int32 or int64 tensor")
+        if t.dim() != 1 or int(t.numel()) != int(party.numel()):
+            raise ValueError(f"{fn}: {nm} must be [M = {int(party.numel())}], got {tuple(t.shape)}")
+    dev, M = party.device, int(party.numel())
+    party, age, sex = (t.to(torch.int64) for t in (party, age, sex))
+    i64 = lambda n: torch.zeros(n, dtype=torch.int64, device=dev)  # noqa: E731
+    if M == 0:
+        return PartyRows(*(i64(0) for _ in range(2)), None if user_codes is None else i64(0), *(i64(0) for _ in range(5)))
+    if int(party.min()) < 0:
+        raise IndexError(f"{fn}: a negative party number")
+    if int(age.min()) < 0 or int(sex.min()) < 0:
+        raise ValueError(f"{fn}: a negative age or sex")
+    P = int(party.max()) + 1
+    m0, d0, w0, dur = (_per_party(fn, x, nm, P, dev) for x, nm in ((start_month, "start_month"), (start_day, "start_day"),
+                                                                   (start_dow, "start_dow"), (duration, "duration")))
+    if int(dur.min()) < 0 or int(m0.min()) < 1 or int(m0.max()) > 12 or int(d0.min()) < 1:
+        raise ValueError(f"{fn}: a negative duration, a start month outside [1, 12] or a start day below 1")
+    d0 = torch.where((m0 == 2) & (d0 == 29), torch.full_like(d0, 28), d0)
+    # the walk, once per party: [P, D] tables of the date on day k of the stay
+    D = int(dur.max())
+    lens = torch.tensor((0,) + MONTH_DAYS + (MONTH_DAYS[-1],), dtype=torch.int64, device=dev)      # index 13: never compared against
+    month_k, day_k = torch.empty((P, max(D, 1)), dtype=torch.int64, device=dev), torch.empty((P, max(D, 1)), dtype=torch.int64, device=dev)
+    mon, dd = m0.clone(), d0 - 1
+    for k in range(D):
+        dd = dd + 1
+        ln = lens[mon.clamp(max=13)]
+        over = (dd > ln) & (mon <= 12)                     # past December the reference has already failed: the month stays 13
+        dd = torch.where(over, dd % ln, dd)
+        mon = mon + over.to(torch.int64)
+        month_k[:, k], day_k[:, k] = mon, dd
+    per_member = dur[party]
+    member = torch.repeat_interleave(torch.arange(M, device=dev), per_member)
+    R = int(member.numel())
+    start = torch.cumsum(per_member, 0) - per_member
+    k = torch.arange(R, device=dev) - start[member]
+    p = party[member]
+    month, day = month_k[p, k], day_k[p, k]
+    dow = (w0[p] + k) % 7
+    age_r, sex_r = (age[member] // 10) * 10 + 5, sex[member]
+    late = torch.nonzero(month > 12)
+    if int(late.numel()):
+        r = int(late[0])
+        raise IndexError(f"{fn}: request row {r} (member {int(member[r])}, day {int(k[r])} of the stay) lies past December: "
+                         "the reference's dictionary has no month 13")
+    user_ids = None
+    if user_codes is not None:
+        if user_codes.dtype != torch.int64 or user_codes.dim() != 1:
+            raise TypeError(f"{fn}: user_codes must be int64 [n_user], got {user_codes.dtype} {tuple(user_codes.shape)}")
+        code = engine.decimal_code((age_r, sex_r, month, day), (0, 0, 2, 2))
+        codes = user_codes.to(code.device).contiguous()
+        n = int(codes.numel())
+        user_ids = torch.searchsorted(codes, code)
+        known = (user_ids < n) & (codes[user_ids.clamp(max=max(n - 1, 0))] == code) if n else torch.zeros_like(code, dtype=torch.bool)
+        miss = torch.nonzero(~known)
+        if int(miss.numel()):
+            r = int(miss[0])
+            raise IndexError(f"{fn}: request row {r}: '{int(age_r[r])}{int(sex_r[r])}{int(month[r]):02d}{int(day[r]):02d}' is not in "
+                             "the user dictionary")
+    return PartyRows(p, member, user_ids, age_r, sex_r, month, day, dow)
+
+
+def context_slots(days: torch.Tensor, month: torch.Tensor, day: torch.Tensor, dow: torch.Tensor) -> torch.Tensor:
+    """int64 [R]: the row of `congestion_table`'s `days` (int64 [S, 3], ascending (month, day, dayofweek)) that holds every request
+    row's (month, day, dow) - the `congestion_slot` of `blended_ranking`.  A request row whose day the table does not have raises
+    IndexError naming the first (the reference ends up with an empty frame there, demo.py:270-274).  Torch ops, any device."""
+    fn = "context_slots"
+    if days.dim() != 2 or int(days.shape[1]) != 3 or days.dtype != torch.int64:
+        raise ValueError(f"{fn}: days must be int64 [S, 3], got {days.dtype} {tuple(days.shape)}")
+    dev = days.device
+    rows = torch.stack([t.reshape(-1).to(device=dev, dtype=torch.int64) for t in (month, day, dow)], 1)
+    if int(rows.shape[0]) == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    every = torch.cat((days, rows))
+    if int(every.min()) < 0 or int(every.max()) >= 2 ** 20:
+        raise IndexError(f"{fn}: a month, day or dayofweek outside [0, 2^20)")
+    pack = lambda t: (t[:, 0] * 2 ** 20 + t[:, 1]) * 2 ** 20 + t[:, 2]  # noqa: E731
+    have, want = pack(days).contiguous(), pack(rows).contiguous()
+    S = int(have.numel())
+    if S > 1 and not bool((have[1:] > have[:-1]).all()):
+        raise ValueError(f"{fn}: days is not in ascending order without repeats")
+    slot = torch.searchsorted(have, want)
+    found = (slot < S) & (have[slot.clamp(max=max(S - 1, 0))] == want) if S else torch.zeros_like(want, dtype=torch.bool)
+    miss = torch.nonzero(~found)
+    if int(miss.numel()):
+        r = int(miss[0])
+        raise IndexError(f"{fn}: request row {r}: the congestion table has no day (month, day, dayofweek) = {tuple(rows[r].tolist())}")
+    return slot
