@@ -685,6 +685,76 @@ int ngcf_segment_kahan_sum_f64(const int64_t *rowptr, int64_t n_rows, const int6
                                int64_t T, int wave_min, double *const *sums, int32_t *status, void *stream);
 int ngcf_haversine_table_f64(const double *dep, int64_t S, const double *item, int64_t n_item, double *out, void *stream);
 
+/* ---- delimited text (csrc/text.hip; the reference's `pd.read_csv(path, sep='|')`, utils.py:38-39, for int and float columns) ----
+ * The input is a uint8 [n] DEVICE buffer, 16-byte aligned.  The delimiter is one byte below 0x80 that is no digit, '+', '-', '.',
+ * 'e', 'E', space, tab, CR, LF or '"'.  Quoting, comments, strings and dates are not supported.
+ *
+ * Rows.  Position p < n starts a row if (p == 0 or byte[p-1] == '\n') and the line is not blank; a line is blank if byte[p] == '\n',
+ * or byte[p] == '\r' followed by '\n', or byte[p] == '\r' with p + 1 == n (pandas' skip_blank_lines).  A final line without a
+ * newline is a row.  A row's text ends before its '\n' and before a '\r' directly in front of that - or, on a final line without a
+ * newline, directly in front of the end of the buffer, the case the blank rule names.
+ *   ngcf_text_count_rows  block_counts[b] (int64 [ceil(n / count_block_bytes)]) = the row starts among the bytes of block b; one
+ *                         16-byte load per lane and step.  A '"' anywhere sets NGCF_TEXT_QUOTE.  (The caller scans the counts.)
+ *   ngcf_text_row_starts  given block_offsets[b] = the rows before block b (the exclusive scan) and their total n_rows, writes
+ *                         starts int64 [n_rows + 1]: the row starts in ascending order and starts[n_rows] = n.  A start whose rank is
+ *                         not below n_rows (the buffer changed between the passes) is not written: NGCF_TEXT_LOST.
+ *
+ * ngcf_text_parse_columns: of the rows skip_rows .. n_rows - 1 of `starts` (the leading ones skipped are the header) and of the
+ * n_fields <= 64 fields of every row, n_columns <= 16 are parsed: column s is field fields[s] of kind kinds[s] (0 int64, 1 float64;
+ * HOST arrays; a field is selected at most once) and goes to out[s] (HOST array of device pointers, int64 or double
+ * [n_rows - skip_rows]), one value per data row, written with ordinary stores.  One lane per row, a workgroup per run of
+ * rows_per_workgroup rows: the run's bytes, up to lds_bytes of them, are brought into LDS with coalesced 16-byte loads, and a row
+ * that does not end inside that window is walked straight from memory by its lane - the same code through a flat pointer, the same
+ * results.  tier: 0 as described, 1 every row from memory, 2 as 0 and a row walked from memory sets NGCF_TEXT_TIER (tests, tools).
+ * Spaces and tabs around a field are skipped.
+ *   int64    [+-]?[0-9]+ ; an empty field, any other byte or a value outside int64 is an error, the overflow found exactly
+ *            (-9223372036854775808 is a value).
+ *   float64  [+-]?(digits[.digits?]|.digits)([eE][+-]?digits)? ; an empty field, nan, NaN and NA give NaN; [+-]?inf and
+ *            [+-]?Infinity the infinities; any other byte is an error.  The decimal significand is gathered as an unsigned integer m
+ *            (leading zeros stripped, at most 19 digits) with a decimal exponent e, so that the field is m * 10^e:
+ *              m == 0                        a signed zero
+ *              m <= 2^53 and |e| <= 22       m * 10^e (e >= 0) or m / 10^-e: ONE IEEE fp64 operation on two operands that are exact
+ *                                            (a table of the powers), never contracted and never a reciprocal multiply, hence
+ *                                            correctly rounded: the bits of strtod and of Python's float()
+ *              anything else                 a SLOW field: NaN is written and (data row << 8) | column appended to slow_list
+ *                                            (int64 [slow_capacity]) at the position an integer atomic counter hands out; the counter
+ *                                            (status[2]) goes on counting past the capacity, so that the caller can size a second run.
+ * status: int64 [4], 8-byte aligned, set by the caller to {0, -1, 0, 0} before the first of the three calls:
+ *   status[0]  sticky bits, OR-ed in: NGCF_TEXT_FIELDS a row with fewer or more than n_fields fields (pandas pads the first case;
+ *              both are refused here), NGCF_TEXT_BYTE a byte outside the grammar, NGCF_TEXT_EMPTY an empty int field,
+ *              NGCF_TEXT_OVERFLOW an int outside int64, NGCF_TEXT_QUOTE a '"', NGCF_TEXT_LOST row starts that do not belong to
+ *              the buffer (never read through: the row's columns are 0 / NaN), NGCF_TEXT_TIER (see tier)
+ *   status[1]  the FIRST offending field as an unsigned word, (data row << 16) | (field << 8) | kind (NGCF_TEXT_KIND_*; a wrong
+ *              field count has field 0; a field that holds a '"' reports that and nothing else), kept with an atomic minimum: the
+ *              same on every run
+ *   status[2]  the number of slow fields
+ * A row with an error still has every selected column written (0 or NaN where there is nothing to parse).
+ * Argument errors, before any launch (NGCF_ERR_ARG, message "text_...: ..."): a negative n, a null pointer, a buffer that is not
+ * 16-byte aligned, a bad delimiter, n_fields outside [1, 64], n_columns outside [1, 16], a field index outside [0, n_fields) or
+ * selected twice, a kind other than 0 and 1, skip_rows outside [0, n_rows], a tier outside [0, 2].  n == 0 is not an error.
+ * ngcf_text_limits: rows_per_workgroup and lds_bytes of the parse, count_block_bytes of the two row passes. */
+#define NGCF_TEXT_MAX_FIELDS 64
+#define NGCF_TEXT_MAX_COLUMNS 16
+#define NGCF_TEXT_KIND_FIELDS 1
+#define NGCF_TEXT_KIND_BYTE 2
+#define NGCF_TEXT_KIND_EMPTY 3
+#define NGCF_TEXT_KIND_OVERFLOW 4
+#define NGCF_TEXT_KIND_QUOTE 5
+#define NGCF_TEXT_FIELDS 1
+#define NGCF_TEXT_BYTE 2
+#define NGCF_TEXT_EMPTY 4
+#define NGCF_TEXT_OVERFLOW 8
+#define NGCF_TEXT_QUOTE 16
+#define NGCF_TEXT_LOST 32
+#define NGCF_TEXT_TIER 64
+int ngcf_text_limits(int *rows_per_workgroup, int *lds_bytes, int *count_block_bytes);
+int ngcf_text_count_rows(const uint8_t *data, int64_t n, int64_t *block_counts, int64_t *status, void *stream);
+int ngcf_text_row_starts(const uint8_t *data, int64_t n, const int64_t *block_offsets, int64_t n_rows, int64_t *starts, int64_t *status,
+                         void *stream);
+int ngcf_text_parse_columns(const uint8_t *data, int64_t n, const int64_t *starts, int64_t n_rows, int64_t skip_rows, int n_fields,
+                            int delimiter, const int32_t *fields, const int32_t *kinds, int n_columns, void *const *out, int64_t *slow_list,
+                            int64_t slow_capacity, int tier, int64_t *status, void *stream);
+
 /* ---- exact per-group sampling (csrc/select.hip; the reference's Preprocess.split_train_test, utils.py:126-148) ----
  * From every group g of the T rows exactly quota[g] rows are marked, uniformly among all subsets of that size: pandas'
  * `sample(frac=, replace=False)` of a part of a frame (one group) and the per-class draws of sklearn's stratified split (one group

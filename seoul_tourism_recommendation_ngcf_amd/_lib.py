@@ -118,6 +118,11 @@ PROTOTYPES = {
     "ngcf_decimal_code": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i32), C.c_int, _i64, _vp, _vp, _vp]),
     "ngcf_segment_kahan_sum_f64": (C.c_int, [_vp, _i64, _vp, C.POINTER(_vp), C.c_int, _i64, C.c_int, C.POINTER(_vp), _vp, _vp]),
     "ngcf_haversine_table_f64": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "ngcf_text_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ngcf_text_count_rows": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "ngcf_text_row_starts": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "ngcf_text_parse_columns": (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_int, C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int,
+                                          C.POINTER(_vp), _vp, _i64, C.c_int, _vp, _vp]),
     "ngcf_select_limits": (C.c_int, [_i64, C.POINTER(C.c_int), C.POINTER(_i64)]),
     "ngcf_select_key": (_u64, [_u64, _i64]),
     "ngcf_select_per_group": (C.c_int, [_vp, _i64, _i64, _vp, _u64, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -28,17 +28,24 @@ table in memory, integer atomics), the rows sorted by the five keys as pivot_tab
 string str(age) + str(sex) + mm + dd among the sorted distinct strings - not the numeric order: age 5 sorts between 45 and 55.  The
 string becomes an integer with the same order (engine.decimal_code: every character a base-11 digit), so the map is one more
 group-by with an inverse, and the reference's dictionaries come out of the few distinct keys on the host (`IdMaps.user_dict`,
-`IdMaps.item_dict`).  `num_dict` is the dictionary of utils.py:152-158.  Reading the CSV stays the caller's.
+`IdMaps.item_dict`).  `num_dict` is the dictionary of utils.py:152-158.
+
+And so is its first line, `pd.read_csv(path, sep='|')` (utils.py:38-39): `read_visits` takes the log's bytes to the device in one
+transfer and parses the six columns the pivot takes there (engine.text: the row starts in two passes, then a lane per row; the
+file's other columns - `total_num`, `area`, `date365`, which the reference drops - are never parsed), and `load_visits` is
+`aggregate_visits` of that: `load_preprocess_data` without its `.sample(100)`, from a path to a `VisitTable` with neither pandas nor
+a host loop.
 
 Not here: the string `scaler='power'` as an alias of that (it stays refused, with a message that says what to pass, until a change
-that may edit the test pinning the refusal), Box-Cox and `inverse_transform`, reading `Datasets_v5.0.txt` (and the reference's
-`.sample(100)` of it), the permuted row order in which the reference's split returns its parts (see `split_by_year`), and the
+that may edit the test pinning the refusal), Box-Cox and `inverse_transform`, the reference's `.sample(100)` of the rows it has
+read, quoted fields, string and date columns of a file (`engine.text`), the permuted row order in which the reference's split returns its parts (see `split_by_year`), and the
 reference's index-alignment quirk when year-20 rows are filtered before the scaler's output is assigned back (`map_ids` takes the
 rows the caller kept).  (`graphs.holdout_split` is another thing: a per-user leave-some-out split of the synthetic graphs.)
 """
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple, Union
 
@@ -312,6 +319,44 @@ def aggregate_visits(date: torch.Tensor, destination: torch.Tensor, dayofweek: t
     g = engine.group_by((date, destination, dayofweek, sex, age), (visitor,), lds_slots=lds_slots)
     d = g.keys[0]
     return VisitTable(d, g.keys[1], g.keys[2], g.keys[3], g.keys[4], g.sums[0], (d // 10000) % 100, (d // 100) % 100, d % 100)
+
+
+VISIT_COLUMNS = ("date", "destination", "dayofweek", "sex", "age", "visitor")
+
+
+def read_visits(source, *, device=None, columns: Sequence[str] = VISIT_COLUMNS, sep: str = "|") -> Tuple[torch.Tensor, ...]:
+    """The raw visit log, `pd.read_csv(path, sep='|')` of utils.py:38-39, as int64 [T] columns on the device, in the order of
+    `columns` - by default the six that `aggregate_visits` takes, in its order.  `source` is a path (read with `np.fromfile` and
+    copied to the device in one transfer), a `bytes` object, or a uint8 tensor on any device; `device` defaults to the tensor's own
+    if that is a ROCm device and to 'cuda' otherwise.  The first row is the header and names the columns; the file's other columns
+    (the reference's has `total_num`, `area`, `date365`, which it drops) are never parsed.  `engine.text.read_table` does the work:
+    its grammar and its errors (ValueError with the data row, the column and the kind; KeyError for a column the header lacks)."""
+    if isinstance(source, torch.Tensor):
+        data = source
+        if device is None and not source.is_cuda:
+            device = "cuda"
+    else:
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            host = np.frombuffer(source, dtype=np.uint8).copy()
+        elif isinstance(source, (str, os.PathLike)):
+            host = np.fromfile(source, dtype=np.uint8)
+        else:
+            raise TypeError(f"read_visits: source must be a path, bytes or a uint8 tensor, got {type(source).__name__}")
+        data = torch.from_numpy(host)
+        device = "cuda" if device is None else device
+    if data.dtype != torch.uint8:
+        raise TypeError(f"read_visits: the source tensor must be uint8, got {data.dtype}")
+    if device is not None:
+        data = data.to(device)
+    table, _ = engine.text.read_table(data, {c: torch.int64 for c in columns}, sep=sep, header=True)
+    return tuple(table[c] for c in columns)
+
+
+def load_visits(source, *, device=None, lds_slots: Optional[int] = None) -> VisitTable:
+    """`Preprocess.load_preprocess_data` (utils.py:36-55) without its `.sample(100)`: `aggregate_visits(*read_visits(source))`, from
+    the log's path (or bytes, or a uint8 tensor) to the pivoted rows on the device.  `date` stays the integer yyyymmdd, as
+    `VisitTable` documents: the reference's `pd.to_datetime` only re-types it."""
+    return aggregate_visits(*read_visits(source, device=device), lds_slots=lds_slots)
 
 
 USER_KEY_WIDTHS = (0, 0, 2, 2)          # str(age) + str(sex) + '%m' + '%d' (utils.py:52-54, 71)
