@@ -790,6 +790,45 @@ uint64_t ngcf_select_key(uint64_t seed, int64_t t);
 int ngcf_select_per_group(const int32_t *group, int64_t T, int64_t G, const int64_t *quota, uint64_t seed, uint8_t *mask,
                           uint64_t *thresholds, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- Adam step (csrc/adam.hip; the reference's `optimizer.step()`, experiment.py:58, of main.py:74's torch.optim.Adam) ----
+ * One launch per 32 tensors (NGCF_ADAM_MAX_TENSORS; more tensors, more launches of the same kernel) updates p, m = exp_avg,
+ * v = exp_avg_sq in place from g and advances the tensors' step counters.  params, grads, exp_avgs, exp_avg_sqs, steps: HOST arrays
+ * of n_tensors device pointers, numel a HOST array of element counts (int64; a tensor of 0 elements is skipped, its pointers not
+ * looked at).  p, g, m, v are contiguous fp32 [numel[i]]; steps[i] is a float32 word, the steps taken so far - torch's capturable
+ * format (`state["step"]`, a 0-dim float32 tensor on the device), exact up to 2^24 as there, and not guarded beyond.  The step words
+ * of one call must be distinct.  The descriptors travel by value in the kernel arguments: no table in memory, no upload per step; a
+ * captured launch is replayed as it stands, with lr, betas, eps and weight_decay baked in.
+ * A workgroup of 256 threads takes one chunk of 4 096 elements of one tensor.  It reads its tensor's step word first, t = step + 1.
+ * Scalars, once per workgroup, in fp64 with IEEE operations only (no pow):
+ *   beta^t, in double-double (hi, lo), square-and-multiply on the integer t:
+ *       r = (1, 0); b = (beta, 0); e = t
+ *       while e > 0:  if e odd: r = mul(r, b);   e = e >> 1;   if e > 0: b = mul(b, b)
+ *       beta^t = r.hi
+ *     mul((a, al_), (b, bl_)), every operation rounded once, none contracted, S = 2^27 + 1:
+ *       p = a * b;   c = S * a;  ah = c - (c - a);  al = a - ah;   c = S * b;  bh = c - (c - b);  bl = b - bh
+ *       e = (((ah * bh - p) + ah * bl) + al * bh) + al * bl;       e = e + (a * bl_ + al_ * b)
+ *       hi = p + e;   lo = e - (hi - p)
+ *     (a plain fp64 chain of squarings doubles its relative error at every squaring: about t * 2^-53 at the end)
+ *   bc1 = 1 - beta1^t;   step_size = -(lr / bc1);   bc2s = sqrt(1 - beta2^t)
+ * step_size, bc2s, c1 = 1 - beta1, beta2, c2 = 1 - beta2, eps and wd = weight_decay are each rounded to fp32 once.
+ * Per element, in fp32, every operation rounded once, none contracted, division and sqrt correctly rounded, denormals kept:
+ *   g = maximize ? -g : g;          if (wd != 0) g = g + wd * p
+ *   m = m + c1 * (g - m)
+ *   v = v * beta2 + (c2 * g) * g
+ *   d = sqrt(v) / bc2s + eps
+ *   p = p + step_size * (m / d)
+ * 16-byte loads and stores where p, g, m and v of a tensor are all 16-byte aligned, element by element otherwise and for the last
+ * numel % 4 elements - through the same per-element function, the same bits.  tests/adam_oracle.py restates all of this on the host.
+ * After its stores a workgroup takes a ticket from *ticket (a uint32 device word of the caller's, 0 before the first call) with an
+ * integer atomic add; the workgroup that takes the launch's last ticket writes step + 1 to every tensor's step word and sets *ticket
+ * back to 0.  Stream order shows the next launch the new steps.  No float atomics: equal inputs give equal bits on every run.
+ * Argument errors, before any launch (NGCF_ERR_ARG, message "adam_step: ..."): a negative count, a null pointer, a pointer that is
+ * not 4-byte aligned, a tensor of more than 2^31 / 32 chunks.  n_tensors == 0 is not an error. */
+#define NGCF_ADAM_MAX_TENSORS 32
+int ngcf_adam_step_f32(int n_tensors, void *const *params, const void *const *grads, void *const *exp_avgs, void *const *exp_avg_sqs,
+                       void *const *steps, const int64_t *numel, uint32_t *ticket, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, int maximize, void *stream);
+
 /* ---- multi-GPU row partition (new design; host-only helper) --------------- */
 /*
  * Cut rows [row_begin, row_end) into `world` contiguous ranges of roughly equal stored-entry

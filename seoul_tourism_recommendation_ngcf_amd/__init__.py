@@ -12,5 +12,6 @@ from . import evaluate
 from . import recommend
 from . import sampling
 from . import preprocess
+from . import optim
 
-__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling", "preprocess"]
+__all__ = ["NGCF", "BPR", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling", "preprocess", "optim"]

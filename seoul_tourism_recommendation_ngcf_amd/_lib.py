@@ -126,6 +126,8 @@ PROTOTYPES = {
     "ngcf_select_limits": (C.c_int, [_i64, C.POINTER(C.c_int), C.POINTER(_i64)]),
     "ngcf_select_key": (_u64, [_u64, _i64]),
     "ngcf_select_per_group": (C.c_int, [_vp, _i64, _i64, _vp, _u64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ngcf_adam_step_f32": (C.c_int, [C.c_int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _vp,
+                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _vp]),
     "ngcf_shard_plan": (C.c_int, [C.POINTER(_i64), _i64, _i64, C.c_int, C.POINTER(_i64)]),
     "ngcf_allgather_rows": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "ngcf_comm_size": (C.c_int, [_vp, C.POINTER(C.c_int)]),
