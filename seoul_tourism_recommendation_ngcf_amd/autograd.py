@@ -61,17 +61,28 @@ class _Probe:
 
 def static_result_counts(all_E: torch.Tensor):
     """(Python references, C++ references, tensors on the storage) of a graph's STATIC all_E - compared with the same reading taken
-    when only the graph runner held it (`GraphedForward`, `NGCF._TrainGraphs`): anything more means a caller still holds the previous
-    replay's `model.all_items_emb` / `all_users_emb` / a slice of them, and the next forward must not replay over it (the reference
-    allocates a fresh all_E per call, NGCF.py:147-149)."""
+    when only the graph runner held it (`GraphedForward`, `train_graphs._TrainGraphs`): anything more means a caller still holds the
+    previous replay's `model.all_items_emb` / `all_users_emb` / a slice of them, and the next forward must not replay over it (the
+    reference allocates a fresh all_E per call, NGCF.py:147-149)."""
     return (sys.getrefcount(all_E), all_E._use_count(), torch._C._storage_Use_Count(all_E.untyped_storage()._cdata))
 
 
 def static_result_baseline(all_E: torch.Tensor):
     """The reading of `static_result_counts` for a tensor only its runner holds, taken through ONE intermediate frame - the shape of
-    the later check (`NGCF._static_result_held(all_E, ...)` -> `static_result_counts(all_E)`): every frame that binds the tensor to a
-    parameter is one more Python reference, so the two readings must come up the same call depth."""
+    the later check (`_static_result_held(model, all_E, ...)` -> `static_result_counts(all_E)`): every frame that binds the tensor to
+    a parameter is one more Python reference, so the two readings must come up the same call depth."""
     return static_result_counts(all_E)
+
+
+def _static_result_held(model, static_all_E, free_counts) -> bool:
+    """Does a caller still hold the previous replay's `all_users_emb` / `all_items_emb` / `_all_E` (or a view of them)?  They are
+    views of the graph's static all_E, which the next replay overwrites - the reference hands out a fresh `cat` per call
+    (NGCF.py:147-149), so a held tensor must stay what it was: then this forward runs eagerly (r04; r03 documented the
+    overwrite as a deviation).  The module's own references are dropped first - both paths set them again."""
+    d = model.__dict__
+    if d.get("_all_E") is static_all_E or getattr(d.get("all_users_emb"), "_base", None) is static_all_E:
+        d["_all_E"] = d["all_users_emb"] = d["all_items_emb"] = None
+    return static_result_counts(static_all_E) != free_counts
 
 
 class E0Cache:

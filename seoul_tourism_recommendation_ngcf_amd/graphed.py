@@ -16,7 +16,27 @@ from __future__ import annotations
 import torch
 
 from . import engine as _eng
-from .autograd import propagate_forward, static_result_baseline
+from .NGCF import _raise_bad_index
+from .autograd import _static_result_held, propagate_forward, static_result_baseline
+
+
+def _batch_sizes(u_id, age, sex, month, day, dow, pos_item, neg_item):
+    """(len(u_id), len(pos_item), len(neg_item)) of a batch whose five feature index vectors are as long as u_id."""
+    sizes = (len(u_id), len(pos_item), len(neg_item))
+    for v in (age, sex, month, day, dow):
+        if len(v) != sizes[0]:
+            raise RuntimeError("shape mismatch: feature index vectors and u_id differ in length")
+    return sizes
+
+
+def _load_indices(static, vals, dev):
+    """A batch into a graph's static index buffers: one multi-tensor copy when every vector is an int64 tensor on the graph's
+    device (the usual case), else one copy each."""
+    if all(v.dtype == torch.int64 and v.device == dev and v.dim() == 1 for v in vals):
+        torch._foreach_copy_(static, vals)
+    else:
+        for s, v in zip(static, vals):
+            s.copy_(v.reshape(-1), non_blocking=True)
 
 
 class _Buffers:
@@ -115,8 +135,7 @@ class GraphedForward:
         return self.replay(check)
 
     def load_inputs(self, u_id, age, sex, month, day, dow, pos_item, neg_item=None):
-        """The batch into the graph's static index buffers: one multi-tensor copy when every vector is an int64 tensor on the
-        graph's device (the usual case), else one copy each."""
+        """The batch into the graph's static index buffers (`_load_indices`)."""
         given = dict(u_id=u_id, age=age, sex=sex, month=month, day=day, dow=dow, pos_item=pos_item)
         if self.with_neg:
             given["neg_item"] = neg_item
@@ -125,12 +144,7 @@ class GraphedForward:
             if v is None or int(v.numel()) != want:
                 raise RuntimeError(f"GraphedForward was captured for {want} elements of {k}: got "
                                    f"{0 if v is None else int(v.numel())}")
-        vals = list(given.values())
-        if all(v.dtype == torch.int64 and v.device == self.dev and v.dim() == 1 for v in vals):
-            torch._foreach_copy_([self.inputs[k] for k in given], vals)
-        else:
-            for k, v in given.items():
-                self.inputs[k].copy_(v.reshape(-1), non_blocking=True)
+        _load_indices([self.inputs[k] for k in given], list(given.values()), self.dev)
 
     def _baked_pointers(self):
         b = self.bufs
@@ -154,10 +168,7 @@ class GraphedForward:
         return u, p, n
 
     def check_status(self):
-        if int(self.status.item()) != 0:                   # (a host sync: every replay so far has written its mirror)
-            self.status.zero_()
-            self.status_host.zero_()
-            raise IndexError("index out of range in NGCF.forward (u_id / feature ids / pos_item / neg_item)")
+        _raise_bad_index(self.status, self.status_host)    # (a host sync: every replay so far has written its mirror)
 
     def peek_status(self):
         """No host sync: has a replay that the GPU has FINISHED seen an out-of-range id?  (Its last node copied the sticky status
@@ -165,6 +176,52 @@ class GraphedForward:
         if int(self.status_host[0]) != 0:
             self.check_status()
 
+
+def _graph_key(model, dev, sizes, year_idx):
+    # the parameter tensors' addresses: from a cached list of the Parameter objects (walking the module tree costs 25 us, more
+    # than the replay's launch) that is rebuilt after train() / eval(), .to() / .cuda(), load_state_dict() and every 16th call
+    model._key_calls = getattr(model, "_key_calls", 0) + 1           # (its own counter: `_graph_calls` only moves on inference replays)
+    if model._plist is None or model._key_calls % 16 == 0:
+        model._plist = list(model.parameters())
+    ptrs = tuple(p.data_ptr() for p in model._plist)
+    return (sizes, year_idx, id(model.lap_list[year_idx]), str(dev), ptrs, float(model.emb_ratio))     # (emb_ratio is a kernel argument)
+
+
+def forward_graphed(model, dev, year, u_id, age, sex, month, day, dow, pos_item, neg_item):
+    """`NGCF.auto_graph`: the inference forward as a hipGraph replay (`GraphedForward`): captured on first use per (index vector
+    lengths, year slice), re-captured when a parameter or `lap_list` entry was replaced (`.to()`, a new tensor assigned); in-place
+    updates (`load_state_dict`, optimizer steps) need nothing - the graph reads the parameters when it runs.  Returns fresh
+    tensors like the eager path, or None: this call runs eagerly.  Out-of-range ids raise IndexError at the next call after the GPU
+    has run the replay (its last node copies the sticky status word to pinned host memory: `_peek_status`, no sync), at the latest
+    `index_check_every` calls later (a synchronising read); `check_indices_now()` reads it on demand."""
+    year_idx = model._year_index(year)
+    sizes = _batch_sizes(u_id, age, sex, month, day, dow, pos_item, neg_item)
+    key = _graph_key(model, dev, sizes, year_idx)                  # IndexError for a bad year_idx, like the reference
+    g = model._graphs.pop(key, None)
+    if g is None:
+        if key not in model._graph_seen:                           # first call of a shape runs eagerly: its ids are checked at once,
+            if len(model._graph_seen) > 64:                        # and a shape that never comes back is never captured
+                model._graph_seen.clear()
+            model._graph_seen.add(key)
+            return None
+        stale = [k for k in model._graphs if k[:4] == key[:4]]     # same shape, replaced parameters: those graphs are dead
+        for k in stale + list(model._graphs)[:max(0, len(model._graphs) - len(stale) - 7)]:
+            model._graphs.pop(k, None)
+        g = GraphedForward(model, sizes[0], year_idx, with_neg=sizes[2] > 0, pos_size=sizes[1], neg_size=sizes[2] or None)
+    model._graphs[key] = g
+    if _static_result_held(model, g.out[0], g._free):
+        return None                                                # a caller kept the last replay's all_*_emb: eager, into fresh tensors
+    model._graph_calls += 1
+    if model.check_indices:
+        model._peek_status()                                       # an earlier replay's bad id, as soon as the GPU got there
+    g.load_inputs(u_id=u_id, age=age, sex=sex, month=month, day=day, dow=dow, pos_item=pos_item,
+                  neg_item=neg_item if sizes[2] > 0 else None)
+    u, p, n = g.replay(check=False)
+    if model.check_indices and model._graph_calls % max(1, int(model.index_check_every)) == 0:
+        g.check_status()
+    outs = [torch.empty_like(u), torch.empty_like(p)] + ([torch.empty_like(n)] if sizes[2] > 0 else [])
+    torch._foreach_copy_(outs, [u, p] + ([n] if sizes[2] > 0 else []))         # fresh tensors like the eager path, one launch
+    return outs[0], outs[1], (outs[2] if sizes[2] > 0 else torch.empty(0))
 
 
 class GraphedTrainStep:
@@ -190,8 +247,7 @@ class GraphedTrainStep:
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
             raise RuntimeError("GraphedTrainStep: build the optimizer with capturable=True (torch keeps its step counters on the device then)")
         dev = model._dev()
-        N, D = model.n_user + model.n_item, model.emb_size + sum(model.weight_size)
-        if N * D * 4 > _ag.DENSE_GRAD_MAX_BYTES:
+        if model._all_E_bytes() > _ag.DENSE_GRAD_MAX_BYTES:
             raise RuntimeError("GraphedTrainStep is for launch-bound sizes: the backward of a larger graph reads the number of gathered "
                                "rows back to the host (a step of that size is not launch-bound anyway)")
         self.model, self.criterion, self.optimizer, self.node_flag, self.dev = model, criterion, optimizer, bool(node_flag), dev
@@ -241,11 +297,7 @@ class GraphedTrainStep:
             if int(v.numel()) != int(self.inputs[k].numel()):
                 raise RuntimeError(f"GraphedTrainStep was captured for {self.inputs[k].numel()} elements of {k}: got {int(v.numel())}")
             vals.append(v)
-        if all(v.dtype == torch.int64 and v.device == self.dev and v.dim() == 1 for v in vals):
-            torch._foreach_copy_([self.inputs[k] for k in self.KEYS], vals)
-        else:
-            for k, v in zip(self.KEYS, vals):
-                self.inputs[k].copy_(v.reshape(-1), non_blocking=True)
+        _load_indices([self.inputs[k] for k in self.KEYS], vals, self.dev)
         if self._baked_pointers() != self._baked:
             raise RuntimeError("GraphedTrainStep: a buffer or parameter baked into the captured step was replaced; capture again")
         if self.model.check_indices:

@@ -11,7 +11,7 @@ import importlib
 
 from seoul_tourism_recommendation_ngcf_amd import _lib
 
-ngcf_mod = importlib.import_module("seoul_tourism_recommendation_ngcf_amd.NGCF")      # (the package re-exports the class under this name)
+ngcf_mod = importlib.import_module("seoul_tourism_recommendation_ngcf_amd.reference_masks")
 
 
 def _ours(n, keep, want_noise):
@@ -42,7 +42,7 @@ def test_host_draws_are_torchs_own(pre, n):
 
 
 def test_module_helper_consumes_the_default_generator_like_the_reference():
-    """`NGCF._reference_bernoulli` (what the reference-mode forward calls): same masks and the same generator state as two
+    """`reference_masks._reference_bernoulli` (what the reference-mode forward calls): same masks and the same generator state as two
     `F.dropout` calls in the reference's order - the node mask on float64 ones, then the message noise on float32 ones."""
     assert ngcf_mod._host_rng_ok()
     torch.manual_seed(77)
@@ -84,7 +84,7 @@ def test_draw_ahead_hands_over_exactly_what_the_forward_would_draw():
     reseed, a foreign draw or another program the helper's work is dropped."""
     import copy
     import importlib
-    mod = importlib.import_module("seoul_tourism_recommendation_ngcf_amd.NGCF")
+    mod = importlib.import_module("seoul_tourism_recommendation_ngcf_amd.reference_masks")
     if not mod._host_rng_ok():
         pytest.skip("this torch build draws differently: masks come from torch itself, nothing is drawn ahead")
     program = (9001, 0.3, (0.1, 0.0, 0.25), 321, (10, 8, 6, 7))       # node dropout + message dropout on two of three layers
@@ -136,7 +136,7 @@ def test_draw_ahead_with_programs_that_do_not_repeat():
     Its buffers are put aside per program and come back (no page-locked allocation per forward), and after three misses in a row
     it stands back for 32 forwards; a hit resets the count."""
     import importlib
-    mod = importlib.import_module("seoul_tourism_recommendation_ngcf_amd.NGCF")
+    mod = importlib.import_module("seoul_tourism_recommendation_ngcf_amd.reference_masks")
     if not mod._host_rng_ok():
         pytest.skip("this torch build draws differently: nothing is drawn ahead")
     A = (5000, 0.3, (0.1,), 100, (8, 8))

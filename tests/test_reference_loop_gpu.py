@@ -100,7 +100,7 @@ def test_the_references_own_loop_is_bit_identical_with_and_without_graph_replays
 
 def test_reference_mode_masks_drawn_ahead_are_the_masks_drawn_in_place(lap, dev, monkeypatch):
     """r04: in the module's DEFAULT dropout modes the masks of the next forward are drawn on a helper thread while the step runs
-    (`NGCF._DrawAhead`: from a copy of the generator state, taken over only if the generator is still in that state).  The
+    (`reference_masks._DrawAhead`: from a copy of the generator state, taken over only if the generator is still in that state).  The
     reference's loop gives the same losses and the same final parameters with the helper on and off - through the mode switch at
     the end of epoch 1 (another program: message dropout off), the evaluation batches in between (no draws) and a re-seed in the
     middle of an epoch - and the helper's masks are the ones used wherever the program repeats."""
