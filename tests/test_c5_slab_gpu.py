@@ -84,7 +84,7 @@ def test_c5_rank_slabs_of_eight():
             del csr, LX, LY, LZ, carry, nrm
         del ur, uc, uv, ir, ic, iv, slabs
         if rank == 3:
-            # the same rank's slabs in the DEFAULT exchange scheme (bipartite, dist._setup): user rows x item replica in the
+            # the same rank's slabs in the DEFAULT exchange scheme (bipartite, sharded.py): user rows x item replica in the
             # owner-major padded numbering, and the transposed slab that forms the item partial sums over the local users
             ob = nd.even_bounds(0, I, W)
             mi = max(ob[q + 1] - ob[q] for q in range(W))

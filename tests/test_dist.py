@@ -68,7 +68,7 @@ def _cpu_worker(rank, world, port, ret):
         want = orc.propagate_torch(L, E0[:U], E0[U:], w1, b1, w2, b2)
 
         # ---- all-gather scheme: padded chunk-major / rank-major layout, the user slab pipelined in 3 row chunks, every
-        # chunk's asynchronous all-gather issued right after the chunk (dist._propagate_allgather does exactly this);
+        # chunk's asynchronous all-gather issued right after the chunk (multigpu/allgather.py does exactly this);
         # the slabs are cut from the interaction triplets, never from the doubled COO
         from seoul_tourism_recommendation_ngcf_amd import graphs
         iu, ii, iw = graphs.synthetic_interactions(U, I, 3000, seed=5, device="cpu")
@@ -137,7 +137,7 @@ def _cpu_worker(rank, world, port, ret):
         local = got_i[torch.where(mine, loc, torch.zeros_like(loc))]
         assert torch.allclose(nd.owner_rows_sum(local, mine), want[U:][it], atol=1e-6)
 
-        # ---- bipartite scheme (dist._propagate_bipartite does exactly this): users partitioned by stored entries, item carry
+        # ---- bipartite scheme (multigpu/bipartite.py does exactly this): users partitioned by stored entries, item carry
         # replicated in the owner-major padded numbering; per layer a reduce-scatter of the item partial sums to the owners
         # (gloo has none: all-reduce + own rows), the dense half for the owned items only, an all-gather of their carry rows
         eb = nd.balanced_bounds(cnt, 0, U, world)
@@ -491,7 +491,7 @@ def _p2p_collectives_worker(rank, world, port, ret):
     """`P2PCollectives.all_gather` / `reduce_scatter` land their pulls in FRESH tensors.  The caching allocator hands a block out
     again by stream order of the COMPUTE stream; the pulls run on copy streams - without the fence in `_stage` they could land while
     kernels of the block's previous owner are still queued (the failure the exchange's self-test showed once in three runs with
-    five ranks, dist.py `selftest`).  Here the previous owner is made as unkind as possible: a tensor of exactly the result's size
+    five ranks, p2p.py `selftest`).  Here the previous owner is made as unkind as possible: a tensor of exactly the result's size
     with a long queue of kernels writing it, freed right before the collective."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NGCF_P2P_TIMEOUT_MS="20000")
     dist.init_process_group("gloo", rank=rank, world_size=world)

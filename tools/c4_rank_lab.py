@@ -1,5 +1,5 @@
 """Compute time of ONE rank of the row-partitioned C3 graph (BASELINE config 4) at W = 1, 2, 4, 8, on one GPU: the rank's item
-slab and user chunks through the real kernels of dist._propagate_allgather, the exchange left out.  This is the compute side of
+slab and user chunks through the real kernels of multigpu/allgather.py, the exchange left out.  This is the compute side of
 the scaling question only (an upper bound on the speed-up if the all-gather cost nothing); the exchange itself needs more than
 one GPU to measure.  Also prints the bytes a rank receives per layer."""
 import os, sys
@@ -65,7 +65,7 @@ for W in (1, 2, 4, 8):
           f"all-gather: {recv / 1e6:.0f} MB received per rank and layer = {recv / 153e9 * 1e3 / max(W - 1, 1) * (W - 1) / 7 if W > 1 else 0:.2f} ms if all 7 links "
           f"of 153 GB/s were busy, {recv / 153e9 * 1e3:.2f} ms over one link", flush=True)
 
-# ---- the bipartite scheme (r03 form, dist._propagate_bipartite): users partitioned by stored entries, item carry replicated in the
+# ---- the bipartite scheme (r03 form, multigpu/bipartite.py): users partitioned by stored entries, item carry replicated in the
 # owner-major padded numbering; per rank and layer: item partial sums over the local users (small table, high re-use), the local
 # user rows (gather from the item replica), the sum of the W partial-sum slices of the OWNED items and their dense half (I/W rows)
 print("bipartite scheme (reduce-scatter of the item partial sums to their owners, sharded item dense, all-gather of the owned carry "
@@ -138,11 +138,11 @@ for W in (1, 2, 4, 8):
           f"(partial-sum slices + carry rows) = {sent / max(W - 1, 1) / 153e9 * 1e3:.3f} ms with every peer on its own 153 GB/s link", flush=True)
 
 # ---- r04: what does NOT shrink with W - the per-pass floor of the W = 8 rank (the last loop's W, r, eb, ob still hold): the E0
-# copy of the local rows (skipped from the second pass on while the tables are unchanged: dist._propagate_bipartite `keep`), the
+# copy of the local rows (skipped from the second pass on while the tables are unchanged: multigpu/bipartite.py `keep`), the
 # served row gathers over the exchange (owned rows -> exchange buffer, W blocks pulled, one select kernel) and BPR
 B, D = 1024, 512
 nu, ni = hi - lo, ob[r + 1] - ob[r]
-allE = torch.randn((nu + ni, D), device=dev) * 0.1                 # one result buffer, users first (dist._propagate_bipartite)
+allE = torch.randn((nu + ni, D), device=dev) * 0.1                 # one result buffer, users first (multigpu/bipartite.py)
 allE_u, allE_i = allE[:nu], allE[nu:]
 uw, iw = torch.randn((U, d), device=dev), torch.randn((I, d), device=dev)
 status = torch.zeros(1, dtype=torch.int32, device=dev)
