@@ -12,6 +12,7 @@
 #include <cstring>
 #include <numeric>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/ngcf_hip.h"
@@ -48,7 +49,7 @@ inline int fail(int code, const char *fmt, ...)
 
 
 // ---------------------------------------------------------------------------------------------
-// options: every tunable of the dispatch code in ONE struct.  csr.hip fills it once per process (the only getenv() of the
+// options: every tunable of the dispatch code in ONE struct.  library.hip fills it once per process (the only getenv() of the
 // library is in ngcf_options_from_env there: launches never touch the environment) and ngcf_set_option changes single
 // fields at run time (tests, tools/).
 // ---------------------------------------------------------------------------------------------
@@ -88,8 +89,8 @@ struct NgcfOptions {
     int swept_prio_kb = 256;       // NGCF_SWEPT_PRIO_KB
     int swept_prio_graded = 1;     // NGCF_SWEPT_PRIO_GRADED
 };
-extern NgcfOptions g_opts;                      // csr.hip
-const NgcfOptions &ngcf_opts();                 // csr.hip: reads the environment on first use
+extern NgcfOptions g_opts;                      // library.hip
+const NgcfOptions &ngcf_opts();                 // library.hip: reads the environment on first use
 
 
 // per-device state (function attributes, side streams) lives in small arrays indexed by the current device
@@ -137,8 +138,8 @@ struct ngcf_csr {
     int32_t *colidx = nullptr;   // device [nnz]
     float *vals = nullptr;       // device [nnz]
     bool owns = false;
-    // a thinned copy made by ngcf_csr_filter (csr.hip): capacity of colidx / vals, the exclusive scan of the keep flags over the
-    // source's entries (pos[e] = kept entries before e, pos[src nnz] = kept in all), scan scratch; seg_row / heavy_row /
+    // a thinned copy made by ngcf_csr_filter (csr_filter.hip): capacity of colidx / vals, the exclusive scan of the keep flags over
+    // the source's entries (pos[e] = kept entries before e, pos[src nnz] = kept in all), scan scratch; seg.seg_row / heavy_row /
     // heavy_seg_ptr are then BORROWED from the source (same segment structure, own seg_begin) and nnz may be an upper bound
     int64_t cap = 0, pos_len = 0;
     int32_t *pos = nullptr;
@@ -146,12 +147,15 @@ struct ngcf_csr {
     bool borrows_plan = false;
     const struct ngcf_csr *filter_src = nullptr;
     // row segmentation: rows with > seg_len entries are cut into segments
+    struct SegSet {
+        int64_t n_seg = 0, n_heavy = 0;
+        int32_t *seg_row = nullptr;        // device [n_seg]   row of each segment
+        int64_t *seg_begin = nullptr;      // device [n_seg]   first entry of each segment
+        int32_t *heavy_row = nullptr;      // device [n_heavy] rows that were cut
+        int64_t *heavy_seg_ptr = nullptr;  // device [n_heavy+1] their segment ranges
+    };
     int32_t seg_len = 0;
-    int64_t n_seg = 0, n_heavy = 0;
-    int32_t *seg_row = nullptr;        // device [n_seg]   row of each segment
-    int64_t *seg_begin = nullptr;      // device [n_seg]   first entry of each segment
-    int32_t *heavy_row = nullptr;      // device [n_heavy] rows that were cut
-    int64_t *heavy_seg_ptr = nullptr;  // device [n_heavy+1] their segment ranges
+    SegSet seg;                        // the cut rows of the whole matrix
     // row groups: maximal runs of rows whose gathered column range is small enough that d-slicing pays
     struct RowGroup {                   // col_hi < col_lo: no entries
         int64_t begin, end;
@@ -163,13 +167,6 @@ struct ngcf_csr {
     // L2-swept plan (spmm_swept.hip): built on request (mode 2/3) for long-lived matrices
     int mode = 0;                      // 0 row-wise (+ d-sliced groups), 1 row-wise only, 2 swept wherever the shape
                                        // allows, 3 swept on the row groups where the plan expects L2 re-use to pay
-    struct SegSet {                    // rows cut into segments (device arrays, same meaning as seg_row.. above)
-        int64_t n_seg = 0, n_heavy = 0;
-        int32_t *seg_row = nullptr;
-        int64_t *seg_begin = nullptr;
-        int32_t *heavy_row = nullptr;
-        int64_t *heavy_seg_ptr = nullptr;
-    };
     struct Swept {
         struct Part {                      // one row group handled by the swept kernel
             int64_t row_lo = 0, row_hi = 0;
@@ -213,10 +210,28 @@ static inline int32_t default_seg_len(int64_t nnz)
     return s;
 }
 
+// device copy of a host array (an empty one still gets an allocation: a non-null pointer)
+template <typename T>
+int upload(T **dptr, const std::vector<T> &h, hipStream_t stream)
+{
+    HIP_TRY(hipMalloc(dptr, sizeof(T) * std::max<size_t>(h.size(), 1)));
+    if (!h.empty()) HIP_TRY(hipMemcpyAsync(*dptr, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, stream));
+    return NGCF_OK;
+}
+
+// the segment plan on the host (csr.hip): the rows of `ranges` longer than seg_len, cut at seg_len
+struct HostSegs {
+    std::vector<int32_t> seg_row, heavy_row;
+    std::vector<int64_t> seg_begin, heavy_ptr;
+};
+HostSegs cut_rows(const std::vector<int64_t> &rowptr, const std::vector<std::pair<int64_t, int64_t>> &ranges, int32_t seg_len);
+int upload_segset(ngcf_csr::SegSet &s, const HostSegs &h, hipStream_t stream);   // no cut rows: no allocation, null pointers
+void free_segset(ngcf_csr::SegSet &s, bool borrowed = false);  // borrowed (a filtered copy): only seg_begin is its own
+
 void free_swept(ngcf_csr *c);                                  // spmm_swept.hip
 int build_swept_plan(ngcf_csr *c, hipStream_t stream);         // spmm_swept.hip (reads c->mode)
 bool swept_usable(const ngcf_csr *c, int64_t ldE, int d);       // spmm_swept.hip: can this call use the parts?
-void prof_mark(hipStream_t stream, int which);                 // spmm.hip: hipEvent around the SpMM launches
+void prof_mark(hipStream_t stream, int which);                 // library.hip: hipEvent around the SpMM launches
 
 // counter-based hash: the keep masks of node and message dropout and the draws of sample.hip are pure functions of (seed, index)
 __host__ __device__ inline uint64_t fmix64(uint64_t x)

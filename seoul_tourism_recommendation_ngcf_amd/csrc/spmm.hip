@@ -1,4 +1,4 @@
-// spmm.hip - row-wise CSR SpMM kernels (plain + d-sliced), dispatch, workspace sizing, launch timing.
+// spmm.hip - row-wise CSR SpMM kernels (plain + d-sliced), dispatch, workspace sizing.
 #include "spmm_device.h"
 
 // One launch covers the whole product: the first `seg_blocks` workgroups take the segments of the cut
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void spmm_tail_kernel(const int64_t *__restric
 
 // one tail product through its compact tables (workspace: [partial sums ... | T_in [n_cols] | T_out [n_rows]] as 16-byte slots)
 template <int TW>
-static int launch_tail(const ngcf_csr *c, const float *E, int64_t ldE, int tail, float *out, int64_t ldo, void *workspace,
+static int launch_tail(const ngcf_csr *c, const ngcf_csr::SegSet &s, const float *E, int64_t ldE, int tail, float *out, int64_t ldo, void *workspace,
                        int64_t workspace_bytes, hipStream_t stream, const EdgeDrop &dr)
 {
     using V = typename VecT<TW>::type;
@@ -322,19 +322,19 @@ static int launch_tail(const ngcf_csr *c, const float *E, int64_t ldE, int tail,
     LAUNCH_CHECK();
     // cut rows (the CSR's own segment plan): one partial V per segment at the start of the workspace, then the fix-up
     V *tpart = reinterpret_cast<V *>(align_up((int64_t)(uintptr_t)workspace, 256));
-    const int64_t seg_blocks = (c->n_seg + 15) / 16, row_blocks = (c->n_rows + 15) / 16;
+    const int64_t seg_blocks = (s.n_seg + 15) / 16, row_blocks = (c->n_rows + 15) / 16;
     if (seg_blocks + row_blocks >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "spmm: too many rows for one launch");
     prof_mark(stream, 0);
     if (dr.n > 0)
         spmm_tail_kernel<TW, true><<<dim3((unsigned)(seg_blocks + row_blocks)), 256, 0, stream>>>(
-            c->rowptr, c->colidx, c->vals, c->n_rows, c->seg_row, c->seg_begin, c->n_seg, seg_blocks, c->seg_len, Tin, Tout, tpart, dr);
+            c->rowptr, c->colidx, c->vals, c->n_rows, s.seg_row, s.seg_begin, s.n_seg, seg_blocks, c->seg_len, Tin, Tout, tpart, dr);
     else
         spmm_tail_kernel<TW, false><<<dim3((unsigned)(seg_blocks + row_blocks)), 256, 0, stream>>>(
-            c->rowptr, c->colidx, c->vals, c->n_rows, c->seg_row, c->seg_begin, c->n_seg, seg_blocks, c->seg_len, Tin, Tout, tpart, dr);
+            c->rowptr, c->colidx, c->vals, c->n_rows, s.seg_row, s.seg_begin, s.n_seg, seg_blocks, c->seg_len, Tin, Tout, tpart, dr);
     LAUNCH_CHECK();
-    if (c->n_heavy > 0) {
-        spmm_fixup_kernel<TW><<<dim3((unsigned)((c->n_heavy + 3) / 4)), 256, 0, stream>>>(
-            c->heavy_row, c->heavy_seg_ptr, c->n_heavy, reinterpret_cast<const float *>(tpart), TW, TW, reinterpret_cast<float *>(Tout), TW);
+    if (s.n_heavy > 0) {
+        spmm_fixup_kernel<TW><<<dim3((unsigned)((s.n_heavy + 3) / 4)), 256, 0, stream>>>(
+            s.heavy_row, s.heavy_seg_ptr, s.n_heavy, reinterpret_cast<const float *>(tpart), TW, TW, reinterpret_cast<float *>(Tout), TW);
         LAUNCH_CHECK();
     }
     prof_mark(stream, 1);
@@ -350,7 +350,7 @@ static int64_t tail_table_bytes(const ngcf_csr *c)
 
 static int64_t partial_bytes(const ngcf_csr *c, int d)
 {
-    const int64_t n_part = std::max(c->n_seg, c->swept.out.n_seg + c->swept.n_partial);
+    const int64_t n_part = std::max(c->seg.n_seg, c->swept.out.n_seg + c->swept.n_partial);
     return align_up(n_part * align_up(d, 4) * (int64_t)sizeof(float), 256) + 256;
 }
 
@@ -359,52 +359,6 @@ extern "C" int64_t ngcf_spmm_workspace_bytes(const ngcf_csr_t *c, int d)
     if (!c || d <= 0) return -1;
     // [partial sums of the cut rows][compact tail table] - the table sits at the end, the partial sums at the start
     return partial_bytes(c, d) + tail_table_bytes(c);
-}
-
-// ---------------------------------------------------------------------------------------------
-// optional in-library timing of the dominant kernel (bench.py's roofline figure): when enabled,
-// a hipEvent pair is recorded on the launch stream around every spmm_kernel launch.
-// ---------------------------------------------------------------------------------------------
-static bool g_prof_on = false;
-static std::vector<hipEvent_t> g_prof_events;   // pairs: begin, end
-static size_t g_prof_used = 0;
-
-void prof_mark(hipStream_t stream, int which)
-{
-    if (!g_prof_on) return;
-    if (g_prof_used >= g_prof_events.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        g_prof_events.push_back(e);
-    }
-    (void)which;
-    (void)hipEventRecord(g_prof_events[g_prof_used++], stream);
-}
-
-extern "C" int ngcf_prof_enable(int on)
-{
-    g_prof_on = on != 0;
-    g_prof_used = 0;
-    return NGCF_OK;
-}
-
-// Waits for the recorded events; returns the number of timed spmm launches and their summed duration.
-extern "C" int ngcf_prof_collect(int64_t *n_launches, double *total_ms)
-{
-    if (!n_launches || !total_ms) return fail(NGCF_ERR_ARG, "prof_collect: null argument");
-    double sum = 0.0;
-    int64_t n = 0;
-    for (size_t i = 0; i + 1 < g_prof_used; i += 2) {
-        float ms = 0.f;
-        HIP_TRY(hipEventSynchronize(g_prof_events[i + 1]));
-        HIP_TRY(hipEventElapsedTime(&ms, g_prof_events[i], g_prof_events[i + 1]));
-        sum += ms;
-        ++n;
-    }
-    *n_launches = n;
-    *total_ms = sum;
-    g_prof_used = 0;
-    return NGCF_OK;
 }
 
 namespace {
@@ -463,16 +417,10 @@ static bool fork_ready(hipStream_t stream)
 }
 
 template <int VEC, int LPR, int CH, int U>
-int launch_spmm(const SpmmArgs &a)
+int launch_spmm(const SpmmArgs &a, const ngcf_csr::SegSet &s)    // s: the cut rows this launch produces
 {
     const ngcf_csr *c = a.c;
-    // cut rows: all of them, or (beside the swept parts) those of the groups the parts do not cover
-    const int64_t n_seg = a.with_swept ? c->swept.out.n_seg : c->n_seg, n_heavy = a.with_swept ? c->swept.out.n_heavy : c->n_heavy;
-    const int32_t *seg_row = a.with_swept ? c->swept.out.seg_row : c->seg_row;
-    const int64_t *seg_begin = a.with_swept ? c->swept.out.seg_begin : c->seg_begin;
-    const int32_t *heavy_row = a.with_swept ? c->swept.out.heavy_row : c->heavy_row;
-    const int64_t *heavy_seg_ptr = a.with_swept ? c->swept.out.heavy_seg_ptr : c->heavy_seg_ptr;
-    const int64_t seg_blocks = (n_seg + 3) / 4;
+    const int64_t seg_blocks = (s.n_seg + 3) / 4;
     // d-slicing of the sliceable row groups needs 16-byte slices of 32 floats
     const bool can_slice = VEC == 4 && a.d % 32 == 0 && a.d >= 64 && c->mode != 1 && !ngcf_opts().no_slicing;
     // table-in-LDS kernel for the groups that gather from a few hundred rows: 16-byte pieces of 64-float slices
@@ -491,7 +439,7 @@ int launch_spmm(const SpmmArgs &a)
         HIP_TRY(hipStreamWaitEvent(g_fork.side, g_fork.ev_fork, 0));
         gs = g_fork.side;
         spmm_kernel<VEC, LPR, CH, U><<<dim3((unsigned)seg_blocks), 256, 0, a.stream>>>(
-            c->rowptr, c->colidx, c->vals, 0, 0, seg_row, seg_begin, n_seg, seg_blocks, c->seg_len, a.E, a.ldE, a.d, a.out, a.ldo,
+            c->rowptr, c->colidx, c->vals, 0, 0, s.seg_row, s.seg_begin, s.n_seg, seg_blocks, c->seg_len, a.E, a.ldE, a.d, a.out, a.ldo,
             a.partial, a.dp, a.dr);
         LAUNCH_CHECK();
         seg_done = true;
@@ -534,15 +482,15 @@ int launch_spmm(const SpmmArgs &a)
         if (blocks >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "spmm: too many rows for one launch");
         if (blocks > 0) {
             spmm_kernel<VEC, LPR, CH, U><<<dim3((unsigned)blocks), 256, 0, gs>>>(
-                c->rowptr, c->colidx, c->vals, rbeg, rend, seg_row, seg_begin, seg_done ? 0 : n_seg, sb, c->seg_len,
+                c->rowptr, c->colidx, c->vals, rbeg, rend, s.seg_row, s.seg_begin, seg_done ? 0 : s.n_seg, sb, c->seg_len,
                 a.E, a.ldE, a.d, a.out, a.ldo, a.partial, a.dp, a.dr);
             LAUNCH_CHECK();
         }
         seg_done = true;
     }
-    if (n_heavy > 0) {
-        const int64_t fb = (n_heavy + 3) / 4;
-        spmm_fixup_kernel<VEC><<<dim3((unsigned)fb), 256, 0, a.stream>>>(heavy_row, heavy_seg_ptr, n_heavy, a.partial, a.dp, a.d, a.out,
+    if (s.n_heavy > 0) {
+        const int64_t fb = (s.n_heavy + 3) / 4;
+        spmm_fixup_kernel<VEC><<<dim3((unsigned)fb), 256, 0, a.stream>>>(s.heavy_row, s.heavy_seg_ptr, s.n_heavy, a.partial, a.dp, a.d, a.out,
                                                                           a.ldo);
         LAUNCH_CHECK();
     }
@@ -586,9 +534,9 @@ int spmm_dispatch(const ngcf_csr *c, const float *E, int64_t ldE, int d, float *
             if (rc != NGCF_OK) return rc;
             const int tail = d - main;
             if (tail <= 4 && workspace && workspace_bytes >= ngcf_spmm_workspace_bytes(c, d) && !ngcf_opts().no_tail_table) {
-                if (tail == 1) return launch_tail<1>(c, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
-                if (tail == 2) return launch_tail<2>(c, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
-                return launch_tail<4>(c, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
+                if (tail == 1) return launch_tail<1>(c, c->seg, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
+                if (tail == 2) return launch_tail<2>(c, c->seg, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
+                return launch_tail<4>(c, c->seg, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
             }
             return spmm_dispatch(c, E + main, ldE, tail, out + main, ldo, workspace, workspace_bytes, stream, dr);
         }
@@ -596,8 +544,16 @@ int spmm_dispatch(const ngcf_csr *c, const float *E, int64_t ldE, int d, float *
     const int dp = (int)align_up(d, 4);
     const bool vec = (d % 4 == 0) && rows_aligned;
     const bool with_swept = vec && swept_usable(c, ldE, d);               // (under edge dropout: the DROP instantiation)
+    // cut rows: all of them, or (beside the swept parts) those of the groups the parts do not cover
+    const ngcf_csr::SegSet *segs = &c->seg;
+    int64_t n_partial = c->seg.n_seg;       // workspace rows: the segments, then the partial rows of the swept parts
+    if (with_swept) {
+        segs = &c->swept.out;
+        n_partial = c->swept.out.n_seg + c->swept.n_partial;
+    }
+    const ngcf_csr::SegSet &s = *segs;
     float *partial = nullptr;
-    if (with_swept ? c->swept.out.n_seg + c->swept.n_partial > 0 : c->n_seg > 0) {
+    if (n_partial > 0) {
         const int64_t need = partial_bytes(c, d);
         if (!workspace || workspace_bytes < need)
             return fail(NGCF_ERR_WORKSPACE, "spmm: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
@@ -610,17 +566,17 @@ int spmm_dispatch(const ngcf_csr *c, const float *E, int64_t ldE, int d, float *
     if (rc != NGCF_OK) return rc;
     if (vec) {
         const int nq = d / 4;
-        if (nq <= 8) rc = launch_spmm<4, 8, 1, 4>(a);
-        else if (nq <= 16) rc = launch_spmm<4, 16, 1, 8>(a);
-        else if (nq <= 32) rc = launch_spmm<4, 32, 1, 8>(a);
-        else if (nq <= 64) rc = launch_spmm<4, 64, 1, 8>(a);
-        else if (nq <= 128) rc = launch_spmm<4, 64, 2, 4>(a);
-        else rc = launch_spmm<4, 64, 3, 2>(a);
-    } else if (d <= 8) rc = launch_spmm<1, 8, 1, 8>(a);       // narrow tail panels: 8 gathered rows per wave instruction
-    else if (d <= 64) rc = launch_spmm<1, 64, 1, 8>(a);
-    else if (d <= 128) rc = launch_spmm<1, 64, 2, 4>(a);
-    else if (d <= 256) rc = launch_spmm<1, 64, 4, 2>(a);
-    else rc = launch_spmm<1, 64, 8, 1>(a);
+        if (nq <= 8) rc = launch_spmm<4, 8, 1, 4>(a, s);
+        else if (nq <= 16) rc = launch_spmm<4, 16, 1, 8>(a, s);
+        else if (nq <= 32) rc = launch_spmm<4, 32, 1, 8>(a, s);
+        else if (nq <= 64) rc = launch_spmm<4, 64, 1, 8>(a, s);
+        else if (nq <= 128) rc = launch_spmm<4, 64, 2, 4>(a, s);
+        else rc = launch_spmm<4, 64, 3, 2>(a, s);
+    } else if (d <= 8) rc = launch_spmm<1, 8, 1, 8>(a, s);       // narrow tail panels: 8 gathered rows per wave instruction
+    else if (d <= 64) rc = launch_spmm<1, 64, 1, 8>(a, s);
+    else if (d <= 128) rc = launch_spmm<1, 64, 2, 4>(a, s);
+    else if (d <= 256) rc = launch_spmm<1, 64, 4, 2>(a, s);
+    else rc = launch_spmm<1, 64, 8, 1>(a, s);
     prof_mark(stream, 1);
     return rc;
 }

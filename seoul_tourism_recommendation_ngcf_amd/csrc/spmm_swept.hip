@@ -1,4 +1,4 @@
-// spmm_swept.hip - the L2-swept SpMM for long-lived matrices: host plan + persistent kernel.
+// spmm_swept.hip - the L2-swept SpMM for long-lived matrices: the persistent kernel, its launch, and the host plan (swept_plan.h) on the device.
 //
 // Same product LE = L.E (NGCF.py:130).  Why: on a graph without locality the row-wise kernels miss L2 on most
 // gathered rows and run at the chip's L2-miss rate (~8 TB/s of gathered bytes); rows served from L2 arrive 2-3x
@@ -23,39 +23,12 @@
 // Rows cut into pieces leave partial sums in the workspace; spmm_fixup_kernel adds them in piece order.
 // Measured on C3 (1x MI355X, d=128): item rows 1.83-1.93 ms vs 3.5 ms row-wise, user rows 1.84-1.94 vs 2.46 ms d-sliced.
 #include "spmm_device.h"
+#include "swept_plan.h"      // the host plan and the geometry constants of a part
+
+using namespace swept_plan;
 
 namespace {
-// Geometry of a part: LPE lanes share one entry, i.e. a slice of SW = 4 LPE floats of the gathered row per wave instruction;
-// EPR = 64 / LPE entries per round, 16 rounds per chunk.  LPE = 16: 64-float (256-byte) slices, four entries per round, 576
-// accumulator rows per workgroup.  LPE = 32 (r03): 128-float (512-byte) slices - at d = 128 the whole row in ONE sweep, two entries
-// per round, 288 accumulator rows per workgroup: twice the row passes, half the slices, every stored entry read once instead of
-// twice, four consecutive 128-byte lines per gather instead of two.
-constexpr int kLdsBytes = 36 * 16 * 256;  // accumulator bytes per workgroup (144 KiB of LDS, + one spare row per wave)
-constexpr int kSweptWGs = 256;            // one workgroup per CU
 constexpr int kRing = 8;                  // rotating sweep counters per XCD
-constexpr int kRowBits = 24;              // e_pack: column in bits 0..23, local row in bits 24..30
-constexpr int kColMask = (1 << kRowBits) - 1;
-
-template <typename F>
-void parallel_for(int64_t n, F &&fn, int64_t min_parallel = 64)
-{
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt > 16) nt = 16;
-    if (nt < 1) nt = 1;
-    if ((int64_t)nt > n) nt = (unsigned)std::max<int64_t>(n, 1);
-    if (n < min_parallel || nt == 1) {
-        fn(0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    const int64_t chunk = (n + nt - 1) / nt;
-    for (unsigned t = 0; t < nt; ++t) {
-        const int64_t lo = t * chunk, hi = std::min<int64_t>(n, lo + chunk);
-        if (lo >= hi) break;
-        th.emplace_back([&fn, lo, hi]() { fn(lo, hi); });
-    }
-    for (auto &t : th) t.join();
-}
 
 void free_part(ngcf_csr::Swept::Part &p)
 {
@@ -69,384 +42,59 @@ void free_part(ngcf_csr::Swept::Part &p)
     p = ngcf_csr::Swept::Part();
 }
 
-void free_segset(ngcf_csr::SegSet &s)
-{
-    if (s.seg_row) (void)hipFree(s.seg_row);
-    if (s.seg_begin) (void)hipFree(s.seg_begin);
-    if (s.heavy_row) (void)hipFree(s.heavy_row);
-    if (s.heavy_seg_ptr) (void)hipFree(s.heavy_seg_ptr);
-    s = ngcf_csr::SegSet();
-}
-
-template <typename T>
-int upload(T **dptr, const std::vector<T> &h, hipStream_t stream)
-{
-    HIP_TRY(hipMalloc(dptr, sizeof(T) * std::max<size_t>(h.size(), 1)));
-    if (!h.empty()) HIP_TRY(hipMemcpyAsync(*dptr, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, stream));
-    return NGCF_OK;
-}
-
-// entries begin+off, begin+off+step, ... < end of one row.  A long row is dealt out to its pieces round-robin so
-// that every piece covers the whole column range evenly (a contiguous cut would pile a piece's work into a few windows)
-struct Piece {
-    int64_t row;            // >= 0 row of the part, < 0 partial row -1-p of the part
-    int64_t begin, end, count;
-    int32_t off, step;
-    int64_t src;            // the row of the part its entries come from (== row when the row is not cut)
-};
-
-// Plan of the rows [row_lo, row_hi).  Leaves part.waves == 0 when the part is not worth it (mode 3) or the shape does
-// not fit the entry encoding.
+// Plan of the rows of one group (swept_plan.h: plan_part) on the device.  Leaves part.waves == 0 when the part is not worth
+// it (mode 3) or the shape does not fit the entry encoding.
 int build_part(const ngcf_csr *c, const ngcf_csr::RowGroup &grp, bool force, hipStream_t stream, ngcf_csr::Swept::Part &part, int LPE)
 {
-    const int kSW = LPE * 4, kEPR = 64 / LPE, kLdsRows = kLdsBytes / (kSW * 4);        // the part's geometry (see the top of the file)
-    const int64_t row_lo = grp.begin, row_hi = grp.end, n = row_hi - row_lo;
-    const int32_t col_lo = grp.col_lo, col_hi = grp.col_hi;
-    if (n <= 0 || col_hi < col_lo) return NGCF_OK;
-    if (col_hi > kColMask) return NGCF_OK;                           // column does not fit the packed entry
+    const NgcfOptions &o = ngcf_opts();
+    Params prm;
+    prm.lpe = LPE;
+    prm.cut = o.swept_cut;
+    prm.moments = !o.swept_no_moments;
+    prm.order_rows = o.swept_order_rows != 0;
+    prm.window_kb = o.swept_window_kb;
+    prm.force = force;
+    prm.debug = o.swept_debug != 0;
+    const int64_t n = grp.end - grp.begin;
+    if (n <= 0 || grp.col_hi < grp.col_lo) return NGCF_OK;           // no rows, no entries
     std::vector<int64_t> rp((size_t)n + 1);
-    HIP_TRY(hipMemcpyAsync(rp.data(), c->rowptr + row_lo, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(rp.data(), c->rowptr + grp.begin, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const int64_t e0 = rp[0], nnz = rp[(size_t)n] - e0;
-    if (nnz <= 0) return NGCF_OK;
-    if (!force && nnz < ((int64_t)1 << 22)) return NGCF_OK;          // small products are launch-bound, not L2-bound
-    // workgroup shape: 16 waves x 36 rows.  (Round 1 ran the parts that need three or more row passes as 8 x 72: fewer,
-    // longer wave tasks fetched 30 % less.  With the lag-driven wave priorities of the kernel 16 waves are faster there
-    // too - C3 user rows 1.60 vs 1.93 ms, profiles/r02_swept_lab.txt.)
-    const int64_t cap = (int64_t)kSweptWGs * kLdsRows;               // output rows resident in LDS at a time
-    const int waves = 16;
-    const int RW = kLdsRows / waves;
-    const int64_t n_wave_slots = (int64_t)kSweptWGs * waves;
-    if (!force) {
-        // expected uses of a fetched table row inside one XCD during one sweep: its column degree times the share
-        // of the output rows that the XCD holds in LDS.  Below ~3 the sweep costs more than the misses it saves;
-        // a table slice that fits the L2s anyway needs no sweep either.
-        const double span = (double)col_hi - col_lo + 1;
-        const double reuse = (double)nnz / span * std::min(1.0, (double)(cap / 8) / (double)n);
-        if (reuse < 3.0 || span * kSW * 4 < (double)(8 << 20)) return NGCF_OK;
-    }
+    if (declined(n, nnz, grp.col_lo, grp.col_hi, prm)) return NGCF_OK;
     std::vector<int32_t> col((size_t)nnz);    // only now the entries come to the host
     std::vector<float> val((size_t)nnz);
     HIP_TRY(hipMemcpyAsync(col.data(), c->colidx + e0, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(val.data(), c->vals + e0, sizeof(float) * (size_t)nnz, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (auto &x : rp) x -= e0;
-    // 1) pieces and wave tasks: all tasks get the same number of entries and at most RW rows
-    int64_t n_rowpass = std::max<int64_t>(1, (n + cap - 1) / cap), n_tasks = 0, T = 0, n_partial = 0;
-    std::vector<Piece> pieces;
-    std::vector<int32_t> heavy_row;
-    std::vector<int64_t> heavy_ptr;
-    for (;; ++n_rowpass) {
-        n_tasks = n_rowpass * n_wave_slots;
-        T = std::max<int64_t>(64, (nnz + n_tasks - 1) / n_tasks);
-        const int64_t Tp = std::max<int64_t>(64, T / std::max(2, ngcf_opts().swept_cut));   // rows are cut well below a task's share
-        pieces.clear();
-        heavy_row.clear();
-        heavy_ptr.assign(1, 0);
-        n_partial = 0;
-        for (int64_t r = 0; r < n; ++r) {
-            const int64_t b = rp[(size_t)r], e = rp[(size_t)r + 1], len = e - b;
-            if (len <= Tp) {
-                pieces.push_back({r, b, e, len, 0, 1, r});
-            } else {
-                const int64_t k = (len + Tp - 1) / Tp;
-                heavy_row.push_back((int32_t)(row_lo + r));
-                for (int64_t j = 0; j < k; ++j) pieces.push_back({-1 - n_partial++, b, e, (len - j + k - 1) / k, (int32_t)j, (int32_t)k, r});
-                heavy_ptr.push_back(n_partial);
-            }
-        }
-        if ((int64_t)pieces.size() <= n_tasks * RW) break;
-        if (n_rowpass > (int64_t)1 << 20) return fail(NGCF_ERR_ARG, "swept plan: cannot place %zu pieces", pieces.size());
-    }
-    if (n_tasks * RW >= (int64_t)1 << 31 || n_partial >= ((int64_t)1 << 31) - 2) return fail(NGCF_ERR_ARG, "swept plan: matrix too large");
-    // Dealing.  Level by level, heaviest piece -> lightest task (every task gets at most one piece per level): all tasks end
-    // within +-2 % of the same entry count.  That alone leaves WHERE in the table a task's entries lie to chance, and the
-    // sweep pays for it: a wave whose rows happen to hold few entries in the first half of the table runs ahead of the
-    // others by (missing entries) / (entries per column) - on the C3 item rows sigma = 1.1 MiB of table slice, 4 096 waves
-    // spread over ~10 MiB against a 4 MiB L2 (measured: profiles/r02_swept_trace.txt; a table
-    // row is then fetched again for the late waves).  So inside buckets of kDealBucket neighbouring (task, piece) pairs of a
-    // level - equal loads to within a fraction of a percent - the pairing is chosen to cancel the low-order cosine moments
-    // of every task's entry positions (position = share of all entries left of the column, so that a uniform sweep is the
-    // target whatever the column popularity): m_k = sum over entries of cos(k pi x), k = 1..kDealK, are the sine-series
-    // coefficients of the task's cumulative-count deviation; the greedy gives each piece to the task of its bucket whose
-    // moments it cancels best.  Simulated on the C3 item rows: spread (p5..p95) 2.9 -> 0.9 MiB, worst wave 4.6 -> 2.0 MiB.
-    constexpr int kDealK = 8, kDealBucket = 256;
-    const bool balance_moments = !ngcf_opts().swept_no_moments;
-    std::vector<float> mom;                                          // [piece][kDealK]
-    if (balance_moments) {
-        const int64_t span = (int64_t)col_hi - col_lo + 1;
-        std::vector<int64_t> ccnt((size_t)span + 1, 0);
-        for (int64_t x = 0; x < nnz; ++x) ccnt[(size_t)(col[(size_t)x] - col_lo) + 1]++;
-        for (int64_t c = 0; c < span; ++c) ccnt[(size_t)c + 1] += ccnt[(size_t)c];
-        std::vector<float> ctab((size_t)span * kDealK);
-        parallel_for(span, [&](int64_t lo, int64_t hi) {
-            for (int64_t c = lo; c < hi; ++c) {
-                const double xpos = (0.5 * (double)(ccnt[(size_t)c] + ccnt[(size_t)c + 1])) / (double)nnz;
-                for (int k = 0; k < kDealK; ++k) ctab[(size_t)c * kDealK + k] = (float)cos((k + 1) * 3.14159265358979323846 * xpos);
-            }
-        });
-        mom.assign(pieces.size() * kDealK, 0.f);
-        parallel_for((int64_t)pieces.size(), [&](int64_t lo, int64_t hi) {
-            for (int64_t pi = lo; pi < hi; ++pi) {
-                const Piece &pc = pieces[(size_t)pi];
-                float acc[kDealK] = {0};
-                for (int64_t x = pc.begin + pc.off; x < pc.end; x += pc.step) {
-                    const float *t = &ctab[(size_t)(col[(size_t)x] - col_lo) * kDealK];
-                    for (int k = 0; k < kDealK; ++k) acc[k] += t[k];
-                }
-                for (int k = 0; k < kDealK; ++k) mom[(size_t)pi * kDealK + k] = acc[k];
-            }
-        });
-    }
-    std::vector<int64_t> order(pieces.size());
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pieces[(size_t)a].count > pieces[(size_t)b].count; });
-    std::vector<int64_t> load((size_t)n_tasks, 0), by_load((size_t)n_tasks);
-    std::vector<float> tmom(balance_moments ? (size_t)n_tasks * kDealK : 0, 0.f);   // moments of every task so far
-    std::vector<int64_t> task_piece((size_t)(n_tasks * RW), -1);    // [task][local row] -> piece
-    for (int64_t lvl = 0; lvl * n_tasks < (int64_t)pieces.size(); ++lvl) {
-        std::iota(by_load.begin(), by_load.end(), 0);
-        std::stable_sort(by_load.begin(), by_load.end(), [&](int64_t a, int64_t b) { return load[(size_t)a] < load[(size_t)b]; });
-        const int64_t lo = lvl * n_tasks, hi = std::min<int64_t>((int64_t)pieces.size(), lo + n_tasks);
-        if (!balance_moments) {
-            for (int64_t i = lo; i < hi; ++i) {
-                const int64_t t = by_load[(size_t)(i - lo)];
-                task_piece[(size_t)(t * RW + lvl)] = order[(size_t)i];
-                load[(size_t)t] += pieces[(size_t)order[(size_t)i]].count;
-            }
-            continue;
-        }
-        const int64_t n_buckets = (hi - lo + kDealBucket - 1) / kDealBucket;
-        parallel_for(n_buckets, [&](int64_t b_lo, int64_t b_hi) {
-            std::vector<int64_t> ps, ts;
-            for (int64_t b = b_lo; b < b_hi; ++b) {
-                const int64_t i0 = lo + b * kDealBucket, i1 = std::min(hi, i0 + kDealBucket);
-                ps.assign(order.begin() + i0, order.begin() + i1);                      // pieces of the bucket ...
-                ts.assign(by_load.begin() + (i0 - lo), by_load.begin() + (i1 - lo));   // ... and its tasks
-                // pieces with the largest moments choose first
-                std::stable_sort(ps.begin(), ps.end(), [&](int64_t a, int64_t c) {
-                    float na = 0.f, nc = 0.f;
-                    for (int k = 0; k < kDealK; ++k) {
-                        na += fabsf(mom[(size_t)a * kDealK + k]);
-                        nc += fabsf(mom[(size_t)c * kDealK + k]);
-                    }
-                    return na > nc;
-                });
-                for (const int64_t pi : ps) {
-                    const float *pm = &mom[(size_t)pi * kDealK];
-                    size_t best = 0;
-                    float best_cost = 3.4e38f;
-                    for (size_t j = 0; j < ts.size(); ++j) {
-                        const float *tm = &tmom[(size_t)ts[j] * kDealK];
-                        float cost = 0.f;
-                        for (int k = 0; k < kDealK; ++k) cost += (tm[k] + pm[k]) * (tm[k] + pm[k]);
-                        if (cost < best_cost) {
-                            best_cost = cost;
-                            best = j;
-                        }
-                    }
-                    const int64_t t = ts[best];
-                    ts[best] = ts.back();
-                    ts.pop_back();
-                    task_piece[(size_t)(t * RW + lvl)] = pi;
-                    load[(size_t)t] += pieces[(size_t)pi].count;
-                    for (int k = 0; k < kDealK; ++k) tmom[(size_t)t * kDealK + k] += pm[k];
-                }
-            }
-        }, 2);
-    }
-    // 2) column windows and the slot layout of every (task, window) bucket
-    // 8 MiB windows; 16 MiB when the table slice is 128 MiB or more (C3 item rows, lead 2: 1.58 vs 1.61 ms; on the 25 MiB
-    // table of the user rows 8 MiB: 1.53 vs 1.84 ms)
-    int64_t win_kb = ngcf_opts().swept_window_kb > 0 ? ngcf_opts().swept_window_kb
-                                                     : (((int64_t)col_hi - col_lo + 1) * kSW * 4 >= ((int64_t)128 << 20) ? 16384 : 8192);
-    if (win_kb < 16) win_kb = 16;
-    const int32_t win_cols = (int32_t)std::max<int64_t>(64, win_kb * 1024 / (kSW * 4));
-    const int64_t n_win = ((int64_t)col_hi - col_lo) / win_cols + 1;
-    if (n_tasks * n_win >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "swept plan: too many windows");
-    std::vector<int64_t> tptr((size_t)(n_tasks * n_win) + 1, 0);
-    auto bucket_hist = [&](int64_t t, std::vector<int32_t> &hist) {   // entries per (window, local row) of task t
-        std::fill(hist.begin(), hist.end(), 0);
-        for (int lr = 0; lr < RW; ++lr) {
-            const int64_t pi = task_piece[(size_t)(t * RW + lr)];
-            if (pi < 0) continue;
-            const Piece &pc = pieces[(size_t)pi];
-            for (int64_t x = pc.begin + pc.off; x < pc.end; x += pc.step)
-                hist[(size_t)((col[(size_t)x] - col_lo) / win_cols) * RW + lr]++;
-        }
-    };
-    // Layout of a (task, window) bucket, two ways (NGCF_SWEPT_ORDER):
-    //  "rows"  : R = max(longest row, ceil(entries / 4)) rounds; row after row is laid down the rounds (wrap-around rule)
-    //  "cols"  : entries sorted by column, rounds filled greedily in that order with entries of distinct rows (an entry
-    //            whose row is already in the round waits for the next one): the wave walks the window left to right
-    // Either way the entries of one row never share a round (they are read-modify-written in LDS without atomics).
-    const bool by_cols = !ngcf_opts().swept_order_rows;   // default: cols
-    struct Ent { int32_t col, lr; float v; };
-    // schedule of one bucket: slot list (index into `ents`, -1 = empty), a multiple of kEPR long
-    auto schedule_cols = [&](std::vector<Ent> &ents, std::vector<int32_t> &slots, std::vector<char> &done) {
-        std::sort(ents.begin(), ents.end(), [](const Ent &x, const Ent &y) { return x.col != y.col ? x.col < y.col : x.lr < y.lr; });
-        slots.clear();
-        done.assign(ents.size(), 0);
-        size_t first = 0, left = ents.size();
-        while (left > 0) {
-            uint64_t in_round[2] = {0, 0};
-            int taken = 0;
-            while (first < ents.size() && done[first]) ++first;
-            for (size_t i = first; i < ents.size() && taken < kEPR && i < first + 512; ++i) {
-                if (done[i]) continue;
-                const int lr = ents[i].lr;
-                if (in_round[lr >> 6] >> (lr & 63) & 1) continue;
-                in_round[lr >> 6] |= (uint64_t)1 << (lr & 63);
-                done[i] = 1;
-                slots.push_back((int32_t)i);
-                ++taken;
-                --left;
-            }
-            for (; taken < kEPR; ++taken) slots.push_back(-1);
-        }
-    };
-    auto gather_bucket = [&](int64_t t, std::vector<std::vector<Ent>> &per_win) {
-        for (auto &v : per_win) v.clear();
-        for (int lr = 0; lr < RW; ++lr) {
-            const int64_t pi = task_piece[(size_t)(t * RW + lr)];
-            if (pi < 0) continue;
-            const Piece &pc = pieces[(size_t)pi];
-            for (int64_t x = pc.begin + pc.off; x < pc.end; x += pc.step)
-                per_win[(size_t)((col[(size_t)x] - col_lo) / win_cols)].push_back({col[(size_t)x], lr, val[(size_t)x]});
-        }
-    };
-    parallel_for(n_tasks, [&](int64_t lo, int64_t hi) {
-        std::vector<int32_t> hist((size_t)n_win * RW), slots;
-        std::vector<std::vector<Ent>> per_win(by_cols ? (size_t)n_win : 0);
-        std::vector<char> done;
-        for (int64_t t = lo; t < hi; ++t) {
-            if (by_cols) {
-                gather_bucket(t, per_win);
-                for (int64_t w = 0; w < n_win; ++w) {
-                    schedule_cols(per_win[(size_t)w], slots, done);
-                    tptr[(size_t)(t * n_win + w) + 1] = (int64_t)slots.size();
-                }
-                continue;
-            }
-            bucket_hist(t, hist);
-            for (int64_t w = 0; w < n_win; ++w) {
-                int64_t total = 0, longest = 0;
-                for (int lr = 0; lr < RW; ++lr) {
-                    total += hist[(size_t)w * RW + lr];
-                    longest = std::max<int64_t>(longest, hist[(size_t)w * RW + lr]);
-                }
-                tptr[(size_t)(t * n_win + w) + 1] = std::max(longest, (total + kEPR - 1) / kEPR) * kEPR;
-            }
-        }
-    });
-    for (size_t i = 1; i < tptr.size(); ++i) tptr[i] += tptr[i - 1];
-    const int64_t n_slots = tptr.back();
-    // empty slots add 0 x (a row of their own window, an L2 hit) to the wave's spare accumulator row RW
-    std::vector<int32_t> e_pack((size_t)std::max<int64_t>(n_slots, 1), -1);
-    std::vector<float> e_val((size_t)std::max<int64_t>(n_slots, 1), 0.f);
-    parallel_for(n_tasks, [&](int64_t lo, int64_t hi) {
-        std::vector<int32_t> hist((size_t)n_win * RW), slots;
-        std::vector<int64_t> rounds((size_t)n_win);
-        std::vector<std::vector<Ent>> per_win(by_cols ? (size_t)n_win : 0);
-        std::vector<char> done;
-        for (int64_t t = lo; t < hi; ++t) {
-            if (by_cols) {
-                gather_bucket(t, per_win);
-                for (int64_t w = 0; w < n_win; ++w) {
-                    std::vector<Ent> &ents = per_win[(size_t)w];
-                    schedule_cols(ents, slots, done);
-                    const int64_t b0 = tptr[(size_t)(t * n_win + w)];
-                    int32_t near_col = ents.empty() ? 0 : ents[0].col;
-                    for (size_t i = 0; i < slots.size(); ++i) {
-                        if (slots[i] >= 0) {
-                            const Ent &e = ents[(size_t)slots[i]];
-                            near_col = e.col;
-                            e_pack[(size_t)b0 + i] = (int32_t)((uint32_t)e.lr << kRowBits) | e.col;
-                            e_val[(size_t)b0 + i] = e.v;
-                        } else {
-                            e_pack[(size_t)b0 + i] = (int32_t)((uint32_t)RW << kRowBits) | near_col;   // spare row, a row just gathered
-                        }
-                    }
-                }
-                continue;
-            }
-            bucket_hist(t, hist);
-            for (int64_t w = 0; w < n_win; ++w) {                   // hist -> first list position of every row in its bucket
-                rounds[(size_t)w] = (tptr[(size_t)(t * n_win + w) + 1] - tptr[(size_t)(t * n_win + w)]) / kEPR;
-                int32_t run = 0;
-                for (int lr = 0; lr < RW; ++lr) {
-                    const int32_t cnt = hist[(size_t)w * RW + lr];
-                    hist[(size_t)w * RW + lr] = run;
-                    run += cnt;
-                }
-            }
-            for (int lr = 0; lr < RW; ++lr) {
-                const int64_t pi = task_piece[(size_t)(t * RW + lr)];
-                if (pi < 0) continue;
-                const Piece &pc = pieces[(size_t)pi];
-                for (int64_t x = pc.begin + pc.off; x < pc.end; x += pc.step) {
-                    const int64_t w = (col[(size_t)x] - col_lo) / win_cols;
-                    const int64_t k = hist[(size_t)w * RW + lr]++, R = rounds[(size_t)w];
-                    const int64_t pos = tptr[(size_t)(t * n_win + w)] + (k % R) * kEPR + k / R;
-                    e_pack[(size_t)pos] = (int32_t)((uint32_t)lr << kRowBits) | col[(size_t)x];
-                    e_val[(size_t)pos] = val[(size_t)x];
-                }
-            }
-            for (int64_t w = 0; w < n_win; ++w) {
-                const int64_t b0 = tptr[(size_t)(t * n_win + w)], b1 = tptr[(size_t)(t * n_win + w) + 1];
-                if (b0 == b1) continue;
-                const int32_t spare = (int32_t)((uint32_t)RW << kRowBits) | (e_pack[(size_t)b0] & kColMask);   // slot 0 is never empty
-                for (int64_t x = b0; x < b1; ++x)
-                    if (e_pack[(size_t)x] < 0) e_pack[(size_t)x] = spare;
-            }
-        }
-    });
-    std::vector<int32_t> dst((size_t)(n_tasks * RW), -1), prow((size_t)(n_tasks * RW), 0);
-    for (size_t i = 0; i < dst.size(); ++i) {
-        if (task_piece[i] < 0) continue;
-        const int64_t r = pieces[(size_t)task_piece[i]].row;
-        dst[i] = r >= 0 ? (int32_t)(row_lo + r) : (int32_t)(-2 - (-1 - r));
-        prow[i] = (int32_t)(row_lo + pieces[(size_t)task_piece[i]].src);   // the matrix row behind every accumulator row (edge dropout key)
-    }
-    if (ngcf_opts().swept_debug) {
-        int64_t mx = 0, mn = INT64_MAX;
-        for (int64_t t = 0; t < n_tasks; ++t) {
-            const int64_t s = tptr[(size_t)((t + 1) * n_win)] - tptr[(size_t)(t * n_win)];
-            mx = std::max(mx, s);
-            mn = std::min(mn, s);
-        }
-        fprintf(stderr, "[swept plan] rows [%lld, %lld) nnz %lld cols [%d, %d]: %d waves x %d rows, %lld row passes, %lld windows x %d "
-                        "cols, T %lld, pieces %zu (partial %lld), slots %lld (+%.1f%%), per task %lld..%lld\n",
-                (long long)row_lo, (long long)row_hi, (long long)nnz, col_lo, col_hi, waves, RW, (long long)n_rowpass, (long long)n_win,
-                win_cols, (long long)T, pieces.size(), (long long)n_partial, (long long)n_slots,
-                100.0 * (double)(n_slots - nnz) / (double)nnz, (long long)mn, (long long)mx);
-    }
-    // 3) upload
-    part.row_lo = row_lo;
-    part.row_hi = row_hi;
-    part.rows_per_wave = RW;
+    const PartPlan plan = plan_part(rp.data(), n, col.data(), val.data(), grp.begin, grp.col_lo, grp.col_hi, prm);
+    if (!plan.error.empty()) return fail(NGCF_ERR_ARG, "%s", plan.error.c_str());
+    part.row_lo = grp.begin;
+    part.row_hi = grp.end;
+    part.rows_per_wave = plan.rows_per_wave;
     part.lpe = LPE;
-    part.n_rowpass = (int32_t)n_rowpass;
-    part.n_win = (int32_t)n_win;
-    part.win_cols = win_cols;
-    part.col_lo = col_lo;
-    part.col_hi = col_hi;
-    part.n_slots = n_slots;
-    part.n_partial = n_partial;
-    part.n_heavy = (int64_t)heavy_row.size();
-    int rc = upload(&part.tptr, tptr, stream);
-    if (rc == NGCF_OK) rc = upload(&part.e_pack, e_pack, stream);
-    if (rc == NGCF_OK) rc = upload(&part.e_val, e_val, stream);
-    if (rc == NGCF_OK) rc = upload(&part.dst, dst, stream);
-    if (rc == NGCF_OK) rc = upload(&part.prow, prow, stream);
-    if (rc == NGCF_OK && part.n_heavy > 0) rc = upload(&part.heavy_row, heavy_row, stream);
-    if (rc == NGCF_OK && part.n_heavy > 0) rc = upload(&part.heavy_seg_ptr, heavy_ptr, stream);
+    part.n_rowpass = plan.n_rowpass;
+    part.n_win = plan.n_win;
+    part.win_cols = plan.win_cols;
+    part.col_lo = grp.col_lo;
+    part.col_hi = grp.col_hi;
+    part.n_slots = plan.n_slots;
+    part.n_partial = plan.n_partial;
+    part.n_heavy = (int64_t)plan.heavy_row.size();
+    int rc = upload(&part.tptr, plan.tptr, stream);
+    if (rc == NGCF_OK) rc = upload(&part.e_pack, plan.e_pack, stream);
+    if (rc == NGCF_OK) rc = upload(&part.e_val, plan.e_val, stream);
+    if (rc == NGCF_OK) rc = upload(&part.dst, plan.dst, stream);
+    if (rc == NGCF_OK) rc = upload(&part.prow, plan.prow, stream);
+    if (rc == NGCF_OK && part.n_heavy > 0) rc = upload(&part.heavy_row, plan.heavy_row, stream);
+    if (rc == NGCF_OK && part.n_heavy > 0) rc = upload(&part.heavy_seg_ptr, plan.heavy_ptr, stream);
     if (rc == NGCF_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NGCF_ERR_HIP, "swept plan: upload failed");
     if (rc != NGCF_OK) {
         free_part(part);
         return rc;
     }
-    part.waves = waves;
+    part.waves = plan.waves;
     return NGCF_OK;
 }
 }  // namespace
@@ -500,34 +148,16 @@ int build_swept_plan(ngcf_csr *c, hipStream_t stream)
     std::vector<int64_t> rp((size_t)c->n_rows + 1);
     HIP_TRY(hipMemcpyAsync(rp.data(), c->rowptr, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    std::vector<int32_t> seg_row, heavy_row;
-    std::vector<int64_t> seg_begin, heavy_ptr(1, 0);
-    for (size_t g = 0; g < c->groups.size(); ++g) {
-        if (w.group_swept[g]) continue;
-        for (int64_t r = c->groups[g].begin; r < c->groups[g].end; ++r) {
-            if (rp[(size_t)r + 1] - rp[(size_t)r] <= c->seg_len) continue;
-            heavy_row.push_back((int32_t)r);
-            for (int64_t b = rp[(size_t)r]; b < rp[(size_t)r + 1]; b += c->seg_len) {
-                seg_row.push_back((int32_t)r);
-                seg_begin.push_back(b);
-            }
-            heavy_ptr.push_back((int64_t)seg_row.size());
-        }
-    }
-    w.out.n_seg = (int64_t)seg_row.size();
-    w.out.n_heavy = (int64_t)heavy_row.size();
+    std::vector<std::pair<int64_t, int64_t>> rest;     // the groups no part covers
+    for (size_t g = 0; g < c->groups.size(); ++g)
+        if (!w.group_swept[g]) rest.push_back({c->groups[g].begin, c->groups[g].end});
+    const HostSegs segs = cut_rows(rp, rest, c->seg_len);     // (alive until the stream is synchronised below)
+    int rc = upload_segset(w.out, segs, stream);
     int64_t base = w.out.n_seg;
     for (auto &p : w.parts) {
         p.partial_base = base;
         base += p.n_partial;
         w.n_partial += p.n_partial;
-    }
-    int rc = NGCF_OK;
-    if (w.out.n_seg > 0) {
-        rc = upload(&w.out.seg_row, seg_row, stream);
-        if (rc == NGCF_OK) rc = upload(&w.out.seg_begin, seg_begin, stream);
-        if (rc == NGCF_OK) rc = upload(&w.out.heavy_row, heavy_row, stream);
-        if (rc == NGCF_OK) rc = upload(&w.out.heavy_seg_ptr, heavy_ptr, stream);
     }
     if (rc == NGCF_OK && (hipMalloc(&w.barrier, sizeof(uint32_t) * 32 * 8 * 4) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess))
         rc = fail(NGCF_ERR_HIP, "swept plan: allocation failed");

@@ -361,13 +361,13 @@ extern "C" int ngcf_spmm_t_rows_f32(const ngcf_csr_t *c, const int32_t *slot, co
     if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(NGCF_ERR_ARG, "spmm_t_rows: drop_p=%f not in [0,1)", drop_p);
     EdgeDrop dr{drop_p > 0.f ? n_seeds : 0, (uint32_t)((double)drop_p * 4294967296.0), {0, 0, 0, 0}, 1};   // the CSR walked is L^T
     for (int q = 0; q < n_seeds; ++q) dr.seed[q] = seeds[q];
-    const int64_t seg_blocks = (c->n_seg + 3) / 4, row_blocks = (c->n_rows + 3) / 4;
+    const int64_t seg_blocks = (c->seg.n_seg + 3) / 4, row_blocks = (c->n_rows + 3) / 4;
     if (seg_blocks + row_blocks >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "spmm_t_rows: too many rows for one launch");
     // r04: the membership bitmap of the R rows in LDS (see spmm_t_rows_bm_kernel) where it fits (N / 8 bytes + 21 KB of hit lists <= 160 KB: N <= 1.13 M) and the matrix
     // is large enough for a persistent grid to pay; it lives behind the partial sums in the workspace
     const int64_t n_slot = std::max(c->n_cols, c->n_rows);      // (square in every use: the slot table covers rows and columns)
     const int64_t n_words = (n_slot + 127) / 128 * 4;             // 32-bit words, a multiple of 4
-    const int64_t part_bytes = c->n_seg > 0 ? align_up(c->n_seg * align_up(std::min(d, 512), 4) * (int64_t)sizeof(float), 256) + 256 : 256;
+    const int64_t part_bytes = c->seg.n_seg > 0 ? align_up(c->seg.n_seg * align_up(std::min(d, 512), 4) * (int64_t)sizeof(float), 256) + 256 : 256;
     uint32_t *bitmap = nullptr;
     unsigned long long *counters = nullptr;
     if (ngcf_opts().t_rows_bitmap && c->n_rows == c->n_cols && t_rows_lds_bytes(n_words) <= kTrLdsBytes && c->nnz >= (1 << 22) && workspace &&
@@ -381,8 +381,8 @@ extern "C" int ngcf_spmm_t_rows_f32(const ngcf_csr_t *c, const int32_t *slot, co
         const int w = std::min(512, d - col0);
         const int dp = (int)align_up(w, 4);
         float *partial = nullptr;
-        if (c->n_seg > 0) {
-            const int64_t need = align_up(c->n_seg * dp * (int64_t)sizeof(float), 256) + 256;
+        if (c->seg.n_seg > 0) {
+            const int64_t need = align_up(c->seg.n_seg * dp * (int64_t)sizeof(float), 256) + 256;
             if (!workspace || workspace_bytes < need)
                 return fail(NGCF_ERR_WORKSPACE, "spmm_t_rows: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
             partial = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
@@ -392,11 +392,11 @@ extern "C" int ngcf_spmm_t_rows_f32(const ngcf_csr_t *c, const int32_t *slot, co
             if (bitmap) {
                 HIP_TRY(allow_full_lds<spmm_t_rows_bm_kernel<NQ>>());
                 spmm_t_rows_bm_kernel<NQ><<<dim3(kTrWGs), kTrWaves * 64, (size_t)t_rows_lds_bytes(n_words), stream>>>(
-                    c->rowptr, c->colidx, c->vals, c->n_rows, c->seg_row, c->seg_begin, c->n_seg, c->seg_len, slot, bitmap, (int)n_words,
+                    c->rowptr, c->colidx, c->vals, c->n_rows, c->seg.seg_row, c->seg.seg_begin, c->seg.n_seg, c->seg_len, slot, bitmap, (int)n_words,
                     counters + col0 / 512, X + col0, ldx, w, init ? init + col0 : nullptr, ldi, out + col0, ldo, partial, dp, dr);
             } else {
                 spmm_t_rows_kernel<NQ><<<dim3((unsigned)(seg_blocks + row_blocks)), 256, 0, stream>>>(
-                    c->rowptr, c->colidx, c->vals, c->n_rows, c->seg_row, c->seg_begin, c->n_seg, seg_blocks, c->seg_len, slot, X + col0, ldx, w,
+                    c->rowptr, c->colidx, c->vals, c->n_rows, c->seg.seg_row, c->seg.seg_begin, c->seg.n_seg, seg_blocks, c->seg_len, slot, X + col0, ldx, w,
                     init ? init + col0 : nullptr, ldi, out + col0, ldo, partial, dp, dr);
             }
             LAUNCH_CHECK();
@@ -407,8 +407,8 @@ extern "C" int ngcf_spmm_t_rows_f32(const ngcf_csr_t *c, const int32_t *slot, co
                        : w <= 256 ? launch(std::integral_constant<int, 4>{})
                                   : launch(std::integral_constant<int, 8>{});
         if (rc != NGCF_OK) return rc;
-        if (c->n_heavy > 0) {
-            spmm_fixup_kernel<1><<<dim3((unsigned)((c->n_heavy + 3) / 4)), 256, 0, stream>>>(c->heavy_row, c->heavy_seg_ptr, c->n_heavy, partial,
+        if (c->seg.n_heavy > 0) {
+            spmm_fixup_kernel<1><<<dim3((unsigned)((c->seg.n_heavy + 3) / 4)), 256, 0, stream>>>(c->seg.heavy_row, c->seg.heavy_seg_ptr, c->seg.n_heavy, partial,
                                                                                           dp, w, out + col0, ldo);
             LAUNCH_CHECK();
         }

@@ -16,6 +16,7 @@ import torch
 
 import ngcf_oracle as orc
 from conftest import FWD_CASES, load_golden
+from csr_cases import random_csr
 from golden_util import batch_of, ctor_args, lap_list_of, layer_params, sd_of
 
 pytestmark = pytest.mark.gpu
@@ -46,21 +47,6 @@ def c_spmm(oracle_clib, rowptr, col32, vals, E):
     fn(_p(rowptr), _p(col32), _p(vals), C.c_int64(len(rowptr) - 1), _p(E), C.c_int64(E.shape[1]),
        C.c_int(E.shape[1]), _p(out), C.c_int64(E.shape[1]))
     return out
-
-
-def random_csr(rng, n_rows, n_cols, mean_deg, heavy=(), empty=()):
-    deg = rng.poisson(mean_deg, n_rows)
-    for r, k in heavy:
-        deg[r] = k
-    for r in empty:
-        deg[r] = 0
-    rowptr = np.zeros(n_rows + 1, np.int64)
-    rowptr[1:] = np.cumsum(deg)
-    nnz = int(rowptr[-1])
-    cols = rng.integers(0, n_cols, nnz).astype(np.int64)
-    vals = rng.normal(0, 0.3, nnz).astype(np.float32)
-    rows = np.repeat(np.arange(n_rows, dtype=np.int64), deg)
-    return rowptr, rows, cols, vals
 
 
 # --------------------------------------------------------------------------------------------
