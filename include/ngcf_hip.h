@@ -344,6 +344,18 @@ int64_t ngcf_layer_bwd_input_workspace_bytes(int d_out);
 int ngcf_layer_bwd_input_f32(const float *dM, int64_t ldM, int64_t n_rows, int d_out, const float *W1, const float *W2,
                              int d_in, const float *LE, int64_t ldLE, const float *E, int64_t ldE, float *dLE, int64_t ldd,
                              float *dE, int64_t lde, void *workspace, int64_t workspace_bytes, void *stream);
+/* Which kernel ngcf_layer_bwd_input_f32 runs for the panel of input columns that starts at col0, and the panel's width in
+ * *panel_cols (may be NULL): the next panel starts at col0 + *panel_cols; a panel's columns past d_in do not exist.  A read-only
+ * query answered by the host function the entry point itself walks its panels with (nothing is launched); the sizes and the
+ * option bwd_input_resident decide, nothing else.  The rules, in this order:
+ *   bwd_input_resident != 0, 4 <= d_out <= 128 and n_rows >= 131 072 (two 32-row tiles for each of the 8 waves of 256 persistent
+ *   workgroups): panels of 128 columns on "resident" (layer_bwd_input_resident_kernel) while more than 4 columns are left, the
+ *   last 1..4 columns on "narrow" (layer_bwd_input_narrow_kernel; d_in <= 4: the whole product);
+ *   otherwise 129..160 columns left: "staged_wide" (layer_bwd_input_kernel<5,false>, one panel of 160);
+ *   otherwise a panel of 128: "staged_small" (<4,true>, 32-row tiles) up to 16 384 rows, "staged_tall" (<4,false>, 128-row
+ *   tiles) above.
+ * NULL (and ngcf_last_error) for sizes the entry point rejects and for a col0 that is not the start of a panel.  For tests and tools. */
+const char *ngcf_layer_bwd_input_path(int64_t n_rows, int d_in, int d_out, int col0, int *panel_cols);
 /* weight gradients of one layer on the fp32 matrix cores: gW1 [d_out, d_in] = dM^T . (LE + E) (the gradient of W1,
  * NGCF.py:131-133), gW2 [d_out, d_in] = dM^T . (LE * E) (W2, NGCF.py:135-136), each row-major with its own leading dimension
  * (so a caller tiling a wide layer passes sub-blocks of the full gradients); d_in, d_out <= 128 per call.  Fixed summation
@@ -353,6 +365,17 @@ int64_t ngcf_bwd_weight_workspace_bytes(void);
 int ngcf_layer_bwd_weight_f32(const float *dM, int64_t ldM, const float *LE, int64_t ldLE, const float *E, int64_t ldE,
                               int64_t n_rows, int d_in, int d_out, float *gW1, int64_t ld1, float *gW2, int64_t ld2,
                               float *gb1, float *gb2, void *workspace, int64_t workspace_bytes, void *stream);
+/* Which kernel ngcf_layer_bwd_weight_f32 would launch for these sizes and operands, and in *n_workgroups (may be NULL) how many
+ * workgroups - one partial result each, which bwd_weight_reduce_kernel adds in workgroup order.  A read-only query answered by
+ * the host function the entry point itself dispatches through (nothing is launched, the operands are not dereferenced - only
+ * their alignment counts; no option enters).  The rules, in this order:
+ *   d_in <= 4 and n_rows >= 65 536: "narrow" (bwd_weight_narrow_kernel), 2 048 workgroups of ceil(n_rows / 2 048) rows;
+ *   otherwise the matrix-core kernel on min(256, max(1, (ceil(n_rows / 32) + 1) / 2)) workgroups, which take the 32-row blocks
+ *   round robin: "mfma_aligned" (bwd_weight_kernel<true>) when dM, LE and E are 16-byte aligned and their leading dimensions
+ *   multiples of 4, "mfma_unaligned" (<false>) otherwise.
+ * NULL (and ngcf_last_error) for sizes ngcf_layer_bwd_weight_f32 rejects.  For tests and tools. */
+const char *ngcf_layer_bwd_weight_path(int64_t n_rows, int d_in, int d_out, const float *dM, int64_t ldM, const float *LE,
+                                       int64_t ldLE, const float *E, int64_t ldE, int *n_workgroups);
 /* out[r, 0:d] += add[r, 0:d] */
 int ngcf_add_rows_f32(float *out, int64_t ldo, const float *add, int64_t lda, int64_t n_rows, int d, void *stream);
 

@@ -76,9 +76,11 @@ PROTOTYPES = {
     "ngcf_layer_bwd_input_workspace_bytes": (_i64, [C.c_int]),
     "ngcf_layer_bwd_input_f32": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                            _vp, _i64, _vp]),
+    "ngcf_layer_bwd_input_path": (C.c_char_p, [_i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ngcf_bwd_weight_workspace_bytes": (_i64, []),
     "ngcf_layer_bwd_weight_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _vp,
                                             _vp, _i64, _vp]),
+    "ngcf_layer_bwd_weight_path": (C.c_char_p, [_i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_int)]),
     "ngcf_add_rows_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_int, _vp]),
     "ngcf_topk_rows_f32": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp]),
     "ngcf_recommend_topk_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp]),

@@ -338,6 +338,41 @@ extern "C" int64_t ngcf_bwd_weight_workspace_bytes(void)
     return (int64_t)kBwWGs * kBwM * kBwN * sizeof(float) + (int64_t)kBwWGs * kBwM * sizeof(float) + 256;
 }
 
+// Which kernel a weight-gradient call takes and how many workgroups - partials for the reduction - it launches.  The decision is
+// made HERE, once: ngcf_layer_bwd_weight_f32 launches what this returns and ngcf_layer_bwd_weight_path reports its name.  Pure host
+// code: the sizes and the alignment of the operands, nothing else (no option enters).
+enum BwdWeightKernel { kBwMfmaAligned, kBwMfmaUnaligned, kBwNarrow };
+struct BwdWeightPath {
+    BwdWeightKernel kernel;
+    int n_wg;              // workgroups of the kernel = partials the reduction adds up
+    const char *name;
+};
+static BwdWeightPath bwd_weight_path(int64_t n_rows, int d_in, const float *dM, int64_t ldM, const float *LE, int64_t ldLE,
+                                     const float *E, int64_t ldE)
+{
+    if (d_in <= 4 && n_rows >= 65536)         // a narrow remainder block of a large matrix: no matrix cores for 2 x d_in columns
+        return {kBwNarrow, kBwWGs * 8, "narrow"};                            // memory-bound: eight workgroups per CU
+    // workgroups: one per CU on a large matrix; on a small one (the Seoul graph's 5 940 rows are 186 blocks, a compacted last
+    // layer a few dozen) every workgroup should still see >= 2 blocks - each writes a 128 KB partial that the reduction reads
+    // back (256 of them: 33 MB and 116 us for a 65 x 130 gradient)
+    const int64_t n_blocks = (n_rows + kBwRows - 1) / kBwRows;
+    const int n_wg = (int)std::min<int64_t>(kBwWGs, std::max<int64_t>(1, (n_blocks + 1) / 2));
+    const bool al = ldM % 4 == 0 && ldLE % 4 == 0 && ldE % 4 == 0 && aligned16(dM) && aligned16(LE) && aligned16(E);
+    return al ? BwdWeightPath{kBwMfmaAligned, n_wg, "mfma_aligned"} : BwdWeightPath{kBwMfmaUnaligned, n_wg, "mfma_unaligned"};
+}
+
+extern "C" const char *ngcf_layer_bwd_weight_path(int64_t n_rows, int d_in, int d_out, const float *dM, int64_t ldM, const float *LE,
+                                                  int64_t ldLE, const float *E, int64_t ldE, int *n_workgroups)
+{
+    if (n_rows < 0 || d_in < 1 || d_out < 1 || d_in > 128 || d_out > 128 || ldM < d_out || ldLE < d_in || ldE < d_in) {
+        fail(NGCF_ERR_ARG, "layer_bwd_weight_path: bad sizes");
+        return nullptr;
+    }
+    const BwdWeightPath path = bwd_weight_path(n_rows, d_in, dM, ldM, LE, ldLE, E, ldE);
+    if (n_workgroups) *n_workgroups = path.n_wg;
+    return path.name;
+}
+
 extern "C" int ngcf_layer_bwd_weight_f32(const float *dM, int64_t ldM, const float *LE, int64_t ldLE, const float *E,
                                          int64_t ldE, int64_t n_rows, int d_in, int d_out, float *gW1, int64_t ld1, float *gW2,
                                          int64_t ld2, float *gb1, float *gb2, void *workspace, int64_t workspace_bytes, void *stream_)
@@ -354,25 +389,19 @@ extern "C" int ngcf_layer_bwd_weight_f32(const float *dM, int64_t ldM, const flo
     float *partial = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
     float *partial_bias = partial + (int64_t)kBwWGs * kBwM * kBwN;
     const int P = (int)align_up(d_in, 32);
-    const bool al = ldM % 4 == 0 && ldLE % 4 == 0 && ldE % 4 == 0 && aligned16(dM) && aligned16(LE) && aligned16(E);
-    // workgroups: one per CU on a large matrix; on a small one (the Seoul graph's 5 940 rows are 186 blocks, a compacted last
-    // layer a few dozen) every workgroup should still see >= 2 blocks - each writes a 128 KB partial that the reduction reads
-    // back (256 of them: 33 MB and 116 us for a 65 x 130 gradient)
-    const int64_t n_blocks = (n_rows + kBwRows - 1) / kBwRows;
-    const int n_wg = (int)std::min<int64_t>(kBwWGs, std::max<int64_t>(1, (n_blocks + 1) / 2));
-    int n_part = n_wg;                        // the partials the reduction adds up: one per workgroup of the kernel that ran
-    if (d_in <= 4 && n_rows >= 65536) {       // a narrow remainder block of a large matrix: no matrix cores for 2 x d_in columns
-        n_part = kBwWGs * 8;                  // memory-bound: eight workgroups per CU
-        partial_bias = partial + (int64_t)n_part * d_out * 2 * d_in;         // (behind the weight partials: 1024 x 128 floats fit easily)
-        bwd_weight_narrow_kernel<<<n_part, 256, 0, stream>>>(dM, ldM, LE, ldLE, E, ldE, n_rows, d_in, d_out, partial, partial_bias);
-    } else if (al) {
+    const BwdWeightPath path = bwd_weight_path(n_rows, d_in, dM, ldM, LE, ldLE, E, ldE);   // every decision: see there
+    const int n_wg = path.n_wg;
+    if (path.kernel == kBwNarrow) {
+        partial_bias = partial + (int64_t)n_wg * d_out * 2 * d_in;           // (behind the weight partials: 2048 x 128 floats fit easily)
+        bwd_weight_narrow_kernel<<<n_wg, 256, 0, stream>>>(dM, ldM, LE, ldLE, E, ldE, n_rows, d_in, d_out, partial, partial_bias);
+    } else if (path.kernel == kBwMfmaAligned) {
         bwd_weight_kernel<true><<<n_wg, 512, 0, stream>>>(dM, ldM, LE, ldLE, E, ldE, n_rows, d_in, d_out, P, partial, partial_bias);
     } else {
         bwd_weight_kernel<false><<<n_wg, 512, 0, stream>>>(dM, ldM, LE, ldLE, E, ldE, n_rows, d_in, d_out, P, partial, partial_bias);
     }
     LAUNCH_CHECK();
     const int total = d_out * 2 * d_in + ((gb1 || gb2) ? d_out : 0);
-    bwd_weight_reduce_kernel<<<(total + 63) / 64, 256, 0, stream>>>(partial, partial_bias, n_part, d_in, d_out, gW1, ld1, gW2, ld2, gb1, gb2);
+    bwd_weight_reduce_kernel<<<(total + 63) / 64, 256, 0, stream>>>(partial, partial_bias, n_wg, d_in, d_out, gW1, ld1, gW2, ld2, gb1, gb2);
     LAUNCH_CHECK();
     return NGCF_OK;
 }
@@ -764,6 +793,49 @@ extern "C" int64_t ngcf_layer_bwd_input_workspace_bytes(int d_out)
     return align_up(2 * n_chunks * kBiKC * kBiMaxCols * (int64_t)sizeof(float), 256) + 256;
 }
 
+// Which kernel the panel of input columns that starts at col0 takes, and the panel's width: the next panel starts at col0 + cols
+// (the panel's columns past d_in do not exist and are never stored).  The decision is made HERE, once: ngcf_layer_bwd_input_f32
+// walks the panels this returns and ngcf_layer_bwd_input_path reports their names.  Pure host code: the sizes and the option
+// bwd_input_resident, nothing else.  col0 is a panel start: 0, or what the widths of the panels before it add up to.
+enum BwdInputKernel { kBiStagedSmall, kBiStagedTall, kBiStagedWide, kBiResident, kBiNarrow };
+struct BwdInputPanel {
+    BwdInputKernel kernel;
+    int cols;              // 128, 160 (staged_wide), or the 1..4 columns of the narrow kernel
+    const char *name;
+};
+static bool bwd_input_rows_ok(int64_t n_rows) { return (n_rows + kBiRows - 1) / kBiRows < (int64_t)1 << 31; }
+static BwdInputPanel bwd_input_panel(int64_t n_rows, int d_in, int d_out, int col0)
+{
+    const int left = d_in - col0;
+    // r04: large matrices at K <= 128 - panels of 128 input columns on the weights-resident kernel, a remainder of 1..4 columns
+    // (the reference's 130- / 515-wide first layers) on the narrow kernel
+    const int k_chunks = (d_out + kBiResDC - 1) / kBiResDC;
+    const bool resident = ngcf_opts().bwd_input_resident && d_out <= 128 && d_out >= 4 && n_rows >= 2 * 32 * kBiResWaves * kBiResWGs &&
+                          ngcf_layer_bwd_input_workspace_bytes(d_out) >= (int64_t)k_chunks * kBiResDC * 256 * (int64_t)sizeof(float) + 256;
+    if (resident) return left > 4 ? BwdInputPanel{kBiResident, 128, "resident"} : BwdInputPanel{kBiNarrow, left, "narrow"};
+    // panels of 128 input columns, the last one up to 160
+    if (left > 128 && left <= 160) return {kBiStagedWide, 160, "staged_wide"};
+    // fewer than 128 tall tiles: 32-row tiles, the waves side by side (see the kernel)
+    return n_rows <= 16384 ? BwdInputPanel{kBiStagedSmall, 128, "staged_small"} : BwdInputPanel{kBiStagedTall, 128, "staged_tall"};
+}
+
+extern "C" const char *ngcf_layer_bwd_input_path(int64_t n_rows, int d_in, int d_out, int col0, int *panel_cols)
+{
+    if (n_rows < 0 || d_in <= 0 || d_out < 1 || !bwd_input_rows_ok(n_rows)) {
+        fail(NGCF_ERR_ARG, "layer_bwd_input_path: bad sizes");
+        return nullptr;
+    }
+    int start = 0;                             // walk the panels as the entry point does
+    while (start < col0 && start < d_in) start += bwd_input_panel(n_rows, d_in, d_out, start).cols;
+    if (col0 < 0 || start != col0 || col0 >= d_in) {
+        fail(NGCF_ERR_ARG, "layer_bwd_input_path: col0=%d is not the start of a panel of d_in=%d", col0, d_in);
+        return nullptr;
+    }
+    const BwdInputPanel panel = bwd_input_panel(n_rows, d_in, d_out, col0);
+    if (panel_cols) *panel_cols = panel.cols;
+    return panel.name;
+}
+
 extern "C" int ngcf_layer_bwd_input_f32(const float *dM, int64_t ldM, int64_t n_rows, int d_out, const float *W1, const float *W2,
                                         int d_in, const float *LE, int64_t ldLE, const float *E, int64_t ldE, float *dLE,
                                         int64_t ldd, float *dE, int64_t lde, void *workspace, int64_t workspace_bytes, void *stream_)
@@ -781,46 +853,44 @@ extern "C" int ngcf_layer_bwd_input_f32(const float *dM, int64_t ldM, int64_t n_
     float *Wp = reinterpret_cast<float *>(align_up((int64_t)(uintptr_t)workspace, 256));
     const int n_chunks = (d_out + kBiKC - 1) / kBiKC;
     const int64_t blocks = (n_rows + kBiRows - 1) / kBiRows;
-    if (blocks >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "layer_bwd_input: too many rows");
-    // r04: large matrices at K <= 128 - panels of 128 input columns on the weights-resident kernel, a remainder of 1..4 columns
-    // (the reference's 130- / 515-wide first layers) on the narrow kernel
+    if (!bwd_input_rows_ok(n_rows)) return fail(NGCF_ERR_ARG, "layer_bwd_input: too many rows");
     const int k_chunks = (d_out + kBiResDC - 1) / kBiResDC;
-    const bool resident = ngcf_opts().bwd_input_resident && d_out <= 128 && d_out >= 4 && n_rows >= 2 * 32 * kBiResWaves * kBiResWGs &&
-                          need >= (int64_t)k_chunks * kBiResDC * 256 * (int64_t)sizeof(float) + 256;
-    if (resident) {
-        HIP_TRY(allow_full_lds<layer_bwd_input_resident_kernel>());
-        const size_t lds = (size_t)k_chunks * kBiResDC * 256 * sizeof(float);
-        int col0 = 0;
-        for (; col0 < d_in && d_in - col0 > 4; col0 += 128) {
+    // panel by panel, each on the kernel bwd_input_panel() names (stream-ordered re-use of Wp)
+    for (int col0 = 0; col0 < d_in;) {
+        const BwdInputPanel panel = bwd_input_panel(n_rows, d_in, d_out, col0);          // every decision: see there
+        switch (panel.kernel) {
+        case kBiResident:
+            HIP_TRY(allow_full_lds<layer_bwd_input_resident_kernel>());
             bwd_input_pack_resident_kernel<<<64, 256, 0, stream>>>(W1, W2, d_out, d_in, col0, k_chunks * kBiResDC, Wp);
             LAUNCH_CHECK();
-            layer_bwd_input_resident_kernel<<<dim3(kBiResWGs), kBiResWaves * 64, lds, stream>>>(dM, ldM, n_rows, d_out, Wp, k_chunks, LE, ldLE, E,
-                                                                                               ldE, d_in, col0, dLE, ldd, dE, lde);
-            LAUNCH_CHECK();
-        }
-        if (col0 < d_in) {
+            layer_bwd_input_resident_kernel<<<dim3(kBiResWGs), kBiResWaves * 64, (size_t)k_chunks * kBiResDC * 256 * sizeof(float), stream>>>(
+                dM, ldM, n_rows, d_out, Wp, k_chunks, LE, ldLE, E, ldE, d_in, col0, dLE, ldd, dE, lde);
+            break;
+        case kBiNarrow:
             layer_bwd_input_narrow_kernel<<<dim3(kBiResWGs * 8), 256, 0, stream>>>(dM, ldM, n_rows, d_out, W1, W2, LE, ldLE, E, ldE, d_in, col0,
-                                                                                  d_in - col0, dLE, ldd, dE, lde);
+                                                                                  panel.cols, dLE, ldd, dE, lde);
+            break;
+        case kBiStagedWide:
+            bwd_input_pack_kernel<<<64, 256, 0, stream>>>(W1, W2, d_out, d_in, col0, panel.cols, n_chunks, Wp);
             LAUNCH_CHECK();
-        }
-        return NGCF_OK;
-    }
-    for (int col0 = 0; col0 < d_in;) {      // panels of 128 input columns, the last one up to 160 (stream-ordered re-use of Wp)
-        const int left = d_in - col0;
-        const int wcols = left > 128 && left <= 160 ? 160 : 128;
-        bwd_input_pack_kernel<<<64, 256, 0, stream>>>(W1, W2, d_out, d_in, col0, wcols, n_chunks, Wp);
-        LAUNCH_CHECK();
-        if (wcols == 160)
             layer_bwd_input_kernel<5, false><<<dim3((unsigned)blocks), 256, 0, stream>>>(dM, ldM, n_rows, d_out, Wp, n_chunks, LE, ldLE, E, ldE,
                                                                                          d_in, col0, dLE, ldd, dE, lde);
-        else if (n_rows <= 16384)         // fewer than 128 tall tiles: 32-row tiles, the waves side by side (see the kernel)
+            break;
+        case kBiStagedSmall:
+            bwd_input_pack_kernel<<<64, 256, 0, stream>>>(W1, W2, d_out, d_in, col0, panel.cols, n_chunks, Wp);
+            LAUNCH_CHECK();
             layer_bwd_input_kernel<4, true><<<dim3((unsigned)((n_rows + 31) / 32)), 256, 0, stream>>>(dM, ldM, n_rows, d_out, Wp, n_chunks, LE, ldLE,
                                                                                                     E, ldE, d_in, col0, dLE, ldd, dE, lde);
-        else
+            break;
+        case kBiStagedTall:
+            bwd_input_pack_kernel<<<64, 256, 0, stream>>>(W1, W2, d_out, d_in, col0, panel.cols, n_chunks, Wp);
+            LAUNCH_CHECK();
             layer_bwd_input_kernel<4, false><<<dim3((unsigned)blocks), 256, 0, stream>>>(dM, ldM, n_rows, d_out, Wp, n_chunks, LE, ldLE, E, ldE,
                                                                                          d_in, col0, dLE, ldd, dE, lde);
+            break;
+        }
         LAUNCH_CHECK();
-        col0 += wcols;
+        col0 += panel.cols;
     }
     return NGCF_OK;
 }

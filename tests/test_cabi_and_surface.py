@@ -108,6 +108,73 @@ def test_dense_path_names_the_kernel_the_dispatch_selects(lib_options):
     assert path(0, 64, 64) == "staged<1,4,1>/padded"
 
 
+def test_bwd_dense_paths_name_the_kernels_the_dispatch_selects(lib_options):
+    """ngcf_layer_bwd_weight_path and ngcf_layer_bwd_input_path are host code (sizes, operand alignment, one option): the
+    documented rules of the two backward dense dispatches, by name."""
+    from seoul_tourism_recommendation_ngcf_amd import _lib
+    lib = _lib.load()
+    assert _lib.PROTOTYPES["ngcf_layer_bwd_weight_path"][0] is C.c_char_p and _lib.PROTOTYPES["ngcf_layer_bwd_input_path"][0] is C.c_char_p
+    A, B, D = 0x10000, 0x20000, 0x30000                       # 16-byte aligned addresses: never dereferenced
+
+    def weight(n, d_in, d_out, dm=A, le=B, e=D, ldm=None, ldle=None, lde=None):
+        pad = lambda d: (d + 3) // 4 * 4                       # noqa: E731
+        n_wg = C.c_int(-1)
+        got = lib.ngcf_layer_bwd_weight_path(n, d_in, d_out, dm, pad(d_out) if ldm is None else ldm, le, pad(d_in) if ldle is None else ldle,
+                                             e, pad(d_in) if lde is None else lde, C.byref(n_wg))
+        return (None, None) if got is None else (got.decode(), n_wg.value)
+
+    # the narrow kernel: at most 4 input columns from 65 536 rows on, 2 048 workgroups; aligned or not
+    assert weight(65536, 4, 128) == weight(65536, 1, 1) == weight(70001, 2, 100, ldm=101) == ("narrow", 2048)
+    assert weight(65535, 4, 128) == ("mfma_aligned", 256) and weight(65536, 5, 128) == ("mfma_aligned", 256)
+    # the matrix-core kernel: two 32-row blocks per workgroup, at least 1 and at most 256 workgroups
+    assert [weight(n, 65, 64)[1] for n in (0, 1, 32, 33, 64, 65, 96, 97, 128, 129, 16320, 16321, 16384, 16423, 1000000)] == [
+        1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 255, 256, 256, 256, 256]
+    assert weight(1000, 65, 64)[0] == "mfma_aligned"
+    # unaligned: any of the three pointers, any of the three leading dimensions
+    for kw in (dict(dm=A + 4), dict(le=B + 8), dict(e=D + 12), dict(ldm=65), dict(ldle=70), dict(lde=67)):
+        assert weight(1000, 65, 64, **kw) == ("mfma_unaligned", 16), kw
+    assert lib.ngcf_layer_bwd_weight_path(1000, 65, 64, A, 64, B, 68, D, 68, None) == b"mfma_aligned"      # the count is optional
+    # what ngcf_layer_bwd_weight_f32 rejects has no path
+    for bad in ((10, 129, 64), (10, 64, 129), (10, 0, 64), (10, 64, 0), (-1, 64, 64)):
+        assert weight(*bad) == (None, None) and "layer_bwd_weight_path" in _lib.last_error()
+    assert weight(10, 64, 64, ldm=63) == weight(10, 64, 64, ldle=63) == weight(10, 64, 64, lde=63) == (None, None)
+
+    def panels(n, d_in, d_out):
+        out, col0 = [], 0
+        while col0 < d_in:
+            w = C.c_int(-1)
+            got = lib.ngcf_layer_bwd_input_path(n, d_in, d_out, col0, C.byref(w))
+            out.append((got.decode(), w.value))
+            col0 += w.value
+        return out
+
+    lib_options(bwd_input_resident=1)
+    small, tall, wide, res = ("staged_small", 128), ("staged_tall", 128), ("staged_wide", 160), ("resident", 128)
+    # below 131 072 rows: 32-row tiles up to 16 384 rows, 128-row tiles above; a last panel of 129..160 columns is one wide panel
+    assert panels(16384, 128, 64) == [small] and panels(16385, 128, 64) == [tall] and panels(131071, 128, 64) == [tall]
+    assert panels(1, 1, 1) == [small] and panels(0, 64, 64) == [small]
+    assert panels(100, 129, 64) == panels(100, 160, 64) == panels(20000, 130, 64) == [wide]
+    assert panels(100, 161, 64) == [small, small] and panels(100, 288, 64) == [small, wide] and panels(20000, 289, 64) == [tall, tall, tall]
+    assert panels(100, 515, 64) == [small] * 3 + [wide] and panels(100, 516 + 29, 64) == [small] * 5 and panels(20000, 416, 64) == [tall, tall, wide]
+    # from 131 072 rows on, d_out in 4..128: resident panels of 128 while more than 4 columns are left, then the narrow kernel
+    assert panels(131072, 128, 128) == [res] and panels(131072, 5, 4) == [res] and panels(131072, 133, 64) == [res, res]
+    assert [panels(131072, d, 64) for d in (1, 4)] == [[("narrow", 1)], [("narrow", 4)]]
+    assert [panels(200000, 128 + r, 65) for r in (1, 2, 3, 4)] == [[res, ("narrow", r)] for r in (1, 2, 3, 4)]
+    assert panels(131072, 260, 4) == [res, res, ("narrow", 4)] and panels(131072, 515, 128) == [res] * 4 + [("narrow", 3)]
+    # d_out outside 4..128, or the option off: the staged kernels at any row count
+    assert panels(131072, 130, 3) == panels(131072, 130, 129) == [wide] and panels(131072, 128, 3) == panels(200000, 4, 129) == [tall]
+    lib_options(bwd_input_resident=0)
+    assert panels(131072, 128, 128) == [tall] and panels(200000, 130, 64) == [wide] and panels(200000, 4, 64) == [tall]
+    lib_options(bwd_input_resident=1)
+    # bad sizes, and a col0 that is not a panel start
+    w = C.c_int(-1)
+    for bad in ((-1, 64, 64, 0), (10, 0, 64, 0), (10, 64, 0, 0), (1 << 40, 64, 64, 0), (10, 64, 64, 64), (10, 64, 64, -128),
+                (10, 64, 64, 1), (10, 256, 64, 256), (10, 140, 64, 128), (131072, 130, 64, 129), (131072, 132, 64, 256)):
+        assert lib.ngcf_layer_bwd_input_path(*bad, C.byref(w)) is None and "layer_bwd_input_path" in _lib.last_error(), bad
+    assert w.value == -1
+    assert lib.ngcf_layer_bwd_input_path(10, 300, 64, 128, None) == b"staged_small" and lib.ngcf_layer_bwd_input_path(131072, 130, 64, 128, None) == b"narrow"
+
+
 @pytest.mark.parametrize("name", ["fwd_sigA_small", "fwd_sigC_demo", "fwd_sigB_y19", "fwd_130_128"])
 def test_state_dict_surface_matches_reference_checkpoints(name):
     from seoul_tourism_recommendation_ngcf_amd import NGCF
