@@ -419,6 +419,61 @@ int ngcf_rank_metrics(const int64_t *top_idx, int64_t B, int k, const int64_t *u
                       const int64_t *truth_rowptr, const int32_t *truth_colidx, int64_t truth_col_offset,
                       const int32_t *ks_host, int n_ks, float *per_user, double *sums, int32_t *status, void *stream);
 
+/* ---- exact held-out positions (csrc/rank_position.hip) ---- */
+/* The exact rank of every held-out item among its user's eligible items, with no score matrix and no top list.  Batch row b is user
+ * r = user_ids ? user_ids[b] : b; the truth set and the optional exclusion set are item sets as above (rowptr int64, colidx int32
+ * ascending within a row, stored id - column offset = item id).  position is int32[n_truth], aligned with truth_colidx: entry e of
+ * truth row r, held-out item t, gets
+ *     position[e] = #{ eligible i != t : rank_before(key(s_i), i, key(s_t), t) }
+ * where eligible means 0 <= i < n_items and i not in the user's exclusion row (the user's other held-out items are eligible and
+ * count), s_i is the score of ngcf_rank_topk_f32 (one ascending-k fmaf chain from 0: the same bits), key is the monotone map float
+ * -> uint32 under which NaN sorts above +inf, and rank_before(ka, a, kb, b) = ka > kb || (ka == kb && a < b).  So position[e] is the
+ * 0-based index of t in the user's full sorted eligible list; wherever it is below 256 it is the column at which
+ * ngcf_rank_topk_f32 returns t.
+ *   - a held-out item that is in the user's exclusion row: -1
+ *   - a held-out id outside [0, n_items) after the offset: -1, and bit 1 (value 2) of *status; it is never used as an index
+ *   - r outside [0, n_user_rows): bit 0 (value 1) of *status, nothing is written for that batch row
+ *   - entries of users that are not in the batch are left untouched: chunked calls fill one buffer
+ *   - a user that occurs twice in user_ids has the same values written twice; duplicate ids within a truth row get equal positions
+ * All counts are integers and every atomic is an integer atomic: the result is identical from run to run and does not depend on
+ * B, the batch order or the item split.  Tiers: truth rows are ranked NGCF_RANK_POS_CAP entries at a time (the sorted pairs of 64
+ * such chunks sit in LDS beside the MFMA tiles); a longer row is cut into chunks that are scored as separate rows of the same user.
+ * Users with an empty truth row cost no scoring work.  The workspace (ngcf_rank_positions_workspace_bytes(B, n_items, D, n_truth),
+ * n_truth = entries of truth_colidx) holds B + n_truth / NGCF_RANK_POS_CAP chunks - enough for any batch of distinct users; a batch
+ * that repeats users with long rows past that sets bit 2 (value 4) of *status and leaves the chunks that did not fit untouched.
+ * Any D >= 1, n_items < 2^31. */
+#define NGCF_RANK_POS_CAP 64
+int64_t ngcf_rank_positions_workspace_bytes(int64_t B, int64_t n_items, int D, int64_t n_truth);
+int ngcf_rank_positions_f32(const float *users, int64_t ldu, const int64_t *user_ids, int64_t n_user_rows, int64_t B,
+                            const float *items, int64_t ldi, int64_t n_items, int D,
+                            const int64_t *truth_rowptr, const int32_t *truth_colidx, int64_t truth_col_offset, int64_t n_truth,
+                            const int64_t *excl_rowptr, const int32_t *excl_colidx, int64_t excl_col_offset,
+                            int32_t *position, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+/* Metrics from positions.  Per batch row: T = the distinct ids of the user's truth row, E = n_items - the length of its exclusion
+ * row (excl_rowptr may be NULL: E = n_items); a user with T = 0 is not evaluated.  Entries with a negative position (-1 not
+ * eligible, -2 never ranked) stay in T and in every denominator and count as misses.  With the valid positions ascending,
+ * p_0 < p_1 < .. < p_{V-1} (duplicate ids once), all in fp64:
+ *   rr   = 1/(p_0 + 1), 0 if V = 0            ap  = (sum_j (j + 1)/(p_j + 1)) / T
+ *   ndcg = sum_j 1/log2(p_j + 2) / sum_{j<T} 1/log2(j + 2)
+ *   auc  = sum_j ((E - T) - (p_j - j)) / (T * (E - T)): the share of (held-out, negative) pairs in the right order, a miss counting
+ *          as ranked below every negative; a user with E - T <= 0 is left out of the AUC sum and of its counter
+ *   per cut-off K of ks_host[0..n_ks) (HOST int32, 0 <= n_ks <= 8, 1 <= K <= n_items): recall = hits/T, ndcg = DCG@K/IDCG@K
+ *   (terms added in ascending position; IDCG over j < min(T, K)), precision = hits/K, hr = hits > 0, hits = #{p_j < K}: the
+ *   arithmetic and summation order of ngcf_rank_metrics, so for K <= 256 the per-user values, written as float32 as that function
+ *   writes them, equal its output bit for bit.  One operation differs below that: log2 is the correctly rounded one of
+ *   csrc/dd_log2.h, not the maths library's (good to an ulp, and which ulp differs from a host library's: at 3, for one), so that a
+ *   host oracle with the same operation order reproduces every per-user fp64 value.
+ * sums (device, float64 [4 + 4*n_ks + 2]) = [rr, ap, ndcg, auc, (recall, ndcg, precision, hr) per K, users, auc_users] is ADDED to
+ * in a fixed order (a wave its users in order, a workgroup its waves, one workgroup the blocks): bit-identical from run to run.
+ * per_user (float64 [B, 4 + 4*n_ks], may be NULL) gets the per-row values, 0 where a user or its AUC is not evaluated.  Rows of up
+ * to NGCF_RANK_POS_WAVE_ROW entries are visited in ascending position out of registers (one entry per lane, a wave-wide minimum per
+ * step); longer rows re-read the entries past that boundary every step.  An r outside [0, n_user_rows) sets bit 0 of *status. */
+#define NGCF_RANK_POS_WAVE_ROW 64
+int ngcf_rank_position_metrics(const int32_t *position, int64_t B, const int64_t *user_ids, int64_t n_user_rows,
+                               const int64_t *truth_rowptr, const int32_t *truth_colidx, int64_t n_truth,
+                               const int64_t *excl_rowptr, int64_t n_items, const int32_t *ks_host, int n_ks,
+                               double *per_user, double *sums, int32_t *status, void *stream);
+
 /* Candidate-list evaluation, the reference's own test protocol (experiment.py:66-119) for T cases x C candidates in one launch
  * (DESIGN 4.3).  Case t scores user r = user_ids[t] (users[r*ldu + 0..D)) against the items cand[t*ldc + 0..C) (rows of `items`,
  * ldi); column 0 is the held-out item.  s_j = <u, item[cand_j]> in fp32 in a summation order that depends on D alone: the same

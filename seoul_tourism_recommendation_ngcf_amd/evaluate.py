@@ -3,7 +3,8 @@ top lists against held-out items (Recall / NDCG / precision / hit rate @K).
 
 The reference ranks with `torch.topk(torch.mm(u, all_items_emb.T), k)` (demo.py:233-235) and computes its metrics as host-side
 bookkeeping (experiment.py:66-133); here both run on the device (engine.rank_topk, engine.ranking_metrics) and the host reads one
-vector back at the end.
+vector back at the end.  `full_ranks` goes past the top list: the exact position of every held-out item (engine.ranks) and MRR, MAP,
+AUC and the @K metrics for any K from those positions.
 
 The reference's own test protocol - one user against a short candidate list whose first entry is the held-out item, Test-BPR / HR@3 /
 NDCG@ks / RMSE (Experiment.eval, experiment.py:66-119) - is `candidate_ranking`: one propagation per year and one launch per chunk
@@ -59,6 +60,48 @@ def full_ranking(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), ye
             if int(status.item()) != 0:
                 raise IndexError(f"full_ranking: a user id lies outside [0, {n_user})")
             return engine.metrics_from_sums(sums, ks)
+    finally:
+        model.train(was_training)
+
+
+def full_ranks(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0,
+               users: Optional[torch.Tensor] = None, user_chunk: int = 65536, return_positions: bool = False):
+    """`full_ranking` without the top list's horizon: the exact position of every held-out item of `test` among its user's eligible
+    items (engine.ranks.rank_positions; the items of `train` are not eligible) and from the positions MRR, MAP, AUC, the uncut
+    NDCG and the @K metrics for any K in [1, n_item] (engine.ranks.position_metrics).  Same plumbing as `full_ranking`: one
+    propagate in eval mode under no_grad, the caller's mode restored, `user_chunk` users per launch against strided views of all_E,
+    one read-back at the end.  Returns {"mrr", "map", "auc", "ndcg", "recall@K", "ndcg@K", "precision@K", "hr@K", "users",
+    "auc_users"}; with `return_positions` the tuple (that dict, the int32 positions - -2 for users that were not ranked -, the truth
+    ItemSets whose `colidx` they align with)."""
+    ks = [int(x) for x in ks]
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            model.propagate(year_idx)
+            U, I = model.all_users_emb, model.all_items_emb
+            dev = U.device
+            n_user, n_item = int(U.shape[0]), int(I.shape[0])
+            excl = _as_sets(train, n_user, n_item, dev)
+            truth = _as_sets(test, n_user, n_item, dev)
+            if users is None:
+                users = torch.arange(n_user, device=dev, dtype=torch.int64)
+            users = users.reshape(-1).to(device=dev, dtype=torch.int64)
+            sums = torch.zeros(4 + 4 * len(ks) + 2, dtype=torch.float64, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            position = torch.full((int(truth.colidx.numel()),), engine.ranks.NOT_RANKED, dtype=torch.int32, device=dev)
+            for c0 in range(0, int(users.numel()), int(user_chunk)):
+                ids = users[c0:c0 + int(user_chunk)]
+                engine.ranks.rank_positions(U, I, truth, user_ids=ids, exclude=excl, out=position, status=status)
+                engine.ranks.position_metrics(position, truth, ks, n_item, exclude=excl, user_ids=ids, sums=sums, status=status)
+            host = torch.cat((sums, status.double())).cpu()            # the one read-back
+            word = int(host[-1])
+            if word & 4:
+                raise RuntimeError("full_ranks: `users` repeats users with long test rows past the workspace; use a smaller user_chunk")
+            if word != 0:
+                raise IndexError(f"full_ranks: a user id lies outside [0, {n_user}) or a held-out item outside [0, {n_item})")
+            out = engine.ranks.position_metrics_from_sums(host[:-1], ks)
+            return (out, position, truth) if return_positions else out
     finally:
         model.train(was_training)
 
