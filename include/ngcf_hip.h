@@ -548,6 +548,28 @@ int ngcf_sample_unseen(const int64_t *seen_rowptr, const int32_t *seen_colidx, i
                        const int64_t *user_ids, int64_t T, int64_t case_offset, int m, uint64_t seed, const int64_t *first,
                        int64_t *out, int64_t ld_out, int32_t *status, void *stream);
 
+/* Hard negatives, dynamic negative sampling for BPR training, for T cases in one launch: of m unseen draws per case, the one the
+ * current embeddings score highest.  Case `row` of user u = user_ids[row]:
+ *   draw    c_0 .. c_{m-1} = exactly the m items of ngcf_sample_unseen for (seed, t = case_offset + row, the seen row of u, m): the
+ *           same case key, positions, partial Fisher-Yates map and rank-to-item conversion, 1 <= m <= NGCF_SAMPLE_HARD_M_MAX
+ *   score   s_j = <users[u*ldu + 0..D), items[c_j*ldi + 0..D)> with exactly the score bits of ngcf_eval_candidates_f32 (a summation
+ *           order that depends on D alone, whatever the tables' alignment)
+ *   select  the largest s_j in the order of ngcf_topk_rows_f32 on the scores' bits (NaN above +inf - a NaN whose sign bit is set,
+ *           as gfx950 makes of inf - inf, below -inf -, -0.0 below +0.0); equal bits: the lowest slot j
+ * and neg[row] = c_j, score[row] = s_j (fp32, may be NULL), slot[row] = j (int32, may be NULL): what ngcf_sample_unseen, then
+ * ngcf_eval_candidates_f32 with `scores`, then an argmax over each row would give, bit for bit, with nothing of size T x m written
+ * to memory.  A case set drawn in chunks with case_offset = the chunk's first case equals the set drawn at once.  *status is OR-ed
+ * into, never cleared: 1 = a user id outside [0, n_rows), 2 = a user with fewer than m unseen items; such a case writes neg = -1,
+ * slot = -1 and a NaN score and loads no embedding row (the user id is checked before any row is loaded; the drawn items lie in
+ * [0, n_items)).  Argument errors, before any launch: m outside [1, 64], n_items outside [1, 2^31), n_item_rows < n_items (the item
+ * table is shorter than the catalogue the sets index), n_user_rows < n_rows, D < 1, ldu or ldi below D, a null pointer; T == 0 is
+ * not an error.  Any D, any alignment (float4 loads where `items` and ldi allow them). */
+#define NGCF_SAMPLE_HARD_M_MAX 64
+int ngcf_sample_hard_f32(const int64_t *seen_rowptr, const int32_t *seen_colidx, int64_t col_offset, int64_t n_rows, int64_t n_items,
+                         const float *users, int64_t ldu, int64_t n_user_rows, const float *items, int64_t ldi, int64_t n_item_rows,
+                         int D, const int64_t *user_ids, int64_t T, int64_t case_offset, int m, uint64_t seed, int64_t *neg,
+                         float *score, int32_t *slot, int32_t *status, void *stream);
+
 /* Per-segment quantile floor, the numeric core of the reference's Preprocess.scale_implicit (utils.py:103-122) for every
  * user in one call.  Segment u is the entries order[rowptr[u] .. rowptr[u+1]), positions into x and out (both double [T]); order ==
  * NULL is the identity: x is already grouped.  With z(v) = ((v - mean) / scale) + shift (0, 1, 0: the identity) and, for the n values

@@ -2,7 +2,7 @@
 // scores of one user against its C candidate items, the position of the held-out item (column 0) among them, and from these
 // HR@hit_k, NDCG@ks, the Test-BPR of bprloss.py:15-22 and |s_0 - rating| - no forward, no mm, no topk, no read-back per case
 // (DESIGN 4.3).
-#include "common.h"
+#include "cand_device.h"
 
 // ---------------------------------------------------------------------------------------------
 // Mapping.  A wave owns a case; a workgroup = 4 waves with nothing shared but the final partial sums.  The wave stages the user
@@ -14,6 +14,7 @@
 // Score bits.  s = <u, item> is: per lane one ascending fmaf chain from 0 over the lane's quads (elements past D enter as 0 in
 // both load forms), then an xor butterfly (8, 4, 2, 1) over the 16 lanes.  Which lane adds what depends on D alone, so a (user
 // row, item row) pair gives the same bits in every case, column, launch shape and alignment; duplicated candidates tie exactly.
+// The quad loads, the chain and the butterfly are cand_device.h's, which sample_hard.hip shares.
 //
 // Per case, from the C scores and squared item norms in LDS: position = number of columns j >= 1 whose key (float_key: NaN above
 // +inf) is above column 0's - column 0 is the lowest column, so it wins every tie (the order of ngcf_topk_rows_f32); the BPR terms
@@ -29,7 +30,7 @@
 #define NGCF_CAND_KS 8
 #define NGCF_CAND_WAVES 4
 #define NGCF_CAND_SLOTS (NGCF_CAND_KS + 4)
-#define NGCF_CAND_LDS_FLOATS 4096          // per wave: a user row that with 2 C floats exceeds this is read from global memory instead
+// NGCF_CAND_LDS_FLOATS (cand_device.h), per wave: a user row that with 2 C floats exceeds it is read from global memory instead
 
 namespace {
 
@@ -39,28 +40,8 @@ struct CandParams {                         // by value: stays in the kernarg se
     float weight_decay, batch_size;
 };
 
-// quad q of a row of D floats, elements past D as 0
-template <bool VEC> __device__ inline float4 cand_quad(const float *row, int q, int D)
-{
-    const int e = 4 * q;
-    if (VEC && e + 3 < D) return *reinterpret_cast<const float4 *>(row + e);
-    float4 v;
-    v.x = row[e];                           // callers pass e < D
-    v.y = e + 1 < D ? row[e + 1] : 0.f;
-    v.z = e + 2 < D ? row[e + 2] : 0.f;
-    v.w = e + 3 < D ? row[e + 3] : 0.f;
-    return v;
-}
-
 // LDS floats of one wave: the user row (whole quads), C scores, C squared norms; a multiple of 4, so every wave's row is 16-byte aligned
 __host__ __device__ inline int cand_wave_floats(int Dp, int C) { return Dp + ((2 * C + 3) & ~3); }
-
-__device__ inline float group16_sum(float x)
-{
-#pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
 
 __device__ inline double wave_sum_f64(double x)
 {
@@ -127,10 +108,8 @@ __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kerne
             for (int q = sub; q < n_quads; q += 16) {
                 const float4 x = cand_quad<VEC>(ra, q, D), y = cand_quad<VEC>(rb, q, D);
                 const float4 u = ULDS ? *reinterpret_cast<const float4 *>(su + 4 * q) : cand_quad<false>(urow, q, D);
-                sa = fmaf(u.x, x.x, sa); sa = fmaf(u.y, x.y, sa); sa = fmaf(u.z, x.z, sa); sa = fmaf(u.w, x.w, sa);
-                sb = fmaf(u.x, y.x, sb); sb = fmaf(u.y, y.y, sb); sb = fmaf(u.z, y.z, sb); sb = fmaf(u.w, y.w, sb);
-                na = fmaf(x.x, x.x, na); na = fmaf(x.y, x.y, na); na = fmaf(x.z, x.z, na); na = fmaf(x.w, x.w, na);
-                nb = fmaf(y.x, y.x, nb); nb = fmaf(y.y, y.y, nb); nb = fmaf(y.z, y.z, nb); nb = fmaf(y.w, y.w, nb);
+                sa = cand_fma4(u, x, sa); sb = cand_fma4(u, y, sb);
+                na = cand_fma4(x, x, na); nb = cand_fma4(y, y, nb);
             }
             sa = group16_sum(sa); sb = group16_sum(sb);
             na = group16_sum(na); nb = group16_sum(nb);

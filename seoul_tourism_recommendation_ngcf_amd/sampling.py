@@ -9,7 +9,7 @@ function of (seed, row number, the user's seen items) that the tests recompute o
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 
@@ -53,6 +53,37 @@ def train_triplets(users: torch.Tensor, items: torch.Tensor, seen: Optional[engi
     users, items, seen = _rows(users, items, seen, n_user, n_item, "train_triplets")
     neg = engine.sample_unseen(seen, users, 1, fmix(int(seed) + int(epoch)))
     return users, items, neg[:, 0]
+
+
+def _hard_draw(users: torch.Tensor, user_emb: torch.Tensor, item_emb: torch.Tensor, seen: engine.ItemSets, m: int, seed_e: int,
+               chunk: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The hard negative of every row (engine.negatives.hard_unseen), in one launch or in pieces of `chunk` rows."""
+    n = int(users.numel())
+    if chunk is None or int(chunk) >= n:
+        return engine.negatives.hard_unseen(seen, user_emb, item_emb, users, m, seed_e, out=out)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"hard_triplets: chunk={chunk}")
+    neg = torch.empty(n, dtype=torch.int64, device=users.device) if out is None else out
+    for r0 in range(0, n, chunk):
+        engine.negatives.hard_unseen(seen, user_emb, item_emb, users[r0:r0 + chunk], m, seed_e, case_offset=r0, out=neg[r0:r0 + chunk])
+    return neg
+
+
+def hard_triplets(users: torch.Tensor, items: torch.Tensor, user_emb: torch.Tensor, item_emb: torch.Tensor,
+                  seen: Optional[engine.ItemSets] = None, *, m: int = 8, seed: int, epoch: int = 0, n_user: int, n_item: int,
+                  chunk: Optional[int] = None):
+    """`train_triplets` with hard negatives (dynamic negative sampling): for positive row t the best-scoring of `m` items the user
+    has no entry for in `seen`, under the tables `user_emb` [>= n_user, D] and `item_emb` [>= n_item, D] - in practice
+    `model.all_users_emb` and `model.all_items_emb` after a propagation (a forward of the model), so the negatives are as fresh as
+    those tables: tables from before the last optimizer steps pick the items that were hard then.  Returns (users, items, neg),
+    int64 [T] on the device of `users`.  With seed_e = fmix(seed + epoch), exactly as in `train_triplets`: neg[t] is an element of
+    row t of `engine.sample_unseen(seen, users, m, seed_e)` - the one with the largest <user_emb[users[t]], item_emb[.]> in the
+    bits and order of `engine.negatives.hard_unseen`, one launch, nothing of size T x m in memory - and with m = 1 the result
+    equals `train_triplets(...)`, whatever the tables.  `chunk` draws the rows in pieces of that many through `case_offset`, with the
+    same result.  `m` in [1, 64].  A user id outside the sets raises IndexError, a user with fewer than `m` unseen items ValueError."""
+    users, items, seen = _rows(users, items, seen, n_user, n_item, "hard_triplets")
+    return users, items, _hard_draw(users, user_emb, item_emb, seen, int(m), fmix(int(seed) + int(epoch)), chunk)
 
 
 def test_candidates(users: torch.Tensor, items: torch.Tensor, seen: Optional[engine.ItemSets] = None, *, m: int = 24, seed: int,
@@ -99,6 +130,61 @@ class TripletLoader:
         return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
 
     def __iter__(self):
+        used = len(self) * self.batch_size if self.drop_last else self.n
+        table = self.table
+        if self.shuffle:
+            perm = torch.randperm(self.n, generator=self.generator, device=table.device)
+            table = table[:, perm[:used]]                                       # the epoch's one gathered copy
+        for b0 in range(0, used, self.batch_size):
+            yield tuple(table[:, b0:b0 + self.batch_size].unbind(0))
+
+
+class HardTripletLoader:
+    """`TripletLoader` whose negatives are redrawn every epoch as hard negatives: the batch shape, `columns`, `shuffle`, `drop_last`
+    and `generator` are `TripletLoader`'s, the `neg` column is `hard_triplets(..., m=m, seed=seed, epoch=e)`.  `tables` is a callable
+    returning `(user_emb, item_emb)`, e.g. `lambda: (model.all_users_emb, model.all_items_emb)` after a propagation; every `iter()`
+    calls it once, draws all negatives with epoch e = 0, 1, 2, ... (`.epoch` is the number of the next one) against those tables,
+    then shuffles and yields views as `TripletLoader` does: one kernel launch, one `torch.randperm` and one gather per epoch.  The
+    seen sets are the positives themselves, `ItemSets.from_pairs(users, items, ...)` over as many users and items as the tables have
+    rows, built at the first `iter()`.  Without `shuffle` the batches are views of the loader's own table, which the next `iter()`
+    overwrites."""
+
+    def __init__(self, users: torch.Tensor, items: torch.Tensor, columns: Sequence[torch.Tensor] = (), *, batch_size: int,
+                 tables: Callable[[], Tuple[torch.Tensor, torch.Tensor]], m: int = 8, seed: int, shuffle: bool = True,
+                 drop_last: bool = True, generator: Optional[torch.Generator] = None):
+        cols = list(columns) if len(columns) else [users]
+        cols += [items]
+        n = int(users.numel())
+        for c in [users] + cols:
+            if c.dim() != 1 or int(c.numel()) != n:
+                raise ValueError(f"HardTripletLoader: every column must be [n = {n}], got {tuple(c.shape)}")
+            if c.device != users.device:
+                raise RuntimeError(f"HardTripletLoader: a column is on {c.device}, users on {users.device}")
+        if int(batch_size) < 1:
+            raise ValueError(f"HardTripletLoader: batch_size={batch_size}")
+        if int(m) < 1 or int(m) > engine.negatives.HARD_M_MAX:
+            raise ValueError(f"HardTripletLoader: m={m} outside [1, {engine.negatives.HARD_M_MAX}]")
+        if not callable(tables):
+            raise TypeError("HardTripletLoader: tables must be a callable returning (user_emb, item_emb)")
+        self.table = torch.stack([c.to(torch.int64) for c in cols] + [torch.full_like(users, -1, dtype=torch.int64)])   # [columns, n]
+        self.users, self.items = users.to(torch.int64), self.table[-2]
+        self.n, self.batch_size = n, int(batch_size)
+        self.tables, self.m, self.seed, self.epoch = tables, int(m), int(seed), 0
+        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
+        self._seen: Optional[engine.ItemSets] = None
+
+    def __len__(self) -> int:
+        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
+
+    def __iter__(self):
+        user_emb, item_emb = self.tables()
+        if self._seen is None:
+            self._seen = engine.ItemSets.from_pairs(self.users, self.items, int(user_emb.shape[0]), int(item_emb.shape[0]))
+        _hard_draw(self.users, user_emb, item_emb, self._seen, self.m, fmix(self.seed + self.epoch), out=self.table[-1])
+        self.epoch += 1
+        return self._batches()
+
+    def _batches(self):
         used = len(self) * self.batch_size if self.drop_last else self.n
         table = self.table
         if self.shuffle:
