@@ -126,6 +126,13 @@ int64_t ngcf_csr_max_row_len(const ngcf_csr_t *csr);        /* stored entries of
  * plan declines - too small, expected re-use below 3, table beyond 32-bit offsets - or a device that does not report 256 CUs,
  * for which one note is printed on stderr) */
 int64_t ngcf_csr_swept_rows(const ngcf_csr_t *csr);
+/* the row groups of the current plan (for tests and tools; read-only): group g covers rows [begin, end); `sliceable`: its rows
+ * gather from a table slice small enough for the d-sliced kernel; `lds_table`: from at most 512 table rows (table-in-LDS
+ * kernel); [col_lo, col_hi]: the columns its rows gather from (col_hi < col_lo: no entries).  Any out pointer may be NULL.
+ * A thinned copy reports its source's groups. */
+int64_t ngcf_csr_n_groups(const ngcf_csr_t *csr);
+int ngcf_csr_group(const ngcf_csr_t *csr, int64_t g, int64_t *begin, int64_t *end, int *sliceable, int *lds_table,
+                   int32_t *col_lo, int32_t *col_hi);
 /* device pointers of the CSR arrays (for tests / the transposed view) */
 const int64_t *ngcf_csr_rowptr(const ngcf_csr_t *csr);
 const int32_t *ngcf_csr_colidx(const ngcf_csr_t *csr);

@@ -42,6 +42,9 @@ PROTOTYPES = {
     "ngcf_csr_n_segments": (_i64, [_vp]),
     "ngcf_csr_max_row_len": (_i64, [_vp]),
     "ngcf_csr_swept_rows": (_i64, [_vp]),
+    "ngcf_csr_n_groups": (_i64, [_vp]),
+    "ngcf_csr_group": (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                 C.POINTER(_i32), C.POINTER(_i32)]),
     "ngcf_csr_rowptr": (_vp, [_vp]),
     "ngcf_csr_colidx": (_vp, [_vp]),
     "ngcf_csr_vals": (_vp, [_vp]),

@@ -72,6 +72,20 @@ extern "C" int64_t ngcf_csr_swept_rows(const ngcf_csr_t *c)
     for (const auto &p : c->swept.parts) n += p.row_hi - p.row_lo;
     return n;
 }
+extern "C" int64_t ngcf_csr_n_groups(const ngcf_csr_t *c) { return c ? (int64_t)c->groups.size() : -1; }
+extern "C" int ngcf_csr_group(const ngcf_csr_t *c, int64_t g, int64_t *begin, int64_t *end, int *sliceable, int *lds_table,
+                              int32_t *col_lo, int32_t *col_hi)
+{
+    if (!c || g < 0 || g >= (int64_t)c->groups.size()) return fail(NGCF_ERR_ARG, "ngcf_csr_group: no such row group");
+    const ngcf_csr::RowGroup &grp = c->groups[(size_t)g];
+    if (begin) *begin = grp.begin;
+    if (end) *end = grp.end;
+    if (sliceable) *sliceable = grp.sliceable ? 1 : 0;
+    if (lds_table) *lds_table = grp.lds_table ? 1 : 0;
+    if (col_lo) *col_lo = grp.col_lo;
+    if (col_hi) *col_hi = grp.col_hi;
+    return NGCF_OK;
+}
 extern "C" const int64_t *ngcf_csr_rowptr(const ngcf_csr_t *c) { return c ? c->rowptr : nullptr; }
 extern "C" const int32_t *ngcf_csr_colidx(const ngcf_csr_t *c) { return c ? c->colidx : nullptr; }
 extern "C" const float *ngcf_csr_vals(const ngcf_csr_t *c) { return c ? c->vals : nullptr; }

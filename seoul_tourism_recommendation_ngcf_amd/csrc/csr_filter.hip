@@ -12,7 +12,9 @@
 // The segment structure is the source's: a row cut into k segments there keeps k segments here (seg_begin' = rowptr'[row]
 // + j*seg_len; trailing ones may be empty), so seg_row / heavy_row / heavy_seg_ptr are shared and no plan is built.  A row
 // that fell to <= seg_len entries is then produced twice - as a row by the row kernels and from its segments by the fix-up,
-// which runs last and writes the same sum.
+// which runs last and writes the same sum.  "Last" holds because a thinned copy is never multiplied under stream capture, where
+// launch_spmm (spmm.hip) would fork the row kernels onto a side stream that joins after the fix-up: its keep flags are drawn on the
+// host every step, so the captured forward and training steps refuse reference-mode node dropout and multiply the cached L only.
 // =============================================================================================
 constexpr int kScanBlock = 2048;        // entries per workgroup (256 threads x 8)
 

@@ -123,6 +123,18 @@ class LaplacianCSR:
         """Rows covered by L2-swept parts (0: all products of this CSR use the row-wise kernels)."""
         return int(_lib.load().ngcf_csr_swept_rows(self._h))
 
+    def groups(self) -> list:
+        """The row groups of the current plan (ngcf_csr_group; for tests and tools): one dict per group with `begin`, `end`,
+        `sliceable`, `lds_table`, `col_lo`, `col_hi` (col_hi < col_lo: the group has no entries)."""
+        lib = _lib.load()
+        out = []
+        for g in range(int(lib.ngcf_csr_n_groups(self._h))):
+            b, e, s, t, lo, hi = C.c_int64(), C.c_int64(), C.c_int(), C.c_int(), C.c_int32(), C.c_int32()
+            _lib.check(lib.ngcf_csr_group(self._h, g, C.byref(b), C.byref(e), C.byref(s), C.byref(t), C.byref(lo), C.byref(hi)))
+            out.append({"begin": b.value, "end": e.value, "sliceable": bool(s.value), "lds_table": bool(t.value),
+                        "col_lo": lo.value, "col_hi": hi.value})
+        return out
+
     def layer_workspace_bytes(self, d_in: int, d_out: int) -> int:
         n = int(_lib.load().ngcf_layer_workspace_bytes(self._h, d_in, d_out))
         if n < 0:

@@ -55,6 +55,7 @@ SIGNATURES = {'ItemSets.__init__': "(self, rowptr: 'torch.Tensor', colidx: 'torc
  'LaplacianCSR.from_coo': "(cls, rows: 'torch.Tensor', cols: 'torch.Tensor', vals: 'torch.Tensor', n_rows: 'int', n_cols: 'int')",
  'LaplacianCSR.from_csr_arrays': "(cls, rowptr: 'torch.Tensor', colidx: 'torch.Tensor', vals: 'torch.Tensor', n_cols: 'int')",
  'LaplacianCSR.from_sparse_coo': "(cls, L: 'torch.Tensor', device, row_range=None)",
+ 'LaplacianCSR.groups': "(self) -> 'list'",
  'LaplacianCSR.layer_workspace_bytes': "(self, d_in: 'int', d_out: 'int') -> 'int'",
  'LaplacianCSR.max_row_len': 'property',
  'LaplacianCSR.n_segments': 'property',
