@@ -344,6 +344,15 @@ int ngcf_layer_bwd_pre_f32(const float *dN, int64_t ldn, const float *dC, int64_
 int ngcf_spmm_t_rows_f32(const ngcf_csr_t *csr_t, const int32_t *slot, const float *X, int64_t ldx, int d, const float *init,
                          int64_t ldi, float *out, int64_t ldo, float drop_p, const uint64_t *seeds, int n_seeds,
                          void *workspace, int64_t workspace_bytes, void *stream);
+/* Which of its two kernels ngcf_spmm_t_rows_f32 would launch for this CSR, width and workspace size under the current options:
+ * a read-only query answered by the host function the entry point itself dispatches through (nothing is launched).  "bitmap":
+ * 16 rows to a wave, the membership of a column in the R rows tested on a bitmap in LDS - a square matrix whose bitmap fits
+ * 160 KiB of LDS beside the hit lists (N <= 1 138 560), d <= 4096, at least 2^22 stored entries (option t_rows_bitmap = 2: any
+ * number; 0: never) and a workspace with room for the bitmap behind the partial sums (their bytes + N / 8 + 1 KiB: the size
+ * ngcf_spmm_workspace_bytes gives has it from 17 rows on); "slot": one wave per row on the slot table, everywhere else.  Both
+ * form every sum in entry order with the same fmaf: the same bits.  NULL (and ngcf_last_error) for a NULL csr, d <= 0 or a
+ * negative size.  For tests and tools. */
+const char *ngcf_spmm_t_rows_path(const ngcf_csr_t *csr_t, int d, int64_t workspace_bytes);
 /* Input gradients of a layer's dense half in one MFMA kernel: dS = dM.W1, dP = dM.W2 (never stored), dLE = dS + dP*E,
  * dE_direct = dS + dP*LE (NGCF.py:131-136 differentiated).  dM: [n_rows, d_out], any d_out >= 1 (65 in the reference's own
  * configuration), with 16-byte aligned rows padded to a multiple of 4 floats (the padding is never used); W1, W2: [d_out, d_in] row-major (nn.Linear.weight); LE, E, dLE, dE: [n_rows, d_in]. */

@@ -76,6 +76,7 @@ PROTOTYPES = {
     "ngcf_layer_bwd_pre_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, C.c_int, _f32, _f32, _u64, _vp, _i64,
                                          _vp, _vp, _i64, _vp]),
     "ngcf_spmm_t_rows_f32": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _f32, C.POINTER(_u64), C.c_int, _vp, _i64, _vp]),
+    "ngcf_spmm_t_rows_path": (C.c_char_p, [_vp, C.c_int, _i64]),
     "ngcf_layer_bwd_input_workspace_bytes": (_i64, [C.c_int]),
     "ngcf_layer_bwd_input_f32": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                            _vp, _i64, _vp]),

@@ -69,7 +69,7 @@ struct NgcfOptions {
     int dense_small_tiles = 1;     // NGCF_DENSE_SMALL_TILES: 32-row tiles for <= 128 output columns on <= 16 384 rows
     int dense_tall = 1;            // NGCF_DENSE_TALL: 256 / 512 output columns as 96-row x 128-column workgroups: 0 never, 1 where measured faster, 2 always
     // spmm_t_rows.hip, bwd_dense.hip
-    int t_rows_bitmap = 1;         // NGCF_T_ROWS_BITMAP: 0 keeps the row-sparse transposed product on the slot-table kernel at every size
+    int t_rows_bitmap = 1;         // NGCF_T_ROWS_BITMAP: the bitmap-in-LDS kernel of the row-sparse transposed product: 0 never (the slot-table kernel at every size), 1 from 2^22 stored entries, 2 at any number of stored entries (every other condition stays)
     int bwd_input_resident = 1;    // NGCF_BWD_INPUT_RESIDENT: 0 keeps the staged input-gradient kernel at every size
     // select.hip
     int select_no_lds = 0;         // NGCF_SELECT_NO_LDS: the per-group select counts in memory at every group count

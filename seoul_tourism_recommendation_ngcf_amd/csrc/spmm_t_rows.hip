@@ -349,6 +349,37 @@ __global__ __launch_bounds__(kTrWaves * 64) void spmm_t_rows_bm_kernel(const int
     }
 }
 
+// Which of the two kernels a call takes.  The choice is made HERE, once: ngcf_spmm_t_rows_f32 launches what this returns and
+// ngcf_spmm_t_rows_path reports it, so a test that names the bitmap kernel fails when the dispatch stops sending it there.
+// Pure host code: the shape of the CSR, the width, the room in the workspace and the option t_rows_bitmap (ngcf_opts()).
+// r04: the membership bitmap of the R rows in LDS (see spmm_t_rows_bm_kernel) where it fits (N / 8 bytes + 21 KB of hit lists
+// <= 160 KB: N <= 1.13 M) and the matrix is large enough for a persistent grid to pay (2^22 stored entries; t_rows_bitmap = 2:
+// at any number, for tests); the bitmap and the panel counters live behind the partial sums in the workspace.
+struct TRowsPath {
+    bool bitmap;
+    int64_t n_slot, n_words, part_bytes;     // rows the slot table covers; 32-bit words of the bitmap (a multiple of 4); bytes of the partial sums in front of it
+};
+static TRowsPath t_rows_path(const ngcf_csr *c, int d, bool has_workspace, int64_t workspace_bytes)
+{
+    TRowsPath p{};
+    p.n_slot = std::max(c->n_cols, c->n_rows);                  // (square in every use: the slot table covers rows and columns)
+    p.n_words = (p.n_slot + 127) / 128 * 4;
+    p.part_bytes = c->seg.n_seg > 0 ? align_up(c->seg.n_seg * align_up(std::min(d, 512), 4) * (int64_t)sizeof(float), 256) + 256 : 256;
+    const int mode = ngcf_opts().t_rows_bitmap;
+    p.bitmap = mode && c->n_rows == c->n_cols && t_rows_lds_bytes(p.n_words) <= kTrLdsBytes && (mode >= 2 || c->nnz >= (1 << 22)) && has_workspace &&
+               d <= 512 * kTrPanels && workspace_bytes >= p.part_bytes + p.n_words * 4 + 1024;
+    return p;
+}
+
+extern "C" const char *ngcf_spmm_t_rows_path(const ngcf_csr_t *c, int d, int64_t workspace_bytes)
+{
+    if (!c || d <= 0 || workspace_bytes < 0) {
+        fail(NGCF_ERR_ARG, "spmm_t_rows_path: bad argument");
+        return nullptr;
+    }
+    return t_rows_path(c, d, workspace_bytes > 0, workspace_bytes).bitmap ? "bitmap" : "slot";
+}
+
 extern "C" int ngcf_spmm_t_rows_f32(const ngcf_csr_t *c, const int32_t *slot, const float *X, int64_t ldx, int d, const float *init,
                                     int64_t ldi, float *out, int64_t ldo, float drop_p, const uint64_t *seeds, int n_seeds,
                                     void *workspace, int64_t workspace_bytes, void *stream_)
@@ -363,15 +394,11 @@ extern "C" int ngcf_spmm_t_rows_f32(const ngcf_csr_t *c, const int32_t *slot, co
     for (int q = 0; q < n_seeds; ++q) dr.seed[q] = seeds[q];
     const int64_t seg_blocks = (c->seg.n_seg + 3) / 4, row_blocks = (c->n_rows + 3) / 4;
     if (seg_blocks + row_blocks >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "spmm_t_rows: too many rows for one launch");
-    // r04: the membership bitmap of the R rows in LDS (see spmm_t_rows_bm_kernel) where it fits (N / 8 bytes + 21 KB of hit lists <= 160 KB: N <= 1.13 M) and the matrix
-    // is large enough for a persistent grid to pay; it lives behind the partial sums in the workspace
-    const int64_t n_slot = std::max(c->n_cols, c->n_rows);      // (square in every use: the slot table covers rows and columns)
-    const int64_t n_words = (n_slot + 127) / 128 * 4;             // 32-bit words, a multiple of 4
-    const int64_t part_bytes = c->seg.n_seg > 0 ? align_up(c->seg.n_seg * align_up(std::min(d, 512), 4) * (int64_t)sizeof(float), 256) + 256 : 256;
+    const TRowsPath path = t_rows_path(c, d, workspace != nullptr, workspace_bytes);     // the choice of the kernel: see there
+    const int64_t n_slot = path.n_slot, n_words = path.n_words, part_bytes = path.part_bytes;
     uint32_t *bitmap = nullptr;
     unsigned long long *counters = nullptr;
-    if (ngcf_opts().t_rows_bitmap && c->n_rows == c->n_cols && t_rows_lds_bytes(n_words) <= kTrLdsBytes && c->nnz >= (1 << 22) && workspace &&
-        d <= 512 * kTrPanels && workspace_bytes >= part_bytes + n_words * 4 + 1024) {
+    if (path.bitmap) {
         bitmap = reinterpret_cast<uint32_t *>(align_up((int64_t)(uintptr_t)workspace + part_bytes, 256));
         counters = reinterpret_cast<unsigned long long *>(align_up((int64_t)(uintptr_t)(bitmap + n_words), 256));   // one per panel
         slot_bitmap_kernel<<<(unsigned)((n_slot + 255) / 256), 256, 0, stream>>>(slot, n_slot, bitmap, n_words, counters, kTrPanels);

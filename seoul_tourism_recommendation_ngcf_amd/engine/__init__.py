@@ -18,7 +18,7 @@ from .groupby import (DECIMAL_MAX_CHARS, GROUPBY_FULL, GROUPBY_LDS_SLOTS, GROUPB
                       groupby_limits, groupby_packing)
 from .laplacian import LAPLACIAN_LONG_TABLES, build_laplacian_year, empty_laplacian_state, inverse_sqrt_degree, laplacian_limits
 from .layers import (LEAKY_SLOPE, bpr_loss, copy_rows, copy_rows_indexed, feature_inject, gather_rows, gather_rows3, layer_dense,
-                     layer_fused, spmm, spmm_t_rows)
+                     layer_fused, spmm, spmm_t_rows, spmm_t_rows_path)
 from .ranking import (BLEND_POINTS_MAX, BLEND_TOP_MAX, CAND_MAX, RANK_K_MAX, ItemSets, blend_points, candidate_metrics_from_sums,
                       eval_candidates, metrics_from_sums, rank_topk, ranking_metrics, recommend_topk, topk_rows)
 from .scaling import (QUANTILE_WAVE_MAX, segment_quantile_floor, segments_from_ids, yeo_johnson, yeo_johnson_launch,

@@ -70,6 +70,18 @@ def spmm_t_rows(csr_t: LaplacianCSR, slot: torch.Tensor, X: torch.Tensor, init: 
                                             float(p), _seed_array(seeds), len(seeds), _ptr(w), w.numel(), _stream()))
 
 
+def spmm_t_rows_path(csr_t: LaplacianCSR, d: int, ws: Workspace, device) -> str:
+    """'bitmap' or 'slot': the kernel `spmm_t_rows` would run on `csr_t` at width d with the scratch `ws` on `device` under the
+    current options (ngcf_spmm_t_rows_path: host code, nothing is launched; for tests and tools).  The workspace size asked about
+    is the one `spmm_t_rows` passes: that of `ws` once it holds ngcf_spmm_workspace_bytes(csr_t, min(d, 512)) bytes."""
+    lib = _lib.load()
+    w = ws.get(csr_t.spmm_workspace_bytes(min(int(d), 512)), device)
+    name = lib.ngcf_spmm_t_rows_path(csr_t._h, int(d), w.numel())
+    if name is None:
+        raise RuntimeError(_lib.last_error())
+    return name.decode()
+
+
 def layer_fused(csr: LaplacianCSR, E_gather: torch.Tensor, E_self: torch.Tensor, W1, b1, W2, b2,
                 carry: Optional[torch.Tensor], norm: torch.Tensor, ws: Workspace,
                 drop_p: float = 0.0, drop_seed: int = 0, drop_mask: Optional[torch.Tensor] = None):

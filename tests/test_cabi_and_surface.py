@@ -175,6 +175,20 @@ def test_bwd_dense_paths_name_the_kernels_the_dispatch_selects(lib_options):
     assert lib.ngcf_layer_bwd_input_path(10, 300, 64, 128, None) == b"staged_small" and lib.ngcf_layer_bwd_input_path(131072, 130, 64, 128, None) == b"narrow"
 
 
+def test_t_rows_path_is_declared_bound_and_rejects_what_the_entry_point_rejects():
+    """ngcf_spmm_t_rows_path (host code; what it answers for a real CSR: tests/test_t_rows_paths_gpu.py): the prototype, the
+    header's words for the option values, NULL + ngcf_last_error without a CSR."""
+    from seoul_tourism_recommendation_ngcf_amd import _lib, engine
+    lib = _lib.load()
+    assert _lib.PROTOTYPES["ngcf_spmm_t_rows_path"] == (C.c_char_p, [C.c_void_p, C.c_int, C.c_int64])
+    header = open(os.path.join(ROOT, "include", "ngcf_hip.h")).read()
+    assert re.search(r"const char \*ngcf_spmm_t_rows_path\(const ngcf_csr_t \*csr_t, int d, int64_t workspace_bytes\);", header)
+    assert "t_rows_bitmap = 2" in header and callable(engine.spmm_t_rows_path)
+    assert lib.ngcf_spmm_t_rows_path(None, 64, 1 << 20) is None and "spmm_t_rows_path" in _lib.last_error()
+    _lib.set_option("t_rows_bitmap", 2)                              # the value is accepted by name
+    _lib.options_from_env()
+
+
 @pytest.mark.parametrize("name", ["fwd_sigA_small", "fwd_sigC_demo", "fwd_sigB_y19", "fwd_130_128"])
 def test_state_dict_surface_matches_reference_checkpoints(name):
     from seoul_tourism_recommendation_ngcf_amd import NGCF

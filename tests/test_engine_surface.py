@@ -35,7 +35,7 @@ PUBLIC = CONSTANTS.keys() | {
     "gather_rows", "gather_rows3", "group_by", "groupby_hash", "groupby_limits", "groupby_packing", "inverse_sqrt_degree",
     "laplacian_limits", "layer_dense", "layer_fused", "metrics_from_sums", "rank_topk", "ranking_metrics", "recommend_topk",
     "sample_unseen", "segment_quantile_floor", "segments_from_ids", "select_key", "select_limits", "select_per_group", "shard_plan", "spmm",
-    "spmm_t_rows", "topk_rows", "yeo_johnson", "yeo_johnson_launch", "yeo_johnson_moments",
+    "spmm_t_rows", "spmm_t_rows_path", "topk_rows", "yeo_johnson", "yeo_johnson_launch", "yeo_johnson_moments",
 }
 
 # private names that the rest of the package, the tools and other tests reach as `engine.<name>`
@@ -118,6 +118,7 @@ SIGNATURES = {'ItemSets.__init__': "(self, rowptr: 'torch.Tensor', colidx: 'torc
  'spmm': "(csr: 'LaplacianCSR', E: 'torch.Tensor', out: 'Optional[torch.Tensor]' = None, ws: 'Optional[Workspace]' = None, edge_drop=None)",
  'spmm_t_rows': "(csr_t: 'LaplacianCSR', slot: 'torch.Tensor', X: 'torch.Tensor', init: 'Optional[torch.Tensor]', out: 'torch.Tensor', ws: "
                 "'Workspace', edge_drop=None)",
+ 'spmm_t_rows_path': "(csr_t: 'LaplacianCSR', d: 'int', ws: 'Workspace', device) -> 'str'",
  'topk_rows': "(scores: 'torch.Tensor', k: 'int')",
  'yeo_johnson': "(x: 'torch.Tensor', lam: 'float', out: 'Optional[torch.Tensor]' = None) -> 'torch.Tensor'",
  'yeo_johnson_launch': "(T: 'int')",
