@@ -302,6 +302,46 @@ int ngcf_bpr_fused_f32(const float *u, int64_t Bu, const float *p, int64_t Bp, c
                        int D, float weight_decay, float batch_size, float *loss,
                        void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- BPR, m negatives per positive (csrc/bpr_multi.hip) -------------------------------------- */
+/*
+ * The loss of a batch whose every positive row is scored against m negatives, without expanding the batch to B*m triplets.
+ * u: [B, D], p: [B, D], n: [B*m, D], fp32 and contiguous; rows b*m .. b*m + m - 1 of n are the negatives of row b.  Nothing
+ * broadcasts: Bu == Bp == B >= 1, Bn == B*m, 1 <= m <= NGCF_BPR_MULTI_M_MAX, D >= 1; anything else is NGCF_ERR_ARG before any
+ * launch.  Per row, with the reference's abs around both scores (bprloss.py:18):
+ *   sp = |u_b.p_b|,  sn_j = |u_b.n_bj|
+ *   reduction NGCF_BPR_MULTI_MEAN     l_b = -(1/m) sum_j logsigmoid(sp - sn_j)
+ *   reduction NGCF_BPR_MULTI_SOFTMAX  l_b = -logsigmoid(sp - lse_b),  lse_b = M + log(sum_j exp(sn_j - M)),  M = max_j sn_j
+ *                                     (= -log(e^sp / (e^sp + sum_j e^sn_j)), finite for scores of several hundred)
+ *   loss = (sum_b l_b + wd*(sum|u|^2 + sum|p|^2 + (1/m) sum|n|^2)) / batch_size
+ * Two identities fix the choices.  (a) With m = 1, MEAN is ngcf_bpr_fused_f32 / ngcf_bpr_backward_f32 bit for bit, loss and all
+ * three gradients: the dot products are fmaf over the lanes' columns (stride 64) and a wave sum, a row's term is
+ * -logsigmoid(|u.p| - |u.n|), four rows make a workgroup partial (sh[0]+sh[2])+(sh[4]+sh[6]) and the second stage is the same code.
+ * (b) MEAN at any m is, mathematically, ngcf_bpr_fused_f32 over the B*m expanded triplets (u and p rows repeated m times) with
+ * batch_size*m; only the order of the sums differs.
+ * Gradients, times *grad_out / batch_size, with sgn(0) = 0 like torch.abs:
+ *   a_j = dl_b/dsn_j   MEAN     (1/m) / (1 + exp(sp - sn_j))
+ *                      SOFTMAX  exp(sn_j - M') / (exp(sp - M') + sum_k exp(sn_k - M')),  M' = max(sp, M)
+ *   A   = sum_j a_j
+ *   du_b  = 2 wd u_b + sum_j a_j (sgn_nj n_bj - sgn_p p_b)      (four chains like ngcf_segment_sum_rows_f32: chain q takes the
+ *                                                               negatives j = q mod 4 ascending, one fma each, chain 0 starts from
+ *                                                               the weight-decay term; combined (c0 + c1) + (c2 + c3))
+ *   dp_b  = -A sgn_p u_b + 2 wd p_b
+ *   dn_bj = a_j sgn_nj u_b + (2 wd / m) n_bj
+ * One wave per positive row, four per workgroup; lane j keeps sn_j and a_j (hence m <= 64); the backward recomputes the scores.
+ * No atomics and no host synchronisation: results are identical from run to run and both calls can be captured in a hipGraph.
+ * `loss` is one device float; workspace: ngcf_bpr_multi_workspace_bytes(B) bytes (NGCF_ERR_WORKSPACE when shorter).
+ */
+#define NGCF_BPR_MULTI_M_MAX 64
+#define NGCF_BPR_MULTI_MEAN 0
+#define NGCF_BPR_MULTI_SOFTMAX 1
+int64_t ngcf_bpr_multi_workspace_bytes(int64_t B);
+int ngcf_bpr_multi_f32(const float *u, int64_t Bu, const float *p, int64_t Bp, const float *n, int64_t Bn, int m, int D,
+                       int reduction, float weight_decay, float batch_size, float *loss, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+int ngcf_bpr_multi_backward_f32(const float *u, int64_t Bu, const float *p, int64_t Bp, const float *n, int64_t Bn, int m, int D,
+                                int reduction, float weight_decay, float batch_size, const float *grad_out, float *du,
+                                float *dp, float *dn, void *stream);
+
 /* ---- backward pass (`loss.backward()` of experiment.py:57; driven by autograd.py) -------------- */
 /* Everything `loss.backward()` runs: no library GEMM at any width.  L^T.dLE re-uses ngcf_spmm_csr_f32 on the CSR of L^T. */
 /* du/dp/dn of the BPR loss (bprloss.py:15-22) times the upstream scalar *grad_out (device). */

@@ -1,7 +1,7 @@
 """Forward drivers of the propagation engine and the autograd seam for training.
 
 `propagate_forward` issues the HIP layer kernels for NGCF.py:120-147 (inference path, nothing saved).
-`Propagate` / `GatherTriple` / `BPRLoss` are `torch.autograd.Function`s so that `loss.backward()`
+`Propagate` / `GatherTriple` / `BPRLoss` / `BPRMultiLoss` are `torch.autograd.Function`s so that `loss.backward()`
 (experiment.py:57) reaches every parameter: their backward runs the HIP kernels of the "backward pass" section
 of include/ngcf_hip.h - weight and input gradients on the fp32 matrix cores, `L^T . dLE` on the SpMM kernels; no library
 GEMM at any width.
@@ -489,6 +489,23 @@ class BPRLoss(torch.autograd.Function):
             _lib.check(lib.ngcf_bpr_backward_f32(_ptr(u), u.shape[0], _ptr(p), p.shape[0], _ptr(n), n.shape[0], u.shape[1],
                                                  ctx.wd, ctx.bs, _ptr(g), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
         return du, dp, dn, None, None, None
+
+
+class BPRMultiLoss(torch.autograd.Function):
+    """BPR against m negatives per positive row (engine.losses) with its gradient kernel."""
+
+    @staticmethod
+    def forward(ctx, u, p, n, m, weight_decay, batch_size, ws, reduction):
+        u, p, n = u.contiguous(), p.contiguous(), n.contiguous()
+        ctx.m, ctx.wd, ctx.bs, ctx.reduction = int(m), float(weight_decay), float(batch_size), reduction
+        ctx.save_for_backward(u, p, n)
+        return _eng.losses.bpr_multi_loss(u, p, n, m, weight_decay, batch_size, ws, reduction)
+
+    @staticmethod
+    def backward(ctx, g):
+        u, p, n = ctx.saved_tensors
+        du, dp, dn = _eng.losses.bpr_multi_backward(u, p, n, ctx.m, ctx.wd, ctx.bs, g.to(torch.float32).contiguous(), ctx.reduction)
+        return du, dp, dn, None, None, None, None, None
 
 
 def propagate_with_grad(owner, csrs, csrs_t_fn, user_w, item_w, w1, b1, w2, b2, drop, seeds, edge_drops=None,

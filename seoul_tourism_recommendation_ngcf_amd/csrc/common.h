@@ -404,7 +404,33 @@ __device__ inline float log_sigmoid(float x)       // F.logsigmoid (bprloss.py:1
     return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
 }
 
-__device__ inline uint32_t float_key(float x)      // monotone map float -> uint32 (larger float = larger key, NaN above +inf)
+// The second stage of both BPR losses (ops.hip, bpr_multi.hip), one workgroup of 256: the workgroups' partials
+// part[2*i] = -sum logsigmoid, part[2*i + 1] = sum of squares in a fixed order -> *loss (bprloss.py:20-22).
+__device__ inline void bpr_finish_block(const float *__restrict__ part, int64_t n_blocks, float wd, float batch_size,
+                                        float *__restrict__ loss)
+{
+    __shared__ float sh[8];
+    float nl = 0.f, sq = 0.f;
+    for (int64_t i = threadIdx.x; i < n_blocks; i += 256) {
+        nl += part[2 * i];
+        sq += part[2 * i + 1];
+    }
+    nl = wave_sum(nl);
+    sq = wave_sum(sq);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        sh[wave * 2] = nl;
+        sh[wave * 2 + 1] = sq;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float a = (sh[0] + sh[2]) + (sh[4] + sh[6]);
+        const float b = (sh[1] + sh[3]) + (sh[5] + sh[7]);
+        *loss = (a + wd * b) / batch_size;                          // bprloss.py:20-22
+    }
+}
+
+__device__ inline uint32_t float_key(float x)     // monotone map float -> uint32 (larger float = larger key, NaN above +inf)
 {
     const uint32_t u = __float_as_uint(x);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);

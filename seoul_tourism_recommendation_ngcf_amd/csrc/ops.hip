@@ -323,25 +323,7 @@ __global__ __launch_bounds__(256) void bpr_rows_kernel(const float *__restrict__
 __global__ __launch_bounds__(256) void bpr_finish_kernel(const float *__restrict__ part, int64_t n_blocks, float wd,
                                                          float batch_size, float *__restrict__ loss)
 {
-    __shared__ float sh[8];
-    float nl = 0.f, sq = 0.f;
-    for (int64_t i = threadIdx.x; i < n_blocks; i += 256) {
-        nl += part[2 * i];
-        sq += part[2 * i + 1];
-    }
-    nl = wave_sum(nl);
-    sq = wave_sum(sq);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-        sh[wave * 2] = nl;
-        sh[wave * 2 + 1] = sq;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float a = (sh[0] + sh[2]) + (sh[4] + sh[6]);
-        const float b = (sh[1] + sh[3]) + (sh[5] + sh[7]);
-        *loss = (a + wd * b) / batch_size;                          // bprloss.py:20-22
-    }
+    bpr_finish_block(part, n_blocks, wd, batch_size, loss);         // (common.h: shared with bpr_multi.hip)
 }
 
 extern "C" int64_t ngcf_bpr_workspace_bytes(int64_t R)

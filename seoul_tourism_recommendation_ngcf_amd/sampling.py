@@ -192,3 +192,74 @@ class HardTripletLoader:
             table = table[:, perm[:used]]                                       # the epoch's one gathered copy
         for b0 in range(0, used, self.batch_size):
             yield tuple(table[:, b0:b0 + self.batch_size].unbind(0))
+
+
+def train_negatives(users: torch.Tensor, items: torch.Tensor, seen: Optional[engine.ItemSets] = None, *, m: int, seed: int,
+                    epoch: int = 0, n_user: int, n_item: int):
+    """`train_triplets` with `m` negatives per positive row, for a `BPRMulti` criterion: returns (users, items, neg) with `neg` int64
+    [T, m], row t the m distinct items of row t of `engine.sample_unseen(seen, users, m, seed_e)`, seed_e = fmix(seed + epoch) as in
+    `train_triplets` - so with m = 1 `neg[:, 0]` is `train_triplets`' column.  `model(..., neg_item=neg[b].reshape(-1))` gathers
+    the rows in the order `BPRMulti` reads them.  A user id outside the sets raises IndexError, a user with fewer than `m` unseen
+    items ValueError."""
+    users, items, seen = _rows(users, items, seen, n_user, n_item, "train_negatives")
+    return users, items, engine.sample_unseen(seen, users, int(m), fmix(int(seed) + int(epoch)))
+
+
+class NegativesLoader:
+    """`TripletLoader` with `m` negatives per row, redrawn every epoch: the batch protocol, `columns`, `shuffle`, `drop_last` and
+    `generator` are `TripletLoader`'s, and a batch is `(*columns[b], items[b], neg[b].reshape(-1))` - `batch_size` ids per column,
+    `batch_size * m` negative ids, the m of a row next to each other - so the loop body of `Experiment.train` runs against it
+    unchanged with `criterion = BPRMulti(weight_decay, batch_size, m)`.  Every `iter()` draws all negatives with epoch e = 0, 1, 2, ...
+    (`.epoch` is the number of the next one): `neg` = `train_negatives(users, items, seen, m=m, seed=seed, epoch=e, ...)[2]`,
+    written straight into the loader's row table, then one `torch.randperm` and one gather of that table's rows; the batches are
+    views of the gathered copy.  `seen` (default: `ItemSets.from_pairs(users, items, users.max() + 1, items.max() + 1)`, the
+    positives themselves over the ids that occur, which costs one host sync at construction) says what counts as seen and how
+    large the catalogue is: pass sets over the full catalogue when some items have no positive row."""
+
+    def __init__(self, users: torch.Tensor, items: torch.Tensor, columns: Sequence[torch.Tensor] = (), *, batch_size: int, m: int,
+                 seed: int, shuffle: bool = True, drop_last: bool = True, generator: Optional[torch.Generator] = None,
+                 seen: Optional[engine.ItemSets] = None):
+        cols = list(columns) if len(columns) else [users]
+        cols += [items]
+        n = int(users.numel())
+        for c in [users] + cols:
+            if c.dim() != 1 or int(c.numel()) != n:
+                raise ValueError(f"NegativesLoader: every column must be [n = {n}], got {tuple(c.shape)}")
+            if c.device != users.device:
+                raise RuntimeError(f"NegativesLoader: a column is on {c.device}, users on {users.device}")
+        if int(batch_size) < 1:
+            raise ValueError(f"NegativesLoader: batch_size={batch_size}")
+        if int(m) < 1 or int(m) > engine.losses.M_MAX:
+            raise ValueError(f"NegativesLoader: m={m} outside [1, {engine.losses.M_MAX}]")
+        engine._require_device(users, "users")
+        self.n_columns, self.m = len(cols), int(m)
+        self.table = torch.empty((n, self.n_columns + self.m), dtype=torch.int64, device=users.device)     # [n, columns | negatives]
+        torch.stack([c.to(torch.int64) for c in cols], dim=1, out=self.table[:, :self.n_columns])
+        self.users = users.to(torch.int64).contiguous()
+        if seen is None and n:
+            seen = engine.ItemSets.from_pairs(self.users, self.table[:, self.n_columns - 1].contiguous(),
+                                              int(self.users.max()) + 1, int(self.table[:, self.n_columns - 1].max()) + 1)
+        self.seen = seen
+        self.n, self.batch_size = n, int(batch_size)
+        self.seed, self.epoch = int(seed), 0
+        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
+
+    def __len__(self) -> int:
+        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
+
+    def __iter__(self):
+        if self.n:
+            engine.sample_unseen(self.seen, self.users, self.m, fmix(self.seed + self.epoch), out=self.table[:, self.n_columns:])
+        self.epoch += 1
+        return self._batches()
+
+    def _batches(self):
+        used = len(self) * self.batch_size if self.drop_last else self.n
+        rows = self.table[:used]
+        if self.shuffle:
+            perm = torch.randperm(self.n, generator=self.generator, device=rows.device)
+            rows = self.table[perm[:used]]                                      # the epoch's one gathered copy
+        cols = rows[:, :self.n_columns].t().contiguous()                        # [columns, used]: a batch's ids are contiguous views
+        neg = rows[:, self.n_columns:].contiguous()                             # [used, m]
+        for b0 in range(0, used, self.batch_size):
+            yield tuple(cols[:, b0:b0 + self.batch_size].unbind(0)) + (neg[b0:b0 + self.batch_size].reshape(-1),)
