@@ -676,6 +676,51 @@ int ngcf_yeo_johnson_moments_launch(int64_t T, int *blocks, int *threads, int *m
 int ngcf_yeo_johnson_moments_f64(const double *x, int64_t T, double lambda, double *result, void *workspace, int64_t workspace_bytes,
                                  void *stream);
 
+/* ---- beyond-accuracy figures of top lists (csrc/list_quality.hip) ----
+ * What the lists are made of, next to how accurate they are.  A list is a row of top_idx (int64, row pitch ld >= k: a column slice of
+ * a wider tensor works), its first k columns best first - ngcf_rank_topk_f32's out_idx, ngcf_blend_points' out_items.  A negative
+ * entry is an empty slot wherever it stands.  An entry >= n_items sets bit 0 (value 1) of *status; it is compared before anything
+ * else is done with it and is never used as an index (the slot then counts as empty).  n_items < 2^31.
+ *
+ * Exposure: counts[i] += the number of entries equal to i in columns [0, k) of all B rows (counts: int64[n_items], ADDED to, so a
+ * user set can be counted in chunks).  Integer atomics only: identical from run to run.  Up to NGCF_EXPOSURE_LDS_ITEMS items (a
+ * constant of the source file) every workgroup folds its slice of at most 2^30 entries into an int32 table in LDS and adds the
+ * non-zero slots with one 64-bit atomic each; above it every entry is one 64-bit atomic in memory.  Same counts either way.
+ * B * k <= 2^40. */
+int ngcf_list_exposure(const int64_t *top_idx, int64_t ld, int64_t B, int k, int64_t n_items, int64_t *counts, int32_t *status,
+                       void *stream);
+/* Summary of an exposure histogram.  sorted_counts: the n_items counts in ascending order c_(1) <= .. <= c_(n) (the caller sorts);
+ * counts, popularity (int64[n_items], both or neither; with them n_user >= 1): the same counts in item order and the items'
+ * popularity.  out (device, int64[6]):
+ *   out[0] covered  = #{c_i > 0}                     out[1] total = sum c_i               out[2] weighted = sum_{i=1..n} i * c_(i)
+ *   out[3] status   : bit 0 (value 1) n_items * total >= 2^62, weighted is then not computed (0); bit 1 (value 2) a negative count
+ *   out[4] the bits of the double clog = sum c_i * log2(c_i), a term with c_i = 0 being 0
+ *   out[5] the bits of the double nov  = sum c_i * (log2(n_user) - log2(max(pop_i, 1))), 0 without popularity
+ * The integers are exact.  In the two doubles log2 is the correctly rounded one of csrc/dd_log2.h, every operation is rounded on its
+ * own (no FMA), and the terms are added in a fixed tree - a thread its strided elements in ascending order, a wave, a workgroup, one
+ * workgroup the blocks; no float atomics - on a grid that depends on n_items alone: bit-identical from run to run.  From these:
+ * coverage = covered / n, gini = 2 weighted / (n total) - (n + 1) / n, entropy = log2(total) - clog / total, novelty = nov / total. */
+int ngcf_exposure_summary(const int64_t *sorted_counts, const int64_t *counts, const int64_t *popularity, int64_t n_items,
+                          int64_t n_user, int64_t *out, void *stream);
+/* Intra-list diversity: the mean cosine distance of the item pairs of a list, at up to 8 cut-offs ks_host[0..n_ks) (HOST int32,
+ * 2 <= K <= min(k, NGCF_LIST_DIV_K_MAX)) from one pass.  items [n_items, D] fp32, row pitch ldi >= D (a row range of all_E, unaligned
+ * rows: 16-byte loads where the pointer and the pitch allow them, dword loads elsewhere, the same bits either way); any D >= 1.
+ * Per row, with e_a the item row of column a:
+ *   G_ab   = sum_k e_a[k] * e_b[k] in fp32 as ONE ascending-k fmaf chain from 0 (the score of ngcf_rank_topk_f32; fp32 MFMA), so its
+ *            bits do not depend on the tiling, on B or on the row order, and G_ab = G_ba
+ *   cos_ab = (double)G_ab / sqrt((double)G_aa * (double)G_bb), every fp64 operation rounded once, no FMA; 0 where the product under the
+ *            root is 0; a NaN propagates.  d_ab = 1.0 - cos_ab
+ *   s_b    = sum_{a < b} d_ab over the a whose slot and b's are not empty, added in ascending a from 0.0
+ *   S_K    = sum_{b < K} s_b over the b whose slot is not empty, added in ascending b from 0.0 - every cut-off is a prefix of one chain
+ *   V_K    = the number of non-empty slots in columns [0, K);   ild@K = S_K / (double)(V_K (V_K - 1) / 2)
+ * A row with V_K < 2 is not evaluated at K: its value is 0 and it is not counted.  per_user (float64 [B, n_ks], may be NULL) gets the
+ * per-row values; sums (device, float64 [2 n_ks]) = [sum of ild@K per K, rows counted at K per K] is ADDED to in a fixed order (a wave
+ * its run of consecutive rows in order, a workgroup its four waves, one workgroup the blocks, on a launch shape that depends on B
+ * alone): bit-identical from run to run.  Nothing of size [B, k, D] or [B, k, k] is written to memory. */
+#define NGCF_LIST_DIV_K_MAX 64
+int ngcf_list_diversity_f32(const int64_t *top_idx, int64_t ld, int64_t B, int k, const float *items, int64_t ldi, int64_t n_items,
+                            int D, const int32_t *ks_host, int n_ks, double *per_user, double *sums, int32_t *status, void *stream);
+
 /* ---- year-slice Laplacians straight into CSR (csrc/laplacian.hip; the reference's Matrix.create_matrix, matrix.py:12-83) ----
  * What matrix.laplacian_slices computes, with the state of R kept between years as a user-sorted CSR (rowptr int64[n_user + 1],
  * item int32, rating fp32) instead of a sorted key list.  Years are taken in order of first appearance; within a year the last

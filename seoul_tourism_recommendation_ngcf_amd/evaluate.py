@@ -4,7 +4,8 @@ top lists against held-out items (Recall / NDCG / precision / hit rate @K).
 The reference ranks with `torch.topk(torch.mm(u, all_items_emb.T), k)` (demo.py:233-235) and computes its metrics as host-side
 bookkeeping (experiment.py:66-133); here both run on the device (engine.rank_topk, engine.ranking_metrics) and the host reads one
 vector back at the end.  `full_ranks` goes past the top list: the exact position of every held-out item (engine.ranks) and MRR, MAP,
-AUC and the @K metrics for any K from those positions.
+AUC and the @K metrics for any K from those positions.  `list_quality` says what the top lists are made of: coverage, Gini, entropy
+and novelty of the items' exposure and the intra-list diversity (engine.lists).
 
 The reference's own test protocol - one user against a short candidate list whose first entry is the held-out item, Test-BPR / HR@3 /
 NDCG@ks / RMSE (Experiment.eval, experiment.py:66-119) - is `candidate_ranking`: one propagation per year and one launch per chunk
@@ -102,6 +103,75 @@ def full_ranks(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), year
                 raise IndexError(f"full_ranks: a user id lies outside [0, {n_user}) or a held-out item outside [0, {n_item})")
             out = engine.ranks.position_metrics_from_sums(host[:-1], ks)
             return (out, position, truth) if return_positions else out
+    finally:
+        model.train(was_training)
+
+
+def list_quality(model, train: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0, user_ids: Optional[torch.Tensor] = None,
+                 user_chunk: int = 65536, lists: Optional[torch.Tensor] = None) -> dict:
+    """What the top-K lists are made of, next to `full_ranking`'s accuracy: for every K in `ks` the catalogue coverage, the Gini
+    coefficient and the entropy (bits) of the items' exposure, the novelty (mean log2(n_user / popularity) of the shown entries,
+    popularity = the items' degree in `train`) and the intra-list diversity `ild` (mean cosine distance of the item pairs of a list,
+    averaged over the lists with at least two entries; NaN for K > 64, the diversity kernel's limit, and when no list has two).
+    The lists are `engine.rank_topk`'s for `user_ids` (default: all users) with the user's `train` items excluded, `user_chunk`
+    users per launch; with `lists` (int64 [G, >= max(ks)], -1 = empty slot: e.g. `blended_ranking`'s `out_items`) they are taken as
+    given and nothing is ranked.  One propagate in eval mode under no_grad, the caller's mode restored; everything is accumulated on
+    the device (engine.lists) and read back once.  Returns {K: {"coverage", "gini", "entropy", "novelty", "ild", "users"}}, `users`
+    = the number of lists."""
+    ks = [int(x) for x in ks]
+    if not ks or min(ks) < 1:
+        raise ValueError(f"list_quality: cut-offs {ks}")
+    div_ks = [K for K in ks if 2 <= K <= engine.lists.DIVERSITY_K_MAX]
+    if len(div_ks) > engine.lists.DIVERSITY_KS_MAX:
+        raise ValueError(f"list_quality: at most {engine.lists.DIVERSITY_KS_MAX} cut-offs up to {engine.lists.DIVERSITY_K_MAX}")
+    k = max(ks)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            model.propagate(year_idx)
+            U, I = model.all_users_emb, model.all_items_emb
+            dev = U.device
+            n_user, n_item = int(U.shape[0]), int(I.shape[0])
+            excl = _as_sets(train, n_user, n_item, dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            popularity = engine.lists.exposure_counts((excl.colidx.to(torch.int64) - excl.col_offset).reshape(-1, 1), n_item,
+                                                      status=status)
+            counts = [torch.zeros(n_item, dtype=torch.int64, device=dev) for _ in ks]
+            div = torch.zeros(2 * len(div_ks), dtype=torch.float64, device=dev)
+
+            def add(top):
+                for K, c in zip(ks, counts):
+                    engine.lists.exposure_counts(top, n_item, k=K, out=c, status=status)
+                if div_ks:
+                    engine.lists.list_diversity(top, I, div_ks, sums=div, status=status)
+
+            if lists is not None:
+                lists = lists.to(device=dev, dtype=torch.int64)
+                if lists.dim() != 2 or int(lists.shape[1]) < k:
+                    raise ValueError(f"list_quality: lists must be [G, >= {k}], got {tuple(lists.shape)}")
+                n_lists = int(lists.shape[0])
+                add(lists)
+            else:
+                if user_ids is None:
+                    user_ids = torch.arange(n_user, device=dev, dtype=torch.int64)
+                user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64)
+                n_lists = int(user_ids.numel())
+                for c0 in range(0, n_lists, int(user_chunk)):
+                    _, top = engine.rank_topk(U, I, k, user_ids=user_ids[c0:c0 + int(user_chunk)], exclude=excl, status=status)
+                    add(top)
+            words = [engine.lists.exposure_summary_launch(c, popularity, n_user) for c in counts]
+            host = torch.cat(words + [div.view(torch.int64), status.to(torch.int64)]).cpu()          # the one read-back
+            if int(host[-1]) != 0:
+                raise IndexError(f"list_quality: a user id lies outside [0, {n_user}) or a list entry is not below {n_item}")
+            means = engine.lists.diversity_from_sums(host[6 * len(ks):-1].view(torch.float64), div_ks) if div_ks else {}
+            out = {}
+            for q, K in enumerate(ks):
+                fig = engine.lists.exposure_figures(host[6 * q:6 * q + 6].tolist(), n_item)
+                out[K] = {name: fig[name] for name in ("coverage", "gini", "entropy", "novelty")}
+                out[K]["ild"] = means.get(f"ild@{K}", float("nan"))
+                out[K]["users"] = n_lists
+            return out
     finally:
         model.train(was_training)
 
