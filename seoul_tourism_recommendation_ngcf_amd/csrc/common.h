@@ -399,7 +399,50 @@ __device__ inline float wave_sum(float x)
     return x;
 }
 
-__device__ inline float log_sigmoid(float x)       // F.logsigmoid (bprloss.py:19)
+// the same xor butterfly (32, 16, .., 1) for the other types the evaluation kernels reduce; every lane ends with the result
+__device__ inline int wave_sum(int x)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+__device__ inline double wave_sum(double x)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+__device__ inline int wave_min(int x)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int y = __shfl_xor(x, m);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+// 64-bit values across lanes, as two 32-bit shuffles: from lane `src`, and from lane (own ^ m)
+__device__ inline int64_t shfl_i64(int64_t x, int src)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src), hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)x >> 32), src);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ inline unsigned long long shfl_xor_u64(unsigned long long x, int m)
+{
+    const uint32_t lo = __shfl_xor((uint32_t)x, m), hi = __shfl_xor((uint32_t)(x >> 32), m);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ inline double shfl_xor_f64(double x, int m)
+{
+    return __longlong_as_double((long long)shfl_xor_u64((unsigned long long)__double_as_longlong(x), m));
+}
+
+__device__ inline float log_sigmoid(float x)      // F.logsigmoid (bprloss.py:19)
 {
     return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
 }

@@ -43,13 +43,6 @@ struct CandParams {                         // by value: stays in the kernarg se
 // LDS floats of one wave: the user row (whole quads), C scores, C squared norms; a multiple of 4, so every wave's row is 16-byte aligned
 __host__ __device__ inline int cand_wave_floats(int Dp, int C) { return Dp + ((2 * C + 3) & ~3); }
 
-__device__ inline double wave_sum_f64(double x)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
-
 template <bool VEC, bool ULDS>
 __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kernel(
     const float *__restrict__ users, int64_t ldu, int64_t n_user_rows, const float *__restrict__ items, int64_t ldi, int64_t n_items,
@@ -139,10 +132,9 @@ __global__ __launch_bounds__(64 * NGCF_CAND_WAVES, 4) void eval_candidates_kerne
                 sq += (double)sn[n];
             }
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) above += __shfl_xor(above, m);
-        nl = wave_sum_f64(nl);
-        sq = wave_sum_f64(sq) + (double)prm.user_repeat * (double)uu + (double)sn[0];
+        above = wave_sum(above);
+        nl = wave_sum(nl);
+        sq = wave_sum(sq) + (double)prm.user_repeat * (double)uu + (double)sn[0];
         if (lane == 0) {
             if (position) position[t] = above;
             if (above < prm.hit_k) acc[0] += 1.0;

@@ -1,7 +1,7 @@
 // Beyond-accuracy figures of top lists: how often every item is shown (exposure counts), what the exposure histogram
 // looks like (coverage, Gini, entropy, novelty from five reduced numbers) and how different the items within one list are
 // (intra-list diversity from the lists' Gram matrices).  The definitions and operation orders are in include/ngcf_hip.h.
-#include "common.h"
+#include "rank_device.h"
 #include "dd_log2.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -88,17 +88,6 @@ struct SummaryAcc {
     unsigned long long covered, total, weighted, bad;
     double clog, nov;
 };
-
-__device__ inline unsigned long long shfl_xor_u64(unsigned long long x, int m)
-{
-    const uint32_t lo = __shfl_xor((uint32_t)x, m), hi = __shfl_xor((uint32_t)(x >> 32), m);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ inline double shfl_xor_f64(double x, int m)
-{
-    return __longlong_as_double((long long)shfl_xor_u64((unsigned long long)__double_as_longlong(x), m));
-}
 
 // wave, then workgroup: the result in thread 0
 __device__ inline SummaryAcc summary_block_reduce(SummaryAcc a)
@@ -431,17 +420,6 @@ __global__ __launch_bounds__(256) void list_diversity_kernel(const int64_t *__re
     }
 }
 
-__global__ __launch_bounds__(64) void list_diversity_finish_kernel(const double *__restrict__ part, int64_t n_blocks, int n_slots,
-                                                                   double *__restrict__ sums)
-{
-#pragma clang fp contract(off) reassociate(off)
-    const int s = threadIdx.x;
-    if (s >= n_slots) return;
-    double a = 0.0;
-    for (int64_t blk = 0; blk < n_blocks; ++blk) a += part[blk * n_slots + s];
-    sums[s] += a;
-}
-
 }  // namespace
 
 extern "C" int ngcf_list_diversity_f32(const int64_t *top_idx, int64_t ld, int64_t B, int k, const float *items, int64_t ldi,
@@ -468,25 +446,16 @@ extern "C" int ngcf_list_diversity_f32(const int64_t *top_idx, int64_t ld, int64
     const int64_t rows_per_wave = (B + blocks_want * 4 - 1) / (blocks_want * 4);
     const int64_t blocks = (B + rows_per_wave * 4 - 1) / (rows_per_wave * 4);
     const int n_slots = 2 * n_ks;
-    void *part = nullptr;
-    HIP_TRY(hipMallocAsync(&part, sizeof(double) * (size_t)(blocks * n_slots), stream));
     const bool vec = aligned16(items) && ldi % 4 == 0;
+    return launch_with_partial_sums("list_diversity", blocks, n_slots, sums, stream, [&](double *part) {
 #define NGCF_LIST_DIV_LAUNCH(NB_, VEC_)                                                                                           \
     list_diversity_kernel<NB_, VEC_><<<dim3((unsigned)blocks), 256, 0, stream>>>(top_idx, ld, B, k_used, items, ldi, n_items, D, n_ks, ks, \
-                                                                                rows_per_wave, per_user, static_cast<double *>(part), \
-                                                                                status)
-    if (k_used <= 32) {
-        if (vec) NGCF_LIST_DIV_LAUNCH(1, true); else NGCF_LIST_DIV_LAUNCH(1, false);
-    } else {
-        if (vec) NGCF_LIST_DIV_LAUNCH(2, true); else NGCF_LIST_DIV_LAUNCH(2, false);
-    }
+                                                                                rows_per_wave, per_user, part, status)
+        if (k_used <= 32) {
+            if (vec) NGCF_LIST_DIV_LAUNCH(1, true); else NGCF_LIST_DIV_LAUNCH(1, false);
+        } else {
+            if (vec) NGCF_LIST_DIV_LAUNCH(2, true); else NGCF_LIST_DIV_LAUNCH(2, false);
+        }
 #undef NGCF_LIST_DIV_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        list_diversity_finish_kernel<<<1, 64, 0, stream>>>(static_cast<double *>(part), blocks, n_slots, sums);
-        e = hipGetLastError();
-    }
-    (void)hipFreeAsync(part, stream);
-    if (e != hipSuccess) return fail(NGCF_ERR_HIP, "list_diversity: kernel launch failed: %s", hipGetErrorString(e));
-    return NGCF_OK;
+    });
 }

@@ -1,6 +1,8 @@
 // Full-catalogue ranking: score every item for every user with fp32 MFMA and keep a streaming top-k per user, never writing the
 // score matrix.  Plus the held-out metrics of the NGCF protocol (Recall / NDCG / precision / hit rate @K) on the device.
-#include "common.h"
+// The (key, item) order, the item split, the row search and the fixed-order sums are rank_device.h's, which rank_position.hip
+// shares; the score-tile walk below is restated in pos_scan_kernel there, and why, in DESIGN 4.3.15.
+#include "rank_device.h"
 
 // ---------------------------------------------------------------------------------------------
 // Tiling.  A workgroup = 4 waves owns UT = 32*UB user rows and walks its item range in tiles of IT = 128 items; wave w computes
@@ -17,32 +19,9 @@
 // raise the threshold), so the buffer never overflows.  Exclusions: one thread per user walks the user's ascending exclusion list
 // with a cursor, one item tile at a time, into a 128-bit mask.
 // ---------------------------------------------------------------------------------------------
-#define NGCF_RANK_IT 128
-#define NGCF_RANK_TK 32
 #define NGCF_RANK_KMAX 256
 
 namespace {
-
-typedef float rank_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr uint32_t kPadKey = 0u;            // below every score key but the one NaN pattern 0xffffffff (which ties it)
-constexpr int32_t kPadIdx = 0x7fffffff;      // ... and then loses on the item index
-
-__device__ inline uint32_t rank_key(float x)      // float_key of ops.hip: larger float = larger key, NaN above +inf
-{
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ inline float rank_unkey(uint32_t k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ inline bool rank_before(uint32_t ka, int32_t ia, uint32_t kb, int32_t ib)   // a precedes b in the output order
-{
-    return ka > kb || (ka == kb && ia < ib);
-}
 
 // Compaction of the users listed in flist[0..nf): sort each one's CAPP pairs (positions >= count hold padding), keep the best k,
 // pad the rest, set the threshold.  All threads of the workgroup take part; one barrier per bitonic stage.
@@ -61,7 +40,7 @@ __device__ void rank_compact(uint32_t *bk, int32_t *bi, uint32_t *cnt, uint32_t 
                 const bool desc = (a & size) == 0;
                 const uint32_t ka = K[a], kb = K[b];
                 const int32_t ia = I[a], ib = I[b];
-                if (rank_before(ka, ia, kb, ib) != desc) {
+                if (pair_before(ka, ia, kb, ib) != desc) {
                     K[a] = kb; K[b] = ka;
                     I[a] = ib; I[b] = ia;
                 }
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(const float *__restrict_
                                                         int64_t excl_off, float *__restrict__ out_val, int64_t *__restrict__ out_idx,
                                                         uint32_t *__restrict__ part_key, int32_t *__restrict__ part_idx, int32_t *status)
 {
-    constexpr int UT = 32 * UB, IT = NGCF_RANK_IT, TK = NGCF_RANK_TK, SLD = TK + 1;
+    constexpr int UT = 32 * UB, IT = kRankIT, TK = kRankTK, SLD = TK + 1;
     constexpr int CAPP = UB == 2 ? 256 : 512;                    // >= k + IT for every k this tile size is used for
     constexpr int NI = IT * TK / 256, NU = UT * TK / 256;        // global loads per thread and chunk
     __shared__ float sI[IT * SLD];
@@ -223,8 +202,8 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(const float *__restrict_
                 const int il = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
                 const int64_t gi = i0 + il;
                 if (gi >= i_end || ((exm[u * (IT / 32) + (il >> 5)] >> (il & 31)) & 1u)) continue;
-                const uint32_t key = rank_key(acc[ub][e]);
-                if (rank_before(key, (int32_t)gi, tk, ti)) {
+                const uint32_t key = float_key(acc[ub][e]);
+                if (pair_before(key, (int32_t)gi, tk, ti)) {
                     const uint32_t pos = atomicAdd(&cnt[u], 1u);
                     bk[u * CAPP + pos] = key;
                     bi[u * CAPP + pos] = (int32_t)gi;
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(const float *__restrict_
             part_key[o] = key;
             part_idx[o] = idx;
         } else {
-            out_val[b * k + j] = has ? rank_unkey(key) : -INFINITY;
+            out_val[b * k + j] = has ? float_unkey(key) : -INFINITY;
             out_idx[b * k + j] = has ? (int64_t)idx : -1;
         }
     }
@@ -292,7 +271,7 @@ __global__ __launch_bounds__(256) void rank_merge_kernel(const uint32_t *__restr
             const int64_t o = ((p / k) * B + b) * k + p % k;
             const uint32_t key = part_key[o];
             const int32_t idx = part_idx[o];
-            if (rank_before(key, idx, thk[0], thi[0])) {
+            if (pair_before(key, idx, thk[0], thi[0])) {
                 const uint32_t pos = atomicAdd(&cnt[0], 1u);
                 bk[pos] = key;
                 bi[pos] = idx;
@@ -303,7 +282,7 @@ __global__ __launch_bounds__(256) void rank_merge_kernel(const uint32_t *__restr
     }
     for (int j = tid; j < k; j += 256) {
         const bool has = j < (int)cnt[0];
-        out_val[b * k + j] = has ? rank_unkey(bk[j]) : -INFINITY;
+        out_val[b * k + j] = has ? float_unkey(bk[j]) : -INFINITY;
         out_idx[b * k + j] = has ? (int64_t)bi[j] : -1;
     }
 }
@@ -320,13 +299,9 @@ RankPlan rank_plan(int64_t B, int64_t n_items, int k)
     p.ub = k <= 128 ? 2 : 1;
     const int64_t ut = 32 * p.ub;
     p.user_tiles = (B + ut - 1) / ut;
-    // enough workgroups for two per CU: split the item range (in whole tiles of >= 16 x 128 items) when the users alone are too few
-    const int64_t want = (512 + p.user_tiles - 1) / p.user_tiles;
-    const int64_t max_splits = std::max<int64_t>(1, n_items / (16 * NGCF_RANK_IT));
-    int64_t s = std::max<int64_t>(1, std::min(want, max_splits));
-    const int64_t tiles = (n_items + NGCF_RANK_IT - 1) / NGCF_RANK_IT;
-    p.split_items = (tiles + s - 1) / s * NGCF_RANK_IT;
-    p.splits = (n_items + p.split_items - 1) / p.split_items;
+    const ItemSplit sp = rank_item_split(p.user_tiles, n_items);
+    p.splits = sp.splits;
+    p.split_items = sp.split_items;
     p.dyn_lds = (size_t)ut * (p.ub == 2 ? 256 : 512) * 8;
     return p;
 }
@@ -433,15 +408,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int64_t *__rest
                 int hits[NK] = {};
                 for (int j = 0; j < k; ++j) {
                     const int64_t it = top_idx[b * k + j];
-                    bool hit = false;
-                    if (it >= 0) {
-                        int64_t lo = first, hi = e1;                 // lower bound of `it` in the row
-                        while (lo < hi) {
-                            const int64_t mid = (lo + hi) >> 1;
-                            if ((int64_t)colidx[mid] - off < it) lo = mid + 1; else hi = mid;
-                        }
-                        hit = lo < e1 && (int64_t)colidx[lo] - off == it;
-                    }
+                    const bool hit = it >= 0 && row_has(colidx, first, e1, off, it);
                     const double g = 1.0 / log2((double)j + 2.0);
 #pragma unroll
                     for (int q = 0; q < NK; ++q) {
@@ -487,16 +454,6 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int64_t *__rest
     }
 }
 
-__global__ __launch_bounds__(64) void rank_metrics_finish_kernel(const double *__restrict__ part, int64_t n_blocks, int n_slots,
-                                                                 double *__restrict__ sums)
-{
-    const int s = threadIdx.x;
-    if (s >= n_slots) return;
-    double a = 0.0;
-    for (int64_t blk = 0; blk < n_blocks; ++blk) a += part[blk * n_slots + s];
-    sums[s] += a;
-}
-
 }  // namespace
 
 extern "C" int ngcf_rank_metrics(const int64_t *top_idx, int64_t B, int k, const int64_t *user_ids, int64_t n_user_rows,
@@ -519,17 +476,9 @@ extern "C" int ngcf_rank_metrics(const int64_t *top_idx, int64_t B, int k, const
     const int n_slots = 4 * n_ks + 1;
     const int64_t blocks = (B + 255) / 256;
     if (blocks >= ((int64_t)1 << 31)) return fail(NGCF_ERR_ARG, "rank_metrics: batch too large");
-    void *part = nullptr;
-    HIP_TRY(hipMallocAsync(&part, sizeof(double) * (size_t)(blocks * n_slots), stream));
-    rank_metrics_kernel<<<dim3((unsigned)blocks), 256, 0, stream>>>(top_idx, B, k, user_ids, n_user_rows, truth_rowptr, truth_colidx,
-                                                                   truth_col_offset, n_ks, ks[0], ks[1], ks[2], ks[3], ks[4],
-                                                                   ks[5], ks[6], ks[7], per_user, static_cast<double *>(part), status);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        rank_metrics_finish_kernel<<<1, 64, 0, stream>>>(static_cast<double *>(part), blocks, n_slots, sums);
-        e = hipGetLastError();
-    }
-    (void)hipFreeAsync(part, stream);
-    if (e != hipSuccess) return fail(NGCF_ERR_HIP, "rank_metrics: kernel launch failed: %s", hipGetErrorString(e));
-    return NGCF_OK;
+    return launch_with_partial_sums("rank_metrics", blocks, n_slots, sums, stream, [&](double *part) {
+        rank_metrics_kernel<<<dim3((unsigned)blocks), 256, 0, stream>>>(top_idx, B, k, user_ids, n_user_rows, truth_rowptr, truth_colidx,
+                                                                       truth_col_offset, n_ks, ks[0], ks[1], ks[2], ks[3], ks[4],
+                                                                       ks[5], ks[6], ks[7], per_user, part, status);
+    });
 }

@@ -1,0 +1,97 @@
+// What the full-catalogue ranking kernels share (rank.hip, rank_position.hip; the sums and their host tail list_quality.hip too),
+// defined once so that every kernel that orders, splits, searches or sums does it the same way.
+#ifndef NGCF_RANK_DEVICE_H
+#define NGCF_RANK_DEVICE_H
+
+#include "common.h"
+
+// ---------------------------------------------------------------------------------------------
+// Pair order.  A score's key is float_key (common.h); the output order of (key, item) pairs is key descending, then item ascending.
+// rank_positions counts what rank_topk lists, so both take the order from pair_before() and the padding from kPadKey / kPadIdx.
+//
+// Item split.  Both scoring kernels walk item tiles of kRankIT = 128 items, K in chunks of kRankTK = 32, and cut the item range by
+// rank_item_split() when the row tiles alone are too few workgroups.
+//
+// Sums.  Per-workgroup fp64 partials are added by ONE thread per slot, blocks in ascending order: bit-identical from run to run.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+typedef float rank_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kRankIT = 128, kRankTK = 32;      // items of a tile, columns of a K chunk
+
+constexpr uint32_t kPadKey = 0u;                // below every score key but the one NaN pattern 0xffffffff (which ties it)
+constexpr int32_t kPadIdx = 0x7fffffff;         // ... and then loses on the item index: padding sorts after every pair of a real item
+
+__device__ inline float float_unkey(uint32_t k)   // the inverse of float_key
+{
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__device__ inline bool pair_before(uint32_t ka, int32_t ia, uint32_t kb, int32_t ib)   // a precedes b: key descending, item ascending
+{
+    return ka > kb || (ka == kb && ia < ib);
+}
+
+// Is item id `c` in the ascending row [lo, end) of a CSR whose columns carry the offset `off`?  (A lower bound, then one compare.)
+__device__ inline bool row_has(const int32_t *__restrict__ colidx, int64_t lo, int64_t end, int64_t off, int64_t c)
+{
+    int64_t hi = end;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)colidx[mid] - off < c) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && (int64_t)colidx[lo] - off == c;
+}
+
+// The item split of a ranking launch: enough workgroups for two per CU - the item range is cut (in whole tiles, >= 16 x 128 items a
+// piece) when the user tiles alone are too few.
+struct ItemSplit {
+    int64_t splits, split_items;
+};
+
+inline ItemSplit rank_item_split(int64_t user_tiles, int64_t n_items)
+{
+    const int64_t want = (512 + user_tiles - 1) / user_tiles;
+    const int64_t max_splits = std::max<int64_t>(1, n_items / (16 * kRankIT));
+    const int64_t s = std::max<int64_t>(1, std::min(want, max_splits));
+    const int64_t tiles = (n_items + kRankIT - 1) / kRankIT;
+    ItemSplit p;
+    p.split_items = (tiles + s - 1) / s * kRankIT;
+    p.splits = (n_items + p.split_items - 1) / p.split_items;
+    return p;
+}
+
+// sums[s] += part[0][s] + part[1][s] + ..: one thread per slot, the workgroups' partials in ascending order
+__global__ __launch_bounds__(64) void sum_partials_kernel(const double *__restrict__ part, int64_t n_blocks, int n_slots,
+                                                          double *__restrict__ sums)
+{
+#pragma clang fp contract(off) reassociate(off)
+    const int s = threadIdx.x;
+    if (s >= n_slots) return;
+    double a = 0.0;
+    for (int64_t blk = 0; blk < n_blocks; ++blk) a += part[blk * n_slots + s];
+    sums[s] += a;
+}
+
+// n_blocks x n_slots (<= 64) partials allocated on the stream, launch(part) fills them, sum_partials_kernel adds them into `sums`,
+// the partials are freed on the stream; `who` names the entry point in the error text.
+template <typename Launch>
+int launch_with_partial_sums(const char *who, int64_t n_blocks, int n_slots, double *sums, hipStream_t stream, Launch launch)
+{
+    void *part = nullptr;
+    HIP_TRY(hipMallocAsync(&part, sizeof(double) * (size_t)(n_blocks * n_slots), stream));
+    launch(static_cast<double *>(part));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        sum_partials_kernel<<<1, 64, 0, stream>>>(static_cast<double *>(part), n_blocks, n_slots, sums);
+        e = hipGetLastError();
+    }
+    (void)hipFreeAsync(part, stream);
+    if (e != hipSuccess) return fail(NGCF_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    return NGCF_OK;
+}
+
+}  // namespace
+
+#endif  // NGCF_RANK_DEVICE_H

@@ -2,8 +2,10 @@
 // sorted list of eligible items, and MRR / MAP / AUC / NDCG / Recall@K for any K from those positions.  The scoring pass is
 // rank_topk_kernel's (rank.hip): fp32 MFMA tiles, no score is ever stored.  The streaming selection is replaced by a streaming
 // count: per user the held-out (key, item) pairs lie sorted in LDS, every computed score finds its gap among them by binary search
-// and bumps an integer counter, and a prefix sum over the gaps gives the positions.
-#include "common.h"
+// and bumps an integer counter, and a prefix sum over the gaps gives the positions.  The (key, item) order, the padding pair,
+// the item split, the row search and the fixed-order sums are rank_topk's by construction (rank_device.h); the score-tile walk of
+// pos_scan_kernel is restated from rank_topk_kernel and held to it bit for bit by the tests (DESIGN 4.3.15 has the reason).
+#include "rank_device.h"
 #include "dd_log2.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -26,53 +28,11 @@
 // LDS of the scan: 25 KiB of tiles + 3 x 64 x 65 words = 49 KiB of pairs and counters: two workgroups per CU (160 KiB).
 // ---------------------------------------------------------------------------------------------
 #define NGCF_POS_CAP NGCF_RANK_POS_CAP
-#define NGCF_POS_IT 128
-#define NGCF_POS_TK 32
 #define NGCF_POS_KS 8
 
 namespace {
 
-typedef float pos_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr uint32_t kPosPadKey = 0u;             // rank.hip's padding pair: sorts after every (key, item) of a real item
-constexpr int32_t kPosPadIdx = 0x7fffffff;
-
-// restated from rank.hip (its results are pinned bit for bit by the existing tests; the two files share no code)
-__device__ inline uint32_t pos_key(float x)
-{
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ inline bool pos_before(uint32_t ka, int32_t ia, uint32_t kb, int32_t ib)   // a precedes b: key descending, item ascending
-{
-    return ka > kb || (ka == kb && ia < ib);
-}
-
 __device__ inline int64_t pos_clamp(int64_t x, int64_t lo, int64_t hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-__device__ inline int64_t pos_shfl64(int64_t x, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src), hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)x >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-__device__ inline int pos_wave_min(int x)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const int y = __shfl_xor(x, m);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-__device__ inline int pos_wave_sum(int x)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
 
 struct PosWs {                 // the workspace, cut up on the host
     int32_t *n_vrows;          // [1] virtual rows of this call (<= vcap)
@@ -141,24 +101,14 @@ __global__ __launch_bounds__(256) void pos_truth_kernel(const float *__restrict_
     const int64_t r = ws.v_row[v], e0 = ws.v_e0[v];
     const int len = ws.v_len[v];
     bool valid = false;
-    uint32_t key = kPosPadKey;
-    int32_t idx = kPosPadIdx;
+    uint32_t key = kPadKey;
+    int32_t idx = kPadIdx;
     if (lane < len) {
         const int64_t c = (int64_t)t_colidx[e0 + lane] - t_off;
         if (c < 0 || c >= n_items) {
             atomicOr(status, 2);                                  // never used as an index
         } else {
-            bool excluded = false;
-            if (x_rowptr) {
-                int64_t lo = x_rowptr[r];
-                const int64_t end = x_rowptr[r + 1];
-                int64_t hi = end;
-                while (lo < hi) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if ((int64_t)x_colidx[mid] - x_off < c) lo = mid + 1; else hi = mid;
-                }
-                excluded = lo < end && (int64_t)x_colidx[lo] - x_off == c;
-            }
+            const bool excluded = x_rowptr && row_has(x_colidx, x_rowptr[r], x_rowptr[r + 1], x_off, c);
             if (!excluded) {
                 const float *ur = users + r * ldu, *ir = items + c * ldi;
                 float acc = 0.f;
@@ -174,7 +124,7 @@ __global__ __launch_bounds__(256) void pos_truth_kernel(const float *__restrict_
                 }
                 for (; k < D; ++k) acc = fmaf(ir[k], ur[k], acc);
                 valid = true;
-                key = pos_key(acc);
+                key = float_key(acc);
                 idx = (int32_t)c;
             }
         }
@@ -183,7 +133,7 @@ __global__ __launch_bounds__(256) void pos_truth_kernel(const float *__restrict_
     for (int j = 0; j < 64; ++j) {
         const uint32_t kj = (uint32_t)__shfl((int)key, j);
         const int32_t ij = __shfl(idx, j);
-        rank += pos_before(kj, ij, key, idx) || (kj == key && ij == idx && j < lane);
+        rank += pair_before(kj, ij, key, idx) || (kj == key && ij == idx && j < lane);
     }
     ws.s_key[v * CAP + rank] = key;
     ws.s_idx[v * CAP + rank] = idx;
@@ -198,7 +148,7 @@ __global__ __launch_bounds__(256) void pos_scan_kernel(const float *__restrict__
                                                        const int64_t *__restrict__ x_rowptr, const int32_t *__restrict__ x_colidx,
                                                        int64_t x_off, PosWs ws)
 {
-    constexpr int UB = 2, UT = 32 * UB, IT = NGCF_POS_IT, TK = NGCF_POS_TK, SLD = TK + 1, CAP = NGCF_POS_CAP, TLD = CAP + 1;
+    constexpr int UB = 2, UT = 32 * UB, IT = kRankIT, TK = kRankTK, SLD = TK + 1, CAP = NGCF_POS_CAP, TLD = CAP + 1;
     constexpr int NI = IT * TK / 256, NU = UT * TK / 256;
     __shared__ float sI[IT * SLD];
     __shared__ float sU[UT * SLD];
@@ -220,8 +170,8 @@ __global__ __launch_bounds__(256) void pos_scan_kernel(const float *__restrict__
     for (int p = tid; p < UT * CAP; p += 256) {
         const int u = p / CAP, j = p % CAP;
         const bool ok = v0 + u < n_v;
-        tk[u * TLD + j] = ok ? ws.s_key[(v0 + u) * CAP + j] : kPosPadKey;
-        ti[u * TLD + j] = ok ? ws.s_idx[(v0 + u) * CAP + j] : kPosPadIdx;
+        tk[u * TLD + j] = ok ? ws.s_key[(v0 + u) * CAP + j] : kPadKey;
+        ti[u * TLD + j] = ok ? ws.s_idx[(v0 + u) * CAP + j] : kPadIdx;
         gp[u * TLD + j] = 0u;
     }
     int64_t cur = 0, cur_end = 0;                                        // exclusion cursor of virtual row `tid` (threads tid < UT)
@@ -231,8 +181,8 @@ __global__ __launch_bounds__(256) void pos_scan_kernel(const float *__restrict__
         const int64_t r = n > 0 ? ws.v_row[v] : -1;                       // a row with no valid entry has nothing to count
         srow[tid] = r;
         nv[tid] = n;
-        thk[tid] = n > 0 ? ws.s_key[v * CAP + n - 1] : kPosPadKey;
-        thi[tid] = n > 0 ? ws.s_idx[v * CAP + n - 1] : kPosPadIdx;
+        thk[tid] = n > 0 ? ws.s_key[v * CAP + n - 1] : kPadKey;
+        thi[tid] = n > 0 ? ws.s_idx[v * CAP + n - 1] : kPadIdx;
         if (r >= 0 && x_rowptr) {
             cur = x_rowptr[r];
             cur_end = x_rowptr[r + 1];
@@ -289,7 +239,7 @@ __global__ __launch_bounds__(256) void pos_scan_kernel(const float *__restrict__
 #pragma unroll
             for (int w = 0; w < IT / 32; ++w) exm[tid * (IT / 32) + w] = m[w];
         }
-        pos_f32x16 acc[UB];
+        rank_f32x16 acc[UB];
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
 #pragma unroll
@@ -325,12 +275,12 @@ __global__ __launch_bounds__(256) void pos_scan_kernel(const float *__restrict__
                 const int il = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
                 const int64_t gi = i0 + il;
                 if (gi >= i_end || ((exm[u * (IT / 32) + (il >> 5)] >> (il & 31)) & 1u)) continue;
-                const uint32_t key = pos_key(acc[ub][e]);
-                if (pos_before(lk, li, key, (int32_t)gi)) continue;      // after the last valid entry: no position changes
+                const uint32_t key = float_key(acc[ub][e]);
+                if (pair_before(lk, li, key, (int32_t)gi)) continue;      // after the last valid entry: no position changes
                 int lo = 0, hi = n - 1;                                   // entries strictly before the item: at most n - 1 now
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    if (pos_before(K[mid], I[mid], key, (int32_t)gi)) lo = mid + 1; else hi = mid;
+                    if (pair_before(K[mid], I[mid], key, (int32_t)gi)) lo = mid + 1; else hi = mid;
                 }
                 atomicAdd(&gp[u * TLD + lo], 1u);
             }
@@ -417,14 +367,10 @@ extern "C" int ngcf_rank_positions_f32(const float *users, int64_t ldu, const in
     const int64_t need = ngcf_rank_positions_workspace_bytes(B, n_items, D, n_truth);
     if (!workspace || workspace_bytes < need)
         return fail(NGCF_ERR_WORKSPACE, "rank_positions: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-    // the item range is split (whole tiles, >= 16 x 128 items) when the batch alone cannot fill the chip (rank_plan's rule, rank.hip)
+    // the item range is split when the batch alone cannot fill the chip: rank_topk's rule
     const int64_t user_tiles = (B + UT - 1) / UT, v_tiles = (vcap + UT - 1) / UT;
-    const int64_t want = (512 + user_tiles - 1) / user_tiles;
-    const int64_t max_splits = std::max<int64_t>(1, n_items / (16 * NGCF_POS_IT));
-    const int64_t s = std::max<int64_t>(1, std::min(want, max_splits));
-    const int64_t tiles = (n_items + NGCF_POS_IT - 1) / NGCF_POS_IT;
-    const int64_t split_items = (tiles + s - 1) / s * NGCF_POS_IT;
-    const int64_t splits = (n_items + split_items - 1) / split_items;
+    const ItemSplit sp = rank_item_split(user_tiles, n_items);
+    const int64_t splits = sp.splits, split_items = sp.split_items;
     if (vcap >= ((int64_t)1 << 31) || splits > 65535)
         return fail(NGCF_ERR_ARG, "rank_positions: batch too large");
     PosWs ws;
@@ -486,14 +432,14 @@ __global__ __launch_bounds__(256) void pos_metrics_kernel(const int32_t *__restr
     for (int i = 0; i < 64; ++i) {
         const int64_t b = b_base + i;
         if (b >= B) break;                                      // the whole wave
-        const int64_t e0 = pos_shfl64(my_e0, i), e1 = pos_shfl64(my_e1, i), xl = pos_shfl64(my_xl, i);
+        const int64_t e0 = shfl_i64(my_e0, i), e1 = shfl_i64(my_e1, i), xl = shfl_i64(my_xl, i);
         double v[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) v[s] = 0.0;
         if (e1 > e0) {
             int distinct = 0;                                   // |T|: the row is ascending
             for (int64_t e = e0 + lane; e < e1; e += 64) distinct += e == e0 || t_colidx[e] != t_colidx[e - 1];
-            const int nt = pos_wave_sum(distinct);
+            const int nt = wave_sum(distinct);
             const int32_t mine = e0 + lane < e1 ? position[e0 + lane] : -1;
             const double neg = (double)(n_items - xl - nt);     // E - T
             double rr = 0.0, ap = 0.0, dcg = 0.0, below = 0.0, dcg_k[NK] = {};
@@ -506,7 +452,7 @@ __global__ __launch_bounds__(256) void pos_metrics_kernel(const int32_t *__restr
                     const int32_t p = position[e];
                     if (p > prev && p < m) m = p;
                 }
-                m = pos_wave_min(m);
+                m = wave_min(m);
                 if (m == 0x7fffffff) break;
                 const double g = 1.0 / ddm::log2_cr((double)m + 2.0);
                 if (j == 0) rr = 1.0 / ((double)m + 1.0);
@@ -565,16 +511,6 @@ __global__ __launch_bounds__(256) void pos_metrics_kernel(const int32_t *__restr
     }
 }
 
-__global__ __launch_bounds__(64) void pos_metrics_finish_kernel(const double *__restrict__ part, int64_t n_blocks, int n_slots,
-                                                                double *__restrict__ sums)
-{
-    const int s = threadIdx.x;
-    if (s >= n_slots) return;
-    double a = 0.0;
-    for (int64_t blk = 0; blk < n_blocks; ++blk) a += part[blk * n_slots + s];
-    sums[s] += a;
-}
-
 }  // namespace
 
 extern "C" int ngcf_rank_position_metrics(const int32_t *position, int64_t B, const int64_t *user_ids, int64_t n_user_rows,
@@ -600,17 +536,9 @@ extern "C" int ngcf_rank_position_metrics(const int32_t *position, int64_t B, co
     const int n_slots = 4 + 4 * n_ks + 2;
     const int64_t blocks = (B + 255) / 256;
     if (blocks >= ((int64_t)1 << 31)) return fail(NGCF_ERR_ARG, "rank_position_metrics: batch too large");
-    void *part = nullptr;
-    HIP_TRY(hipMallocAsync(&part, sizeof(double) * (size_t)(blocks * n_slots), stream));
-    pos_metrics_kernel<<<dim3((unsigned)blocks), 256, 0, stream>>>(position, B, user_ids, n_user_rows, truth_rowptr, truth_colidx, n_truth,
-                                                                  excl_rowptr, n_items, n_ks, ks[0], ks[1], ks[2], ks[3], ks[4], ks[5],
-                                                                  ks[6], ks[7], per_user, static_cast<double *>(part), status);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        pos_metrics_finish_kernel<<<1, 64, 0, stream>>>(static_cast<double *>(part), blocks, n_slots, sums);
-        e = hipGetLastError();
-    }
-    (void)hipFreeAsync(part, stream);
-    if (e != hipSuccess) return fail(NGCF_ERR_HIP, "rank_position_metrics: kernel launch failed: %s", hipGetErrorString(e));
-    return NGCF_OK;
+    return launch_with_partial_sums("rank_position_metrics", blocks, n_slots, sums, stream, [&](double *part) {
+        pos_metrics_kernel<<<dim3((unsigned)blocks), 256, 0, stream>>>(position, B, user_ids, n_user_rows, truth_rowptr, truth_colidx,
+                                                                      n_truth, excl_rowptr, n_items, n_ks, ks[0], ks[1], ks[2], ks[3],
+                                                                      ks[4], ks[5], ks[6], ks[7], per_user, part, status);
+    });
 }

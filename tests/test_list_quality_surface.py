@@ -74,7 +74,7 @@ def test_an_entry_is_compared_with_n_items_before_it_is_an_index():
     expo = src[src.index("void list_exposure_kernel"):src.index('extern "C" int ngcf_list_exposure')]
     assert expo.index("if (id >= n_items)") < expo.index("expo_tab[id]") < expo.index("counts[id]")
     assert expo.index("if (id < 0) continue;") < expo.index("if (id >= n_items)")
-    div = src[src.index("void list_diversity_kernel"):src.index("void list_diversity_finish_kernel")]
+    div = src[src.index("void list_diversity_kernel"):src.index('extern "C" int ngcf_list_diversity_f32')]
     assert div.index("if (v >= n_items)") < div.index("id = (int32_t)v") < div.index("sid[lane] = id") < div.index("(int64_t)it * ldi")
     assert div.count("(int64_t)it * ldi") == 2 and div.count("if (it >= 0 && kk < D)") + div.count("(it >= 0 && kk < D) ?") == 2
 

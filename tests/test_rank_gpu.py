@@ -61,6 +61,42 @@ def test_rank_bit_identical_to_recommend_topk(B, n_items, D, k):
     assert not bool(torch.gather(m, 1, i.clamp(min=0))[valid].any())
 
 
+def _boundary_rows(B, n_items, keep, seed):
+    """Exclusion rows that hold items 127, 128, 2175 and 2176 - the two sides of a tile boundary and of the item-split boundary of
+    (33, 4224): 33 tiles, 2 splits of 2176 items - and everything else but `keep` random items per user."""
+    rng = np.random.default_rng(seed)
+    edge = np.array([127, 128, 2175, 2176])
+    rows = []
+    for _ in range(B):
+        stay = np.setdiff1d(rng.permutation(n_items)[:keep], edge)
+        rows.append(np.setdiff1d(np.arange(n_items), stay))
+    return rows
+
+
+@pytest.mark.parametrize("k", [128, 129])
+def test_rank_every_branch_of_the_tile_walk_at_once(k):
+    """B = 33, n_items = 4224, D = 33: one 64-user tile at k = 128, two 32-user tiles at k = 129, the last one partly filled either
+    way; two item splits of 2176 items; a second K chunk of one column; exclusion rows across the tile and the split boundary.  4224 is
+    33 whole tiles, so n_items = 4223 follows: the same split, and a last tile that the item range cuts short."""
+    eng = _eng()
+    for n_items in (4224, 4223):
+        u, items = _tables(33, n_items, 33, 41)
+        rv, ri, scores = eng.recommend_topk(u, items, k, return_scores=True)
+        v, i = eng.rank_topk(u, items, k)
+        assert torch.equal(v, rv) and torch.equal(i, ri)
+        for keep in (n_items - 40, 100):                                  # few exclusions; fewer than k eligible items
+            rows = _boundary_rows(33, n_items, keep, 42 + keep)
+            rowptr = torch.tensor([0] + np.cumsum([len(r) for r in rows]).tolist(), dtype=torch.int64, device=DEV)
+            sets = eng.ItemSets(rowptr, torch.tensor(np.concatenate(rows), dtype=torch.int32, device=DEV), 0, n_items)
+            v, i = eng.rank_topk(u, items, k, exclude=sets)
+            m = _mask(sets, 33, n_items).to(DEV)
+            wv, wi = eng.topk_rows(scores.masked_fill(m, float("-inf")), k)
+            valid = i >= 0
+            assert torch.equal(valid.sum(1).cpu(), torch.clamp((~m).sum(1), max=k).cpu())
+            assert torch.equal(v[valid], wv[valid]) and torch.equal(i[valid], wi[valid])
+            assert bool((v[~valid] == float("-inf")).all()) and not bool(torch.gather(m, 1, i.clamp(min=0))[valid].any())
+
+
 def test_rank_exact_selection_with_ties():
     eng = _eng()
     g = torch.Generator().manual_seed(5)

@@ -114,6 +114,32 @@ def test_positions_at_the_tile_boundaries(B, n_items, D):
     _check_against_oracle(u, items, excl, truth)
 
 
+@pytest.mark.parametrize("n_items", [4224, 4223])
+def test_positions_every_branch_of_the_tile_walk_at_once(n_items):
+    """B = 33, D = 33, 33 item tiles in two splits of 2176 (the last tile cut short at 4223): a partly filled row tile, a second K
+    chunk of one column, and exclusion rows that hold 127, 128, 2175, 2176 - both sides of a tile boundary and of the split boundary -
+    while their neighbours 126, 129, 2174, 2177 are held out.  First against the oracle and rank_topk's top 256, then, with fewer
+    than 256 eligible items per user, against the positions read off rank_topk's full order."""
+    eng = _eng()
+    B, D = 33, 33
+    u, items = _tables(B, n_items, D, 41)
+    rng = np.random.default_rng(43)
+    edge, near = np.array([127, 128, 2175, 2176]), np.array([126, 129, 2174, 2177])
+    rest = np.setdiff1d(np.arange(n_items), np.concatenate([edge, near]))
+    pools = [rng.permutation(rest) for _ in range(B)]
+    _check_against_oracle(u, items, [np.sort(np.concatenate([edge, p[:20]])) for p in pools],
+                          [np.sort(np.concatenate([near, p[20:40]])) for p in pools])
+    truth = [np.sort(np.concatenate([near, p[:30]])) for p in pools]
+    excl = [np.setdiff1d(np.arange(n_items), np.concatenate([near, p[:240]])) for p in pools]
+    excl_s, truth_s = _sets_of(excl, n_items), _sets_of(truth, n_items)
+    top = eng.rank_topk(u, items, 256, exclude=excl_s)[1]
+    assert bool(((top >= 0).sum(1) == 244).all())                              # every eligible item, in order
+    found = [top[b][:, None] == torch.tensor(truth[b], device=DEV)[None, :] for b in range(B)]
+    assert all(bool(f.any(0).all()) for f in found)
+    want = torch.cat([f.int().argmax(0) for f in found]).int()
+    assert torch.equal(eng.ranks.rank_positions(u, items, truth_s, exclude=excl_s), want)
+
+
 def test_positions_do_not_depend_on_batch_chunks_strides_or_runs():
     eng = _eng()
     B, n_items, D = 300, 20000, 64

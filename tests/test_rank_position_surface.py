@@ -41,6 +41,27 @@ def test_header_declares_the_three_functions_and_keeps_version_11():
     assert any(p.endswith("rank_position.hip") for p in _build.SOURCES)
 
 
+def test_the_ranking_kernels_share_one_definition_of_order_split_and_sums():
+    """By reading the sources: the pair order, the item split, the row search and the fixed-order sums stand once, in rank_device.h
+    (the key map in common.h), and the header is part of the source hash."""
+    from seoul_tourism_recommendation_ngcf_amd import _build
+    csrc = os.path.join(ROOT, "seoul_tourism_recommendation_ngcf_amd", "csrc")
+    assert any(p.endswith("rank_device.h") for p in _build.HEADERS)
+    text = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".h"))}
+    sites = lambda words: sorted(f for f, t in text.items() for _ in range(t.count(words)))  # noqa: E731
+    assert sites("n_items / (16 * ") == ["rank_device.h"]
+    assert sites("(u & 0x80000000u) ? ~u") == ["common.h"]
+    assert sites("void sum_partials_kernel(") == ["rank_device.h"]
+    for f in ("rank.hip", "rank_position.hip"):
+        assert '#include "rank_device.h"' in text[f] and "rank_item_split(" in text[f]
+        assert "pair_before(" in text[f] and "row_has(" in text[f] and "launch_with_partial_sums(" in text[f]
+    # ops.hip's recommend_topk_kernel, which the MFMA kernels are pinned against, keeps its own statement of the order on purpose
+    assert sites("ka > kb || (ka == kb && ") == ["ops.hip", "rank_device.h"]
+    for gone in ("rank_metrics_finish_kernel", "pos_metrics_finish_kernel", "list_diversity_finish_kernel", "rank_key(", "pos_key(",
+                 "rank_before(", "pos_before(", "kPosPadKey"):
+        assert not sites(gone), gone
+
+
 def test_argument_errors_come_before_any_launch():
     from seoul_tourism_recommendation_ngcf_amd.engine import ranks
     truth = _sets(2, 5)
