@@ -721,6 +721,45 @@ int ngcf_exposure_summary(const int64_t *sorted_counts, const int64_t *counts, c
 int ngcf_list_diversity_f32(const int64_t *top_idx, int64_t ld, int64_t B, int k, const float *items, int64_t ldi, int64_t n_items,
                             int D, const int32_t *ks_host, int n_ks, double *per_user, double *sums, int32_t *status, void *stream);
 
+/* ---- diversified top lists (csrc/list_rerank.hip) ----
+ * Greedy Maximal Marginal Relevance: from a pool of n candidates per request pick `top` of them one by one, each pick trading its
+ * relevance against its similarity to what is already picked.  One launch; nothing of size [B, n, D] or [B, n, n] goes to memory.
+ *
+ * Pool: row b of pool_idx (int64, row pitch ld >= n), columns [0, n), 1 <= n <= NGCF_LIST_MMR_POOL_MAX, 1 <= top <= n -
+ * ngcf_rank_topk_f32's out_idx, ngcf_blend_points' out_items.  A negative entry is an empty slot wherever it stands.  An entry
+ * >= n_items sets bit 0 (value 1) of *status; it is compared before anything else is done with it and is never used as an index
+ * (the slot then counts as empty).  n_items < 2^31.
+ * Relevance: rel [B, n], row pitch ldr >= n, fp32 (rel_f64 = 0: ngcf_rank_topk_f32's values) or fp64 (rel_f64 = 1:
+ * ngcf_blend_points' ratings), widened to double on load: v_a.  The relevance of an empty slot is not used.
+ * items [n_items, D] fp32, row pitch ldi >= D (a row range of all_E, unaligned rows: 16-byte loads where the pointer and the pitch
+ * allow them, dword loads elsewhere, the same bits either way); any D >= 1.  Per row, with e_a the item row of slot a:
+ *   G_ab   = sum_k e_a[k] * e_b[k] in fp32 as ONE ascending-k fmaf chain from 0 (the bits of ngcf_list_diversity_f32 and
+ *            ngcf_rank_topk_f32; fp32 MFMA): G_ab = G_ba
+ *   cos_ab = (double)G_ab / sqrt((double)G_aa * (double)G_bb), every fp64 operation rounded once, no FMA; 0.0 where the product under
+ *            the root is 0; a NaN propagates
+ *   r_a    normalize = 0: v_a.  normalize = 1: with vmin and vmax the smallest and the largest FINITE v_a of the non-empty slots (a
+ *            zero of either sign enters both as +0.0), r_a = (v_a - vmin) / (vmax - vmin) - a subtraction, a subtraction, a
+ *            division, each rounded once - for a finite v_a; r_a = 0.0 for every finite v_a when vmax == vmin or when no value is
+ *            finite; a v_a that is not finite (an infinity, a NaN) stays as it is
+ *   step 0:      key_a = lam * r_a
+ *   step t >= 1: key_a = lam * r_a - (1.0 - lam) * m_a; 1.0 - lam is formed once; two products and one subtraction, each rounded
+ *            once, no FMA.  m_a = cos_as of the first pick s; with every further pick s it becomes a NaN if it or cos_as is a NaN,
+ *            cos_as if cos_as > m_a, and stays otherwise: the largest cosine to the slots picked so far, a NaN once any of them is
+ *   pick:    the non-empty slot not picked so far with the greatest key.  A NaN key ranks below every other key, -inf included; +0.0
+ *            and -0.0 are equal; among equal keys, and among NaN keys, the lowest slot wins
+ * The loop runs min(top, V) steps, V = the number of non-empty slots.  Step t writes out_items[b, t] = the picked item id,
+ * out_slots[b, t] = its pool column (int32, may be NULL) and out_keys[b, t] = the key it was picked with (float64, may be NULL; a
+ * NaN key is written as the quiet NaN 0x7ff8000000000000); the columns t >= V hold (-1, -1, -inf).  The outputs are [B, top],
+ * contiguous.  A row's result depends on that row alone - not on B, the row order or the launch shape - and there are no atomics
+ * but the status bit: identical from run to run.
+ * Argument errors, before any launch (NGCF_ERR_ARG, message "list_mmr: ..."): a null pointer (out_slots and out_keys may be NULL),
+ * n outside [1, NGCF_LIST_MMR_POOL_MAX], top outside [1, n], lam a NaN or outside [0, 1], D < 1, n_items outside [1, 2^31), a
+ * negative B, a row pitch below its row.  B == 0 launches nothing. */
+#define NGCF_LIST_MMR_POOL_MAX 64
+int ngcf_list_mmr_f32(const int64_t *pool_idx, int64_t ld, const void *rel, int rel_f64, int64_t ldr, int64_t B, int n, int top,
+                      const float *items, int64_t ldi, int64_t n_items, int D, double lam, int normalize, int64_t *out_items,
+                      int32_t *out_slots, double *out_keys, int32_t *status, void *stream);
+
 /* ---- year-slice Laplacians straight into CSR (csrc/laplacian.hip; the reference's Matrix.create_matrix, matrix.py:12-83) ----
  * What matrix.laplacian_slices computes, with the state of R kept between years as a user-sorted CSR (rowptr int64[n_user + 1],
  * item int32, rating fp32) instead of a sorted key list.  Years are taken in order of first appearance; within a year the last

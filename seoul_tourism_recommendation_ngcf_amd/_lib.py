@@ -104,6 +104,8 @@ PROTOTYPES = {
     "ngcf_list_exposure": (C.c_int, [_vp, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "ngcf_exposure_summary": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "ngcf_list_diversity_f32": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _i64, _i64, C.c_int, C.POINTER(_i32), C.c_int, _vp, _vp, _vp, _vp]),
+    "ngcf_list_mmr_f32": (C.c_int, [_vp, _i64, _vp, C.c_int, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _i64, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp,
+                                   _vp, _vp]),
     "ngcf_eval_candidates_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _i64, _i64, C.c_int, _vp, C.POINTER(_i32),
                                            C.c_int, C.c_int, _f32, _f32, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "ngcf_blend_workspace_bytes": (_i64, [_i64, _i64, C.c_int, C.c_int]),

@@ -5,7 +5,7 @@ streams only; no tensor arithmetic of the hot path happens in torch.  Importing 
 the device: `_lib.load()` runs inside the calls.  Callers reach every name below, the private ones included, as `engine.<name>`;
 the trip-context family (csrc/context.hip), the delimited-text family (csrc/text.hip), the optimizer step (csrc/adam.hip), the exact
 held-out positions (csrc/rank_position.hip), the hard negatives (csrc/sample_hard.hip), the loss against m negatives per positive
-(csrc/bpr_multi.hip) and the beyond-accuracy list figures (csrc/list_quality.hip) keep their modules' names: `engine.context.<name>`,
+(csrc/bpr_multi.hip) and the beyond-accuracy list figures with the diversifying re-rank (csrc/list_quality.hip, csrc/list_rerank.hip) keep their modules' names: `engine.context.<name>`,
 `engine.text.<name>`, `engine.optim.<name>`, `engine.ranks.<name>`, `engine.negatives.<name>`, `engine.losses.<name>`,
 `engine.lists.<name>`.
 """

@@ -1,7 +1,9 @@
 """Beyond-accuracy figures of top lists (the header's section "beyond-accuracy figures of top lists", csrc/list_quality.hip): how
 often every item is shown, what that exposure histogram looks like (coverage, Gini, entropy, novelty) and how different the items
 within one list are (intra-list diversity).  A list is a row of an int64 `top_idx` - `rank_topk`'s indices, `blend_points`'
-`out_items`, or a column slice of either -, negative entries are empty slots.  Reached as `engine.lists.<name>`."""
+`out_items`, or a column slice of either -, negative entries are empty slots.  And what changes those figures: `mmr_rerank`, the
+greedy diversifying re-rank of a pool of candidates (the header's section "diversified top lists", csrc/list_rerank.hip).  Reached
+as `engine.lists.<name>`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,11 +14,12 @@ from typing import Optional, Sequence
 import torch
 
 from .. import _lib
-from ._plumbing import _f32c, _on, _ptr, _require_device, _require_dtype, _require_same_device, _row_major_ld, _status_word, _stream, _sums_slots
+from ._plumbing import _f32c, _on, _ptr, _require_device, _require_dtype, _require_same_device, _row_major_ld, _status_word, _stream, _sums_slots, _unit_inner
 
 EXPOSURE_LDS_ITEMS = 16384     # NGCF_EXPOSURE_LDS_ITEMS: catalogues up to this size are counted in LDS tables
 DIVERSITY_K_MAX = 64           # NGCF_LIST_DIV_K_MAX: the largest cut-off of list_diversity
 DIVERSITY_KS_MAX = 8
+MMR_POOL_MAX = 64              # NGCF_LIST_MMR_POOL_MAX: the largest pool of mmr_rerank
 SUMMARY_OVERFLOW, SUMMARY_NEGATIVE = 1, 2     # the status bits of exposure_summary_launch's fourth word
 _FIGURES = ("coverage", "gini", "entropy", "novelty")
 
@@ -201,3 +204,64 @@ def diversity_from_sums(sums, ks: Sequence[int]) -> dict:
         out[f"ild@{K}"] = s[q] / n if n else math.nan
         out[f"lists@{K}"] = n
     return out
+
+
+def mmr_rerank(pool_idx: torch.Tensor, relevance: torch.Tensor, item_emb: torch.Tensor, top: int, lam: float = 0.7,
+               normalize: bool = True, return_slots: bool = False, return_keys: bool = False,
+               status: Optional[torch.Tensor] = None):
+    """Diversified top lists (ngcf_list_mmr_f32): greedy Maximal Marginal Relevance over a pool of candidates per request, one
+    launch.  `pool_idx` int64 [B, n], n <= MMR_POOL_MAX, negative entries are empty slots - `rank_topk`'s indices, `blend_points`'
+    `out_items`; `relevance` [B, n] float32 (`rank_topk`'s values) or float64 (`blended_ranking`'s ratings), the value of every
+    pool entry; `item_emb` [n_items, D] float32.  Strided views are taken as they are where the inner stride is 1.  Pick 0 is the
+    slot of the greatest lam * r; pick t >= 1 that of the greatest lam * r_a - (1 - lam) * max over the picked s of cos(e_a, e_s),
+    ties to the lowest slot, a NaN key last; with `normalize` r is the relevance scaled to [0, 1] by the finite extremes of the
+    row, otherwise the relevance as given (the header states every operation and its order).  lam = 1 keeps the pool's order by
+    relevance, lam = 0 is farthest-first after the first pick.
+    Returns the picked item ids int64 [B, top]; with `return_slots` / `return_keys` a tuple with their pool columns (int32) and the
+    keys they were picked with (float64) appended in that order.  Columns past a row's non-empty slots hold (-1, -1, -inf).  An
+    entry >= n_items raises IndexError after the call's one read-back - the other rows are complete by then -; with a caller's int32
+    `status` word it is only flagged there (bit 0) and the call does not sync."""
+    lib = _lib.load()
+    fn = "mmr_rerank"
+    # shapes, types and limits first (they hold on any device), then where the tensors live
+    if pool_idx.dtype != torch.int64:
+        raise TypeError(f"{fn}: pool_idx must be int64, got {pool_idx.dtype}")
+    if relevance.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{fn}: relevance must be float32 or float64, got {relevance.dtype}")
+    if item_emb.dtype != torch.float32:
+        raise TypeError(f"{fn}: item_emb must be float32, got {item_emb.dtype}")
+    if pool_idx.dim() != 2 or int(pool_idx.shape[1]) < 1:
+        raise ValueError(f"{fn}: pool_idx must be [B, n], got {tuple(pool_idx.shape)}")
+    n = int(pool_idx.shape[1])
+    if tuple(relevance.shape) != tuple(pool_idx.shape):
+        raise ValueError(f"{fn}: relevance must be [B, n] = {tuple(pool_idx.shape)} as pool_idx, got {tuple(relevance.shape)}")
+    if item_emb.dim() != 2 or int(item_emb.shape[0]) < 1 or int(item_emb.shape[1]) < 1 or int(item_emb.shape[0]) >= 2 ** 31:
+        raise ValueError(f"{fn}: item_emb must be [n_items, D], got {tuple(item_emb.shape)}")
+    if n > MMR_POOL_MAX:
+        raise ValueError(f"{fn}: a pool of n={n} entries, at most {MMR_POOL_MAX}")
+    top = int(top)
+    if top < 1 or top > n:
+        raise ValueError(f"{fn}: top={top} outside [1, n={n}]")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"{fn}: lam={lam} outside [0, 1]")
+    _require_device(item_emb, "item_emb")
+    dev = item_emb.device
+    _require_same_device(fn, (("pool_idx", pool_idx), ("relevance", relevance)), "item_emb", dev)
+    status, check_status = _status_word(fn, status, dev)
+    pool_idx, relevance, item_emb = _unit_inner(pool_idx), _unit_inner(relevance), _unit_inner(item_emb)
+    B, n_items, D = int(pool_idx.shape[0]), int(item_emb.shape[0]), int(item_emb.shape[1])
+    out_items = torch.empty((B, top), dtype=torch.int64, device=dev)
+    out_slots = torch.empty((B, top), dtype=torch.int32, device=dev) if return_slots else None
+    out_keys = torch.empty((B, top), dtype=torch.float64, device=dev) if return_keys else None
+    if B > 0:
+        with _on(dev):
+            _lib.check(lib.ngcf_list_mmr_f32(_ptr(pool_idx), _row_major_ld(pool_idx, "pool_idx"), _ptr(relevance),
+                                             int(relevance.dtype == torch.float64), _row_major_ld(relevance, "relevance"), B, n, top,
+                                             _ptr(item_emb), _row_major_ld(item_emb, "item_emb"), n_items, D, lam, int(bool(normalize)),
+                                             _ptr(out_items), _ptr(out_slots), _ptr(out_keys), _ptr(status), _stream()))
+    if check_status:
+        _raise_bad_id(fn, int(status.item()), n_items)
+    if not (return_slots or return_keys):
+        return out_items
+    return (out_items,) + ((out_slots,) if return_slots else ()) + ((out_keys,) if return_keys else ())

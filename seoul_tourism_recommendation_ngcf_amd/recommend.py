@@ -199,6 +199,67 @@ def blended_ranking(model, user_ids: torch.Tensor, *, features=None, year=None, 
         model.train(was_training)
 
 
+def diversified_ranking(model, user_ids: torch.Tensor, *, train=None, lam: float = 0.7, pool: int = 64, top: int = 10,
+                        year_idx: int = 0, normalize: bool = True, user_chunk: int = 65536):
+    """Top lists that are not ten near-duplicates in embedding space: per user the best `pool` items by predicted preference
+    (`engine.rank_topk` on the propagated tables, the user's `train` items left out) re-ranked greedily by Maximal Marginal
+    Relevance (`engine.lists.mmr_rerank`): pick 0 is the best item, every further pick the one with the greatest
+    lam * relevance - (1 - lam) * (largest cosine to the items picked so far).  lam = 1 is `rank_topk`'s own order, smaller values
+    trade accuracy for `evaluate.list_quality`'s `ild`, which takes the result as `lists=`.
+
+      user_ids    int64 [B], one list per entry.
+      train       engine.ItemSets or (users, items) pairs left out of the pools, or None.
+      pool        candidates per user, at most engine.lists.MMR_POOL_MAX = 64; clipped to the catalogue size.
+      top         picks per user, at most the (clipped) pool.
+      normalize   scale a pool's scores to [0, 1] before they meet the cosines (scores of an inner-product model have no fixed range).
+      user_chunk  users per ranking and re-ranking launch; the result does not depend on it.
+
+    Returns (items int64 [B, top], keys float64 [B, top]) on the device: the picked ids and the key each was picked with; columns
+    past a user's eligible items hold (-1, -inf).  One propagate in eval mode under no_grad, the caller's mode restored; one status
+    word for the whole call, read back once at the end: a user id outside the table raises IndexError then.
+
+    `blended_ranking`'s lists diversify the same way: `engine.lists.mmr_rerank(out_items, out_ratings, model.all_items_emb, top)`
+    takes its float64 ratings as they are."""
+    fn = "diversified_ranking"
+    pool, top, user_chunk, lam = int(pool), int(top), int(user_chunk), float(lam)
+    if pool < 1 or pool > engine.lists.MMR_POOL_MAX:
+        raise ValueError(f"{fn}: pool={pool} outside [1, {engine.lists.MMR_POOL_MAX}]")
+    if top < 1 or top > pool:
+        raise ValueError(f"{fn}: top={top} outside [1, pool={pool}]")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"{fn}: lam={lam} outside [0, 1]")
+    if user_chunk < 1:
+        raise ValueError(f"{fn}: user_chunk={user_chunk}")
+    if not isinstance(user_ids, torch.Tensor) or user_ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{fn}: user_ids must be an int32 or int64 tensor")
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            model.propagate(year_idx)
+            U, I = model.all_users_emb, model.all_items_emb
+            dev = U.device
+            n_user, n_item = int(U.shape[0]), int(I.shape[0])
+            n = min(pool, n_item)
+            if top > n:
+                raise ValueError(f"{fn}: top={top} above the pool of {n} entries (the catalogue has {n_item} items)")
+            excl = None if train is None else _as_sets(train, n_user, n_item, dev)
+            user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64)
+            B = int(user_ids.numel())
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            items = torch.empty((B, top), dtype=torch.int64, device=dev)
+            keys = torch.empty((B, top), dtype=torch.float64, device=dev)
+            for c0 in range(0, B, user_chunk):
+                vals, idx = engine.rank_topk(U, I, n, user_ids=user_ids[c0:c0 + user_chunk], exclude=excl, status=status)
+                items[c0:c0 + user_chunk], keys[c0:c0 + user_chunk] = engine.lists.mmr_rerank(
+                    idx, vals, I, top, lam=lam, normalize=normalize, return_keys=True, status=status)
+            if int(status.item()) != 0:                                # the one read-back
+                raise IndexError(f"{fn}: a user id lies outside [0, {n_user})")
+            return items, keys
+    finally:
+        model.train(was_training)
+
+
 # ---- the trip context from raw rows: what demo.py builds between its pickles and the blend -------------------------------------------
 INF = float("inf")
 MONTH_DAYS = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)           # demo.py:114, month_info: no leap year
