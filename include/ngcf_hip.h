@@ -342,6 +342,65 @@ int ngcf_bpr_multi_backward_f32(const float *u, int64_t Bu, const float *p, int6
                                 int reduction, float weight_decay, float batch_size, const float *grad_out, float *du,
                                 float *dp, float *dn, void *stream);
 
+/* ---- Full-catalogue softmax (csrc/softmax_full.hip) ------------------------------------------- */
+/*
+ * The softmax loss over the whole catalogue, the limit of the sampled losses above, without a [B, n_items] matrix in memory:
+ *   s_bj = <u_b, i_j> * inv_tau          L_b = lse_j s_bj - s_b,pos_b
+ *   loss = (sum_b L_b + wd * (sum_b |u_b|^2 + sum_b |i_pos_b|^2)) / batch_size
+ * users: [B, D] fp32 rows, leading dimension ldu; items: [n_items, D] fp32 rows, leading dimension ldi (a row block of all_E);
+ * pos: [B] int64 item ids.  Scores are plain (no abs: rank_topk ranks by the plain score; the abs is the reference's BPR's).
+ * An id outside [0, n_items) is never used as an index: the row has no positive term (s_b,pos = 0, no |i_pos|^2, no -1 in the
+ * gradient) and bit 0 of *status (device int32) is set with an integer atomic.  1 <= B, n_items < 2^31, D >= 1, inv_tau > 0 and
+ * finite, batch_size > 0; anything else is NGCF_ERR_ARG before any launch.
+ *
+ * The recipe, operation by operation where it decides bits (fp32 unless fp64 is said; no contraction but the fmaf named):
+ *   score    the fp32 score of ngcf_rank_topk_f32: ONE chain acc = fmaf(u_bk, i_jk, acc), k ascending from acc = 0 (the MFMA step
+ *            order of rank.hip, K zero-padded to a multiple of 32); s_bj = acc * inv_tau, rounded once.  With inv_tau = 1, spos[b]
+ *            has the bits rank_topk returns for (b, pos_b).
+ *   forward  a workgroup owns 64 users and one item piece (rank_item_split of the 64-user tiles: whole tiles of 128 items) and
+ *            walks the piece in tiles of 128 items.  A lane holds one user and 16 items of a tile: wave w (0..3), lane half h,
+ *            register e -> item 32 w + (e & 3) + 8 (e >> 2) + 4 h of the tile.  Per lane a running pair (m, l), from (-inf, 0):
+ *              tm = max over the lane's valid scores of the tile (fmaxf, e ascending);  M = fmaxf(m, tm);  Ms = M, or 0 if M = -inf
+ *              l = l * expf(m - Ms);  then for e ascending: l = l + expf(s_e - Ms);  m = M
+ *            The positive's score is the s_e of the lane that holds item pos_b when its tile passes: spos[b] <= m in the bits.
+ *   merge    (m, l) <- (ma, la) + (mb, lb):  M = fmaxf(ma, mb);  Ms = M or 0 as above;  l = la * expf(ma - Ms) + lb * expf(mb - Ms).
+ *            The eight holders of a user merge as a left fold in the order h' = 2 w + h = 0..7; the item pieces as a left fold in
+ *            ascending piece order; then lse_b = m + logf(l).
+ *   sums     L_b = (double)lse_b - (double)spos_b;  |u_b|^2 and |i_pos_b|^2 in fp64: lane t of the row's wave adds the exact fp64
+ *            squares of columns t, t + 64, .. ascending, the lanes combine by the xor butterfly 32, 16, .., 1, the two norms add.
+ *            Four rows a workgroup: (r0 + r1) + (r2 + r3) in fp64, for the L's and for the norms.  Last stage, one workgroup of
+ *            256: thread t adds the workgroups t, t + 256, .. ascending, thread 0 adds the 256 results ascending;
+ *            loss = (float)((sumL + (double)wd * sumsq) / (double)batch_size).
+ *   A maximum of -inf, an infinite score or a NaN faults nothing: a NaN input gives a NaN loss (fmaxf drops the NaN, expf keeps it).
+ *
+ * Gradients, times *grad_out (one device float):
+ *   c    = grad_out / batch_size * inv_tau            (in that order)
+ *   g_bj = c * (expf(s_bj - lse_b) - [j == pos_b])     s_bj recomputed by the recipe above
+ *   dU_b = sum_j g_bj i_j + (2 wd * (grad_out / batch_size)) u_b
+ *   dI_j = sum_b g_bj u_b + (2 wd * (grad_out / batch_size) * c_j) i_j,   c_j = the batch rows whose positive is j, counted in integers
+ * One kernel with the roles swapped: a workgroup owns 32 output rows and a slab of <= 512 output columns and walks the other side in
+ * tiles of 128 rows; each output element is ONE chain acc = fmaf(g, w, acc) over the walked rows in ascending order from 0
+ * (v_mfma_f32_32x32x2_f32), the weight-decay term joins last as fmaf(coefficient, x, acc).  A width above 512 takes ceil(D / 512)
+ * slabs, each of which recomputes the scores over the full D: at D = 1 539 the score work is done four times.  When the output
+ * tiles are few the walked side is cut by rank_item_split into pieces; each piece writes a partial [rows, D] block (for dI with its own
+ * share of c_j, for dU the weight-decay term in piece 0) and one pass adds the pieces in ascending order; one piece stores directly.
+ * du / ditems may be NULL (not both): that gradient is not computed.  Nothing of size B x n_items is in memory; no float atomics;
+ * loss, lse, spos, dU and dI are bit-identical from run to run; no host synchronisation, so both calls can be captured.
+ *
+ * ngcf_softmax_full_plan (host only): out = {forward pieces, 1, dU pieces, dU column slabs, dI pieces, dI column slabs}.
+ * Workspace for both calls: ngcf_softmax_full_workspace_bytes(B, n_items, D) = the (max, sum) partials (2 x pieces x B floats), the
+ * loss partials and, where a gradient is cut, pieces x rows x D floats (NGCF_ERR_WORKSPACE when shorter; -1 for a bad shape).
+ */
+int ngcf_softmax_full_plan(int64_t B, int64_t n_items, int D, int64_t out[6]);
+int64_t ngcf_softmax_full_workspace_bytes(int64_t B, int64_t n_items, int D);
+int ngcf_softmax_full_f32(const float *users, int64_t ldu, int64_t B, const float *items, int64_t ldi, int64_t n_items, int D,
+                          const int64_t *pos, float inv_tau, float weight_decay, float batch_size, float *loss, float *lse,
+                          float *spos, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+int ngcf_softmax_full_backward_f32(const float *users, int64_t ldu, int64_t B, const float *items, int64_t ldi, int64_t n_items,
+                                   int D, const int64_t *pos, const float *lse, float inv_tau, float weight_decay,
+                                   float batch_size, const float *grad_out, float *du, int64_t lddu, float *ditems, int64_t lddi,
+                                   void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- backward pass (`loss.backward()` of experiment.py:57; driven by autograd.py) -------------- */
 /* Everything `loss.backward()` runs: no library GEMM at any width.  L^T.dLE re-uses ngcf_spmm_csr_f32 on the CSR of L^T. */
 /* du/dp/dn of the BPR loss (bprloss.py:15-22) times the upstream scalar *grad_out (device). */

@@ -1,7 +1,7 @@
 """Forward drivers of the propagation engine and the autograd seam for training.
 
 `propagate_forward` issues the HIP layer kernels for NGCF.py:120-147 (inference path, nothing saved).
-`Propagate` / `GatherTriple` / `BPRLoss` / `BPRMultiLoss` are `torch.autograd.Function`s so that `loss.backward()`
+`Propagate` / `GatherTriple` / `BPRLoss` / `BPRMultiLoss` / `SoftmaxFullLoss` are `torch.autograd.Function`s so that `loss.backward()`
 (experiment.py:57) reaches every parameter: their backward runs the HIP kernels of the "backward pass" section
 of include/ngcf_hip.h - weight and input gradients on the fp32 matrix cores, `L^T . dLE` on the SpMM kernels; no library
 GEMM at any width.
@@ -506,6 +506,25 @@ class BPRMultiLoss(torch.autograd.Function):
         u, p, n = ctx.saved_tensors
         du, dp, dn = _eng.losses.bpr_multi_backward(u, p, n, ctx.m, ctx.wd, ctx.bs, g.to(torch.float32).contiguous(), ctx.reduction)
         return du, dp, dn, None, None, None, None, None
+
+
+class SoftmaxFullLoss(torch.autograd.Function):
+    """The softmax over the whole catalogue (engine.losses): the forward keeps `lse`, the backward recomputes the scores.  The item
+    table's gradient is dense ([n_items, D]): autograd adds it to the row-sparse one of `GatherTriple` on the way to `all_E`."""
+
+    @staticmethod
+    def forward(ctx, u, items, pos, inv_tau, weight_decay, batch_size, ws, status):
+        ctx.inv_tau, ctx.wd, ctx.bs, ctx.ws = float(inv_tau), float(weight_decay), float(batch_size), ws
+        loss, lse = _eng.losses.softmax_full_loss(u, items, pos, inv_tau, weight_decay, batch_size, ws, status)
+        ctx.save_for_backward(u, items, pos, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        u, items, pos, lse = ctx.saved_tensors
+        du, di = _eng.losses.softmax_full_backward(u, items, pos, lse, ctx.inv_tau, ctx.wd, ctx.bs, g.to(torch.float32).contiguous(),
+                                                   ctx.ws, need_u=ctx.needs_input_grad[0], need_items=ctx.needs_input_grad[1])
+        return du, di, None, None, None, None, None, None
 
 
 def propagate_with_grad(owner, csrs, csrs_t_fn, user_w, item_w, w1, b1, w2, b2, drop, seeds, edge_drops=None,

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import engine as _eng
-from .autograd import BPRLoss, BPRMultiLoss
+from .autograd import BPRLoss, BPRMultiLoss, SoftmaxFullLoss
 
 
 class BPR(nn.Module):
@@ -54,3 +54,56 @@ class BPRMulti(nn.Module):
             return BPRMultiLoss.apply(u_idx, pos_idx, neg_idx, self.m, self.weight_decay, self.batch_size, self._ws, self.reduction)
         return _eng.losses.bpr_multi_loss(u_idx.detach().contiguous(), pos_idx.detach().contiguous(), neg_idx.detach().contiguous(),
                                           self.m, self.weight_decay, self.batch_size, self._ws, self.reduction)
+
+
+class SoftmaxFull(nn.Module):
+    """The softmax loss over the WHOLE catalogue, the limit of `BPR` (one negative) and `BPRMulti` (m <= 64): with
+    s_bj = <u_b, i_j> / temperature the loss is (sum_b (logsumexp_j s_bj - s_b,pos_b) + weight_decay (|u|^2 + sum_b |i_pos_b|^2)) /
+    batch_size, on the fused HIP kernels of `engine.losses` - the [B, n_items] score matrix and its gradient are never in memory.
+    Scores are plain: the `abs` of the reference's BPR is not applied (the ranking of `evaluate` has none either).
+
+    `forward(u_embeds, pos_item, item_table)` -> 0-dim tensor: `u_embeds` [B, D] are the user rows the model returns, `pos_item`
+    [B] int64 item ids, `item_table` [n_items, D] the propagated item rows.  A training loop:
+
+        u, _, _ = model(..., pos_item=pos, neg_item=torch.empty(0), node_flag=True)
+        loss = crit(u, pos, model.all_items_emb)
+
+    The item table's gradient reaches `all_E` as a dense block and meets the row-sparse one of the gathers in autograd.  A forward
+    replayed from the model's captured training graphs hands out a DETACHED `model.all_items_emb`, so the item table would silently
+    get no gradient: that raises a RuntimeError - set `model.auto_train_graph = False` for loops that use this loss.
+
+    `check_indices=True` reads the status word back after the launch and raises IndexError naming the first id outside the
+    catalogue (one host sync per call, the trade of `model.check_indices`); False never syncs and leaves the sticky int32 word in
+    `.status` (bit 0: some positive was out of range; such a row has no positive term)."""
+
+    def __init__(self, weight_decay, batch_size, temperature=1.0, check_indices=True):
+        super().__init__()
+        t = float(temperature)
+        if not (t > 0 and t < float("inf")):
+            raise ValueError(f"SoftmaxFull: temperature={temperature} is not a positive finite number")
+        self.weight_decay = weight_decay
+        self.batch_size = batch_size
+        self.temperature = t
+        self.check_indices = bool(check_indices)
+        self.status = None
+        self._ws = _eng.Workspace()
+
+    def forward(self, u_embeds, pos_item, item_table):
+        grad = torch.is_grad_enabled() and (u_embeds.requires_grad or item_table.requires_grad)
+        if grad and u_embeds.requires_grad and item_table.grad_fn is None and not item_table.requires_grad:
+            raise RuntimeError("SoftmaxFull: item_table carries no gradient although u_embeds does - a forward replayed from the "
+                               "captured training graphs returns a detached model.all_items_emb; set model.auto_train_graph = False "
+                               "for loops that use this loss")
+        inv_tau = 1.0 / self.temperature
+        if u_embeds.is_cuda and (self.status is None or self.status.device != u_embeds.device):
+            self.status = torch.zeros(1, dtype=torch.int32, device=u_embeds.device)
+        if grad:
+            loss = SoftmaxFullLoss.apply(u_embeds, item_table, pos_item, inv_tau, self.weight_decay, self.batch_size, self._ws, self.status)
+        else:
+            loss, _ = _eng.losses.softmax_full_loss(u_embeds.detach(), item_table.detach(), pos_item, inv_tau, self.weight_decay,
+                                                    self.batch_size, self._ws, self.status)
+        if self.check_indices and int(self.status.item()) != 0:
+            self.status.zero_()
+            bad = pos_item[(pos_item < 0) | (pos_item >= item_table.shape[0])]
+            raise IndexError(f"SoftmaxFull: pos_item holds {int(bad[0])}, outside the catalogue of {int(item_table.shape[0])} items")
+        return loss

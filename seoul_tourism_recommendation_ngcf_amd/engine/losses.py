@@ -1,14 +1,16 @@
 """BPR against `m` negatives per positive row (`ngcf_bpr_multi_f32` / `ngcf_bpr_multi_backward_f32`: csrc/bpr_multi.hip; in the
 header next to the BPR section): the loss of `[B, D]` users and positives and `[B*m, D]` negatives without expanding the batch to
-`B*m` triplets, and its three gradients.  Like the wrappers of `layers`, no check here costs a host sync."""
+`B*m` triplets, and its three gradients; and the limit of that series, the softmax over the WHOLE catalogue (`ngcf_softmax_full_f32`
+/ `ngcf_softmax_full_backward_f32`: csrc/softmax_full.hip), whose [B, n_items] score matrix is never in memory.  Like the wrappers
+of `layers`, no check here costs a host sync."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
 from .. import _lib
-from ._plumbing import Workspace, _on, _ptr, _require_device, _require_dtype, _require_same_device, _stream
+from ._plumbing import Workspace, _on, _ptr, _require_device, _require_dtype, _require_same_device, _status_word, _stream
 
 M_MAX = 64                                       # NGCF_BPR_MULTI_M_MAX: lane j of a row's wave keeps negative j
 REDUCTIONS = {"mean": 0, "softmax": 1}           # NGCF_BPR_MULTI_MEAN, NGCF_BPR_MULTI_SOFTMAX
@@ -69,3 +71,100 @@ def bpr_multi_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int
         _lib.check(lib.ngcf_bpr_multi_backward_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, red, float(weight_decay),
                                                    float(batch_size), _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
     return du, dp, dn
+
+
+# ---- the softmax over the whole catalogue (`ngcf_softmax_full_f32` / `ngcf_softmax_full_backward_f32`: csrc/softmax_full.hip) ------
+def _full_operands(fn: str, u: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, inv_tau: float) -> Tuple[int, int, int]:
+    """The refusals of both full-catalogue calls, before anything reaches the device: (B, n_items, D)."""
+    for nm, t in (("u", u), ("items", items)):
+        if t.dim() != 2:
+            raise ValueError(f"{fn}: {nm} must be 2-D, got shape {tuple(t.shape)}")
+    if pos.dim() != 1:
+        raise ValueError(f"{fn}: pos must be 1-D, got shape {tuple(pos.shape)}")
+    B, D, n_items = int(u.shape[0]), int(u.shape[1]), int(items.shape[0])
+    if B < 1 or D < 1:
+        raise ValueError(f"{fn}: u is {tuple(u.shape)}: at least one row and one column expected")
+    if n_items < 1:
+        raise ValueError(f"{fn}: items is {tuple(items.shape)}: at least one item expected")
+    if int(items.shape[1]) != D:
+        raise ValueError(f"{fn}: u {tuple(u.shape)} and items {tuple(items.shape)} differ in width")
+    if int(pos.shape[0]) != B:
+        raise ValueError(f"{fn}: pos has {int(pos.shape[0])} ids for {B} rows of u")
+    _require_dtype(fn, torch.float32, (("u", u), ("items", items)))
+    _require_dtype(fn, torch.int64, (("pos", pos),))
+    for nm, t in (("u", u), ("items", items)):
+        if D > 1 and t.stride(1) != 1:
+            raise ValueError(f"{fn}: {nm} must have unit stride in its last dimension, got strides {t.stride()}")
+        if int(t.shape[0]) > 1 and t.stride(0) < D:
+            raise ValueError(f"{fn}: the rows of {nm} overlap, strides {t.stride()}")
+    if not (inv_tau > 0 and inv_tau < float("inf")):
+        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+    _require_device(u, "u")
+    _require_same_device(fn, (("items", items), ("pos", pos)), "u", u.device)
+    return B, n_items, D
+
+
+def _ld(t: torch.Tensor) -> int:
+    return int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+
+
+def softmax_full_plan(B: int, n_items: int, D: int) -> dict:
+    """How the three launches cut a shape (host only): pieces of the walked side and column slabs of the forward, dU and dI."""
+    import ctypes as C
+    out = (C.c_int64 * 6)()
+    _lib.check(_lib.load().ngcf_softmax_full_plan(int(B), int(n_items), int(D), out))
+    return {"forward": (out[0], out[1]), "du": (out[2], out[3]), "ditems": (out[4], out[5])}
+
+
+def softmax_full_loss(u: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, inv_tau: float, weight_decay: float, batch_size: float,
+                      ws: Workspace, status: Optional[torch.Tensor] = None, spos: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`(loss, lse)` of the softmax over the whole catalogue: `u` [B, D] and `items` [n_items, D] float32 rows (unit inner stride, any
+    row stride: `model.all_items_emb` as it is), `pos` [B] int64.  With s_bj = <u_b, i_j> * inv_tau, `lse` [B] is logsumexp_j s_bj and
+    the loss (sum_b (lse_b - s_b,pos_b) + weight_decay (|u|^2 + sum_b |i_pos_b|^2)) / batch_size as a 0-dim device tensor; no
+    [B, n_items] matrix exists.  An id of `pos` outside the catalogue is never an index: its row has no positive term and bit 0 of
+    `status` (an int32 device word, sticky; None: a word nobody reads) is set - no check here costs a host sync.  `spos` [B]
+    float32, when given, receives the positives' scores."""
+    B, n_items, D = _full_operands("softmax_full_loss", u, items, pos, inv_tau)
+    dev = u.device
+    status, _ = _status_word("softmax_full_loss", status, dev)
+    if spos is None:
+        spos = torch.empty(B, dtype=torch.float32, device=dev)
+    elif spos.dtype != torch.float32 or tuple(spos.shape) != (B,) or spos.device != dev or not spos.is_contiguous():
+        raise ValueError(f"softmax_full_loss: spos must be a contiguous float32 tensor of {B} elements on {dev}")
+    lib = _lib.load()
+    w = ws.get(int(lib.ngcf_softmax_full_workspace_bytes(B, n_items, D)), dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    pos = pos.contiguous()
+    with _on(dev):
+        _lib.check(lib.ngcf_softmax_full_f32(_ptr(u), _ld(u), B, _ptr(items), _ld(items), n_items, D, _ptr(pos), float(inv_tau),
+                                             float(weight_decay), float(batch_size), _ptr(loss), _ptr(lse), _ptr(spos), _ptr(status),
+                                             _ptr(w), w.numel(), _stream()))
+    return loss, lse
+
+
+def softmax_full_backward(u: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, lse: torch.Tensor, inv_tau: float,
+                          weight_decay: float, batch_size: float, grad_out: torch.Tensor, ws: Workspace, need_u: bool = True,
+                          need_items: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """`(du, ditems)` of `softmax_full_loss` times the upstream scalar `grad_out` (one float32 on the device), from the `lse` the
+    forward returned: the scores are recomputed, two launches of one kernel with the roles swapped.  `ditems` is dense, [n_items, D]
+    contiguous; a gradient that is not needed (`need_u` / `need_items` False) is not computed and comes back as None."""
+    B, n_items, D = _full_operands("softmax_full_backward", u, items, pos, inv_tau)
+    dev = u.device
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or lse.device != dev or not lse.is_contiguous():
+        raise ValueError(f"softmax_full_backward: lse must be a contiguous float32 tensor of {B} elements on {dev}")
+    if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != dev:
+        raise ValueError(f"softmax_full_backward: grad_out must be one float32 on {dev}")
+    if not (need_u or need_items):
+        return None, None
+    lib = _lib.load()
+    w = ws.get(int(lib.ngcf_softmax_full_workspace_bytes(B, n_items, D)), dev)
+    du = torch.empty((B, D), dtype=torch.float32, device=dev) if need_u else None
+    di = torch.empty((n_items, D), dtype=torch.float32, device=dev) if need_items else None
+    pos = pos.contiguous()
+    with _on(dev):
+        _lib.check(lib.ngcf_softmax_full_backward_f32(_ptr(u), _ld(u), B, _ptr(items), _ld(items), n_items, D, _ptr(pos), _ptr(lse),
+                                                      float(inv_tau), float(weight_decay), float(batch_size), _ptr(grad_out),
+                                                      _ptr(du), D, _ptr(di), D, _ptr(w), w.numel(), _stream()))
+    return du, di
