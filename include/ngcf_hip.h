@@ -685,6 +685,52 @@ int ngcf_sample_hard_f32(const int64_t *seen_rowptr, const int32_t *seen_colidx,
                          int D, const int64_t *user_ids, int64_t T, int64_t case_offset, int m, uint64_t seed, int64_t *neg,
                          float *score, int32_t *slot, int32_t *status, void *stream);
 
+/* Popularity-weighted negatives for T cases in one launch: m distinct items the case's user has no stored interaction with, drawn in
+ * proportion to an integer weight w_i per item.  The seen sets are those of ngcf_sample_unseen; w_i in [0, 2^40],
+ * n_items in [1, 2^31), W = sum of all w_i in [1, 2^62).  The law is successive sampling, np.random.choice(p = w / sum, replace =
+ * False): slot 0 is item i with probability w_i / U over the user's unseen items, U their weight; slot j is item i with probability
+ * w_i / U_j over the unseen items not drawn yet, U_j = U - (w of slots 0 .. j-1).  An item of weight 0 is never drawn.  Integer
+ * weights make every comparison exact and the result recomputable on the host.
+ *
+ * Prepared arrays, once per (seen sets, weights):
+ *   cdf  int64 [n_items + 1]   cdf[i] = sum of w_i' over i' < i, so cdf[0] = 0, cdf[n_items] = W and w_i = cdf[i+1] - cdf[i]; the
+ *                              caller's (an int64 prefix sum is exact)
+ *   gap  int64, one per stored entry of the seen sets, at the entry's position in seen_colidx: for the k-th seen item c_k of a row,
+ *                              gap_k = cdf[c_k] - S_k with S_k = sum of w[c_k'] over k' < k - the unseen weight below c_k; it
+ *                              does not decrease with k
+ *   mass int64 [n_rows]        U = W - S_len, the user's unseen weight
+ * ngcf_weighted_prepare fills gap and mass from cdf, one wave per seen row, integer adds only (identical from run to run); S_K is
+ * recovered as cdf[c_K] - gap_K for K < len and as W - mass[u] for K = len.  Its *status is OR-ed into, never cleared: 4 = a stored
+ * id outside [0, n_items) (it counts as weight 0; arrays prepared from such sets are not to be drawn from).
+ *
+ * The draw of case `row`, user u = user_ids[row], is a pure function of (seed, t = case_offset + row, the seen row, the weights), with
+ * no rejection loop, all arithmetic unsigned 64-bit; fmix, the case key and the step constant are ngcf_sample_unseen's:
+ *   a = fmix(seed ^ (t * 0x9E3779B97F4A7C15))
+ *   for j in 0 .. m-1:
+ *     r'  = mulhi64(fmix(a + (j + 1) * 0xD1B54A32D192ED03), U_j)                  a point in [0, U_j)
+ *     step over the drawn intervals (q_i, w_i), i < j, of the user's unseen coordinate:
+ *           e_i = q_i - sum of w_i' over the i' with q_i' < q_i ;  r = r' + sum of w_i over the i with e_i <= r'
+ *     K   = #{k : gap_k <= r}                                                     a search of the user's gap row
+ *     tgt = r + S_K
+ *     c_j = the largest i with cdf[i] <= tgt                                      a search of cdf; w[c_j] > 0 and c_j is unseen
+ *     q_j = cdf[c_j] - S_K ;  U_{j+1} = U_j - w[c_j]
+ * mulhi64 without rejection gives every point of [0, U_j) floor(2^64 / U_j) hash values or one more: a relative bias of at most
+ * U_j / 2^64 per point (< 2^-2 at the largest admissible U, 2^-34 at U = 2^30), the trade ngcf_sample_unseen makes.  A case set drawn in chunks with case_offset = the
+ * chunk's first case equals the set drawn at once, and slot 0 of a draw of m items is the draw of one item.
+ * out[row*ld_out + 0..m): the items; draw_weight[row*ld_weight + 0..m) (may be NULL): w of each; case_mass[row] (may be NULL): U -
+ * so slot j's proposal probability is exactly draw_weight_j / (case_mass - sum of draw_weight over the slots before j).  *status is
+ * OR-ed into, never cleared: 1 = a user id outside [0, n_rows) (no id is used as an index before it is checked; its case_mass is
+ * 0), 2 = a user with fewer than m positive-weight unseen items (U_j = 0 at some step); all slots of such a case are -1 and its
+ * weights 0.  Argument errors, before any launch: m outside [1, NGCF_SAMPLE_WEIGHTED_M_MAX], n_items outside [1, 2^31), ld_out (or,
+ * with draw_weight, ld_weight) < m, a null pointer; T == 0 (n_rows == 0 for the preparation) is not an error. */
+#define NGCF_SAMPLE_WEIGHTED_M_MAX 64
+int ngcf_weighted_prepare(const int64_t *seen_rowptr, const int32_t *seen_colidx, int64_t col_offset, int64_t n_rows, int64_t n_items,
+                          const int64_t *cdf, int64_t *gap, int64_t *mass, int32_t *status, void *stream);
+int ngcf_sample_weighted(const int64_t *seen_rowptr, const int32_t *seen_colidx, int64_t col_offset, int64_t n_rows, int64_t n_items,
+                         const int64_t *cdf, const int64_t *gap, const int64_t *mass, const int64_t *user_ids, int64_t T,
+                         int64_t case_offset, int m, uint64_t seed, int64_t *out, int64_t ld_out, int64_t *draw_weight,
+                         int64_t ld_weight, int64_t *case_mass, int32_t *status, void *stream);
+
 /* Per-segment quantile floor, the numeric core of the reference's Preprocess.scale_implicit (utils.py:103-122) for every
  * user in one call.  Segment u is the entries order[rowptr[u] .. rowptr[u+1]), positions into x and out (both double [T]); order ==
  * NULL is the identity: x is already grouped.  With z(v) = ((v - mean) / scale) + shift (0, 1, 0: the identity) and, for the n values

@@ -120,6 +120,9 @@ PROTOTYPES = {
     "ngcf_sample_unseen": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, C.c_int, _u64, _vp, _vp, _i64, _vp, _vp]),
     "ngcf_sample_hard_f32": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_int, _vp, _i64, _i64, C.c_int, _u64,
                                        _vp, _vp, _vp, _vp, _vp]),
+    "ngcf_weighted_prepare": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ngcf_sample_weighted": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, _u64, _vp, _i64, _vp, _i64,
+                                       _vp, _vp, _vp]),
     "ngcf_segment_quantile_floor_f64": (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp,
                                                  _vp, _vp]),
     "ngcf_yeo_johnson_f64": (C.c_int, [_vp, _i64, C.c_double, _vp, _vp]),

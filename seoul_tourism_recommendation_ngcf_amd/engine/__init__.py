@@ -4,7 +4,7 @@ Everything here hands `tensor.data_ptr()` + the current HIP stream to libngcf_hi
 streams only; no tensor arithmetic of the hot path happens in torch.  Importing the package neither loads the library nor touches
 the device: `_lib.load()` runs inside the calls.  Callers reach every name below, the private ones included, as `engine.<name>`;
 the trip-context family (csrc/context.hip), the delimited-text family (csrc/text.hip), the optimizer step (csrc/adam.hip), the exact
-held-out positions (csrc/rank_position.hip), the hard negatives (csrc/sample_hard.hip), the loss against m negatives per positive
+held-out positions (csrc/rank_position.hip), the hard and the popularity-weighted negatives (csrc/sample_hard.hip, csrc/sample_weighted.hip), the loss against m negatives per positive
 (csrc/bpr_multi.hip) and the beyond-accuracy list figures with the diversifying re-rank (csrc/list_quality.hip, csrc/list_rerank.hip) keep their modules' names: `engine.context.<name>`,
 `engine.text.<name>`, `engine.optim.<name>`, `engine.ranks.<name>`, `engine.negatives.<name>`, `engine.losses.<name>`,
 `engine.lists.<name>`.

@@ -1,6 +1,8 @@
 """Hard negatives on the device (`ngcf_sample_hard_f32`: csrc/sample_hard.hip; in the header next to `ngcf_sample_unseen`): of `m`
 unseen draws per case, the one the current embeddings score highest - `sample_unseen`, `eval_candidates`' scores and an argmax in
-one launch, with one item per case written to memory."""
+one launch, with one item per case written to memory.  And popularity-weighted negatives (`ngcf_weighted_prepare`,
+`ngcf_sample_weighted`: csrc/sample_weighted.hip): `m` distinct unseen items per case in proportion to an integer weight per item,
+with the weights and the unseen mass from which the proposal probability follows exactly."""
 from __future__ import annotations
 
 from typing import Optional
@@ -81,3 +83,115 @@ def hard_unseen(seen: ItemSets, user_emb: torch.Tensor, item_emb: torch.Tensor, 
     if not (return_score or return_slot):
         return neg
     return (neg,) + ((score,) if return_score else ()) + ((slot,) if return_slot else ())
+
+
+# ---- popularity-weighted negatives (ngcf_weighted_prepare, ngcf_sample_weighted: csrc/sample_weighted.hip) ----------------------------
+WEIGHTED_M_MAX = 64                              # NGCF_SAMPLE_WEIGHTED_M_MAX: lane j of a case's wave keeps drawn interval j
+WEIGHT_MAX = 2 ** 40                             # the largest weight of one item
+WEIGHT_TOTAL_MAX = 2 ** 62                       # the sum of all weights lies below it
+
+
+class WeightedSets:
+    """Seen sets with an integer weight per item, prepared for `weighted_unseen`: `cdf` int64 [n_items + 1] (the weight below every
+    item, `torch.cumsum` - exact in int64), `gap` int64 (one per stored entry of `seen`: the unseen weight below that entry) and
+    `mass` int64 [n_rows] (every user's unseen weight), the last two by ngcf_weighted_prepare.  `weights`: int64 [seen.n_items] on
+    the sets' device, every value in [0, 2^40].  One read-back, of the total W with the weights' range, refuses W = 0, W >= 2^62
+    and a weight that is negative or above 2^40 with ValueError.  Prepare once per (seen sets, weights); the draws only read it."""
+
+    def __init__(self, seen: ItemSets, weights: torch.Tensor):
+        lib = _lib.load()
+        _require_dtype("WeightedSets", torch.int64, (("weights", weights),))
+        if weights.dim() != 1 or int(weights.numel()) != seen.n_items:
+            raise ValueError(f"WeightedSets: weights must be [n_items = {seen.n_items}], got {tuple(weights.shape)}")
+        if seen.n_items < 1 or seen.n_items >= 2 ** 31:
+            raise ValueError(f"WeightedSets: n_items={seen.n_items} outside [1, 2^31)")
+        _require_device(seen.rowptr, "the item sets")
+        dev = seen.rowptr.device
+        _check_sets(seen, dev, 0, "WeightedSets")
+        if seen.rowptr.dtype != torch.int64 or seen.colidx.dtype != torch.int32:
+            raise TypeError("WeightedSets: the item sets must be int64 row pointers and int32 columns")
+        _require_same_device("WeightedSets", (("weights", weights),), "the item sets", dev)
+        self.seen = seen
+        self.cdf = torch.zeros(seen.n_items + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(weights, 0, out=self.cdf[1:])
+        self.gap = torch.empty(max(int(seen.colidx.numel()), 1), dtype=torch.int64, device=dev)
+        self.mass = torch.empty(max(seen.n_rows, 1), dtype=torch.int64, device=dev)
+        # a set without entries has no column array to point at; its row pointers are all 0 and nothing is read through it
+        self._colidx = seen.colidx if seen.colidx.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        with _on(dev):
+            # the kernel reads nothing through a value of cdf, so it may run before the weights' range is known
+            _lib.check(lib.ngcf_weighted_prepare(_ptr(seen.rowptr), _ptr(self._colidx), seen.col_offset, seen.n_rows, seen.n_items,
+                                                 _ptr(self.cdf), _ptr(self.gap), _ptr(self.mass), _ptr(status), _stream()))
+        # the int64 sum wraps from 2^63 on: an fp64 sum, capped at 2^62, tells a wrapped total from a small one
+        coarse = weights.sum(dtype=torch.float64).clamp(max=float(WEIGHT_TOTAL_MAX)).to(torch.int64)
+        total, coarse, lowest, highest, bits = torch.stack((self.cdf[-1], coarse, weights.min(), weights.max(),
+                                                            status[0].to(torch.int64))).tolist()
+        if lowest < 0 or highest > WEIGHT_MAX:
+            raise ValueError(f"WeightedSets: the weights span [{lowest}, {highest}], outside [0, 2^40]")
+        if total < 1 or total >= WEIGHT_TOTAL_MAX or coarse >= WEIGHT_TOTAL_MAX:
+            raise ValueError(f"WeightedSets: the weights sum to {total}, outside [1, 2^62)")
+        if bits:
+            raise IndexError(f"WeightedSets: a stored item id of the seen sets lies outside [0, {seen.n_items})")
+        self.total = int(total)
+
+    @property
+    def n_rows(self) -> int:
+        return self.seen.n_rows
+
+    @property
+    def n_items(self) -> int:
+        return self.seen.n_items
+
+
+def weighted_unseen(wsets: WeightedSets, user_ids: torch.Tensor, m: int, seed: int, *, case_offset: int = 0,
+                    return_weights: bool = False, out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """`m` distinct items per case that the case's user has no entry for in `wsets.seen`, drawn in proportion to the items' weights
+    (ngcf_sample_weighted): slot 0 is item i with probability w_i / U over the user's unseen items (U: their weight, `wsets.mass`),
+    slot j with probability w_i / U_j over those not drawn yet, U_j = U - (the weights of slots 0 .. j-1) - successive sampling, the
+    law of `np.random.choice(p=w / w.sum(), replace=False)`, not numpy's stream; an item of weight 0 is never drawn.  Case t of
+    user `user_ids[t]` (int64 [T] on the sets' device) is a pure function of (seed, case_offset + t, the user's seen row, the
+    weights), written out in include/ngcf_hip.h: a case set drawn in chunks with `case_offset` equals the set drawn at once, and
+    column 0 of a draw of m items is the draw of one.  With all weights 1 the law is `sample_unseen`'s uniform one, the items are
+    not.  `m` in [1, 64].  Returns int64 [T, m] - with `return_weights` a tuple (items, draw_weight int64 [T, m], case_mass int64
+    [T]): the weight of every drawn item and U, so slot j's proposal probability is exactly
+    draw_weight[t, j] / (case_mass[t] - draw_weight[t, :j].sum()).  `out`: an int64 row-major tensor of T rows and at least m columns
+    to write the items into (the returned tensor is a view of its leading columns).  A user id outside the sets raises IndexError,
+    a user with fewer than `m` positive-weight unseen items ValueError, after one host sync; every slot of such a case is -1 and
+    its weights 0.  With a caller's int32 `status` word the bits (1, 2) are only OR-ed into it and the call neither syncs nor
+    raises."""
+    m, seed = int(m), int(seed) & 0xFFFFFFFFFFFFFFFF
+    # shapes, types and limits first (they hold on any device), then where the tensors live
+    if m < 1 or m > WEIGHTED_M_MAX:
+        raise ValueError(f"weighted_unseen: m={m} outside [1, {WEIGHTED_M_MAX}]")
+    if not isinstance(wsets, WeightedSets):
+        raise TypeError(f"weighted_unseen: wsets must be a WeightedSets, got {type(wsets).__name__}")
+    _require_dtype("weighted_unseen", torch.int64, (("user_ids", user_ids), ("out", out)))
+    if user_ids.dim() != 1:
+        raise ValueError(f"weighted_unseen: user_ids must be [T], got {tuple(user_ids.shape)}")
+    T = int(user_ids.numel())
+    if out is not None and (out.dim() != 2 or int(out.shape[0]) != T or int(out.shape[1]) < m):
+        raise ValueError(f"weighted_unseen: out must be [T = {T}, >= {m}], got {tuple(out.shape)}")
+    lib = _lib.load()
+    seen = wsets.seen
+    dev = wsets.cdf.device
+    _require_device(wsets.cdf, "the weighted sets")
+    _require_same_device("weighted_unseen", (("user_ids", user_ids), ("out", out), ("status", status)), "the weighted sets", dev)
+    status, check_status = _status_word("weighted_unseen", status, dev)
+    user_ids = user_ids.contiguous()
+    if out is None:
+        out = torch.empty((T, m), dtype=torch.int64, device=dev)
+    draw_weight = torch.empty((T, m), dtype=torch.int64, device=dev) if return_weights else None
+    case_mass = torch.empty(T, dtype=torch.int64, device=dev) if return_weights else None
+    with _on(dev):
+        _lib.check(lib.ngcf_sample_weighted(_ptr(seen.rowptr), _ptr(wsets._colidx), seen.col_offset, seen.n_rows, seen.n_items,
+                                            _ptr(wsets.cdf), _ptr(wsets.gap), _ptr(wsets.mass), _ptr(user_ids), T, int(case_offset),
+                                            m, seed, _ptr(out), _row_major_ld(out, "out"), _ptr(draw_weight), m, _ptr(case_mass),
+                                            _ptr(status), _stream()))
+    if check_status and T:
+        bits = int(status.item())
+        if bits & 1:
+            raise IndexError(f"weighted_unseen: a user id lies outside [0, {seen.n_rows})")
+        if bits & 2:
+            raise ValueError(f"weighted_unseen: a user has fewer than m={m} unseen items of positive weight among {seen.n_items}")
+    return (out[:, :m], draw_weight, case_mass) if return_weights else out[:, :m]

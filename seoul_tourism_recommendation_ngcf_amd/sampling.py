@@ -263,3 +263,127 @@ class NegativesLoader:
         neg = rows[:, self.n_columns:].contiguous()                             # [used, m]
         for b0 in range(0, used, self.batch_size):
             yield tuple(cols[:, b0:b0 + self.batch_size].unbind(0)) + (neg[b0:b0 + self.batch_size].reshape(-1),)
+
+
+# ---- popularity-weighted negatives (engine.negatives.weighted_unseen) ----------------------------------------------------------------
+def popularity_weights(items: torch.Tensor, n_item: int, alpha: float = 0.75, resolution: int = 1024) -> torch.Tensor:
+    """Integer item weights from the items' counts in `items` (the positives' item column; ids in [0, n_item)), int64 [n_item] on the
+    tensor's device: the counts themselves with `alpha` = 1, all ones with `alpha` = 0, otherwise
+    floor(count^alpha * resolution + 0.5) in fp64 - at least 1 where the count is positive, 0 where it is 0, so an item nobody
+    interacted with is never drawn.  alpha = 0.75 is the usual smoothing of a popularity sampler.  The weights are data: the draw is
+    exact in them, and nothing downstream depends on how `pow` rounds.  Plain torch: it runs wherever `items` lives."""
+    n_item, alpha, resolution = int(n_item), float(alpha), int(resolution)
+    if items.dim() != 1 or items.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"popularity_weights: items must be an integer [T] tensor, got {items.dtype} {tuple(items.shape)}")
+    if n_item < 1 or resolution < 1 or alpha < 0:
+        raise ValueError(f"popularity_weights: n_item={n_item}, alpha={alpha}, resolution={resolution}")
+    if alpha == 0:
+        return torch.ones(n_item, dtype=torch.int64, device=items.device)
+    if items.numel() and (int(items.min()) < 0 or int(items.max()) >= n_item):
+        raise IndexError(f"popularity_weights: an item id lies outside [0, {n_item})")
+    counts = torch.bincount(items.to(torch.int64), minlength=n_item)
+    if alpha == 1:
+        return counts
+    scaled = torch.floor(counts.to(torch.float64).pow(alpha) * resolution + 0.5).to(torch.int64)
+    return torch.where(counts > 0, scaled.clamp(min=1), torch.zeros_like(scaled))
+
+
+def _weighted_sets(weights, seen: Optional[engine.ItemSets], what: str) -> "engine.negatives.WeightedSets":
+    """`weights` as prepared sets: an int64 [n_item] tensor is prepared against `seen`, a `WeightedSets` is taken as it is."""
+    if isinstance(weights, engine.negatives.WeightedSets):
+        if seen is not None and seen is not weights.seen:
+            raise ValueError(f"{what}: the prepared weights belong to other seen sets")
+        return weights
+    return engine.negatives.WeightedSets(seen, weights)
+
+
+def weighted_negatives(users: torch.Tensor, items: torch.Tensor, weights, seen: Optional[engine.ItemSets] = None, *, m: int, seed: int,
+                       epoch: int = 0, n_user: int, n_item: int, return_logq: bool = False):
+    """`train_negatives` with popularity-weighted negatives: returns (users, items, neg) with `neg` int64 [T, m], row t the m distinct
+    items of row t of `engine.negatives.weighted_unseen(wsets, users, m, seed_e)`, seed_e = fmix(seed + epoch) as in
+    `train_triplets` - slot j is item i with probability w_i / U_j over the user's unseen items not drawn before, successive
+    sampling.  `weights`: int64 [n_item] (e.g. `popularity_weights(items, n_item)`), prepared against `seen` (default: the positives
+    themselves) in this call - or an `engine.negatives.WeightedSets`, prepared once and passed to every call.  It is this
+    distribution, not anyone's random stream; with all-ones weights it is uniform but does not return `train_negatives`' items.
+    With `return_logq` a fourth tensor, float64 [T, m]: logq[t, j] = log(w_j / U_j), the log proposal probability of slot j given
+    the slots before it, formed in torch from the kernel's exact integers - what a sampled softmax subtracts from the negatives'
+    scores (the corrected loss itself is not part of this package yet).  `m` in [1, 64].  A user id outside the sets raises
+    IndexError, a user with fewer than `m` positive-weight unseen items ValueError."""
+    m = int(m)
+    if m < 1 or m > engine.negatives.WEIGHTED_M_MAX:
+        raise ValueError(f"weighted_negatives: m={m} outside [1, {engine.negatives.WEIGHTED_M_MAX}]")
+    prepared = isinstance(weights, engine.negatives.WeightedSets)
+    if not prepared:
+        if weights.dtype != torch.int64:
+            raise TypeError(f"weighted_negatives: weights must be int64, got {weights.dtype}")
+        if weights.dim() != 1 or int(weights.numel()) != int(n_item):
+            raise ValueError(f"weighted_negatives: weights must be [n_item = {int(n_item)}], got {tuple(weights.shape)}")
+    users, items, seen = _rows(users, items, weights.seen if prepared and seen is None else seen, n_user, n_item, "weighted_negatives")
+    wsets = _weighted_sets(weights, seen, "weighted_negatives")
+    seed_e = fmix(int(seed) + int(epoch))
+    if not return_logq:
+        return users, items, engine.negatives.weighted_unseen(wsets, users, m, seed_e)
+    neg, w, mass = engine.negatives.weighted_unseen(wsets, users, m, seed_e, return_weights=True)
+    left = mass[:, None] - (torch.cumsum(w, 1) - w)                                     # U_j, exact in int64
+    return users, items, neg, torch.log(w.to(torch.float64) / left.to(torch.float64))
+
+
+def weighted_triplets(users: torch.Tensor, items: torch.Tensor, weights, seen: Optional[engine.ItemSets] = None, *, seed: int,
+                      epoch: int = 0, n_user: int, n_item: int, return_logq: bool = False):
+    """`weighted_negatives` with one negative per row, the shape of `train_triplets`: (users, items, neg int64 [T]) - and with
+    `return_logq` the float64 [T] log(w / U) of every negative."""
+    got = weighted_negatives(users, items, weights, seen, m=1, seed=seed, epoch=epoch, n_user=n_user, n_item=n_item,
+                             return_logq=return_logq)
+    return got[:2] + tuple(t[:, 0] for t in got[2:])
+
+
+class WeightedNegativesLoader:
+    """`NegativesLoader` with popularity-weighted negatives: the batch protocol, `columns`, `shuffle`, `drop_last` and `generator`
+    are `TripletLoader`'s, a batch is `(*columns[b], items[b], neg[b].reshape(-1))`, and every `iter()` redraws all negatives with
+    epoch e = 0, 1, 2, ... (`.epoch` is the number of the next one): `neg` = `weighted_negatives(users, items, weights, seen, m=m,
+    seed=seed, epoch=e, ...)[2]`, written straight into the loader's row table.  `weights`: int64, one per item of `seen`
+    (default: `ItemSets.from_pairs` over the positives and `weights.numel()` items), prepared once at construction
+    (`.wsets`, an `engine.negatives.WeightedSets`)."""
+
+    def __init__(self, users: torch.Tensor, items: torch.Tensor, weights: torch.Tensor, columns: Sequence[torch.Tensor] = (), *,
+                 batch_size: int, m: int, seed: int, shuffle: bool = True, drop_last: bool = True,
+                 generator: Optional[torch.Generator] = None, seen: Optional[engine.ItemSets] = None):
+        cols = list(columns) if len(columns) else [users]
+        cols += [items]
+        n = int(users.numel())
+        for c in [users] + cols:
+            if c.dim() != 1 or int(c.numel()) != n:
+                raise ValueError(f"WeightedNegativesLoader: every column must be [n = {n}], got {tuple(c.shape)}")
+            if c.device != users.device:
+                raise RuntimeError(f"WeightedNegativesLoader: a column is on {c.device}, users on {users.device}")
+        if int(batch_size) < 1:
+            raise ValueError(f"WeightedNegativesLoader: batch_size={batch_size}")
+        if int(m) < 1 or int(m) > engine.negatives.WEIGHTED_M_MAX:
+            raise ValueError(f"WeightedNegativesLoader: m={m} outside [1, {engine.negatives.WEIGHTED_M_MAX}]")
+        if weights.dtype != torch.int64 or weights.dim() != 1:
+            raise TypeError(f"WeightedNegativesLoader: weights must be an int64 [n_item] tensor, got {weights.dtype} {tuple(weights.shape)}")
+        engine._require_device(users, "users")
+        self.n_columns, self.m = len(cols), int(m)
+        self.table = torch.empty((n, self.n_columns + self.m), dtype=torch.int64, device=users.device)     # [n, columns | negatives]
+        torch.stack([c.to(torch.int64) for c in cols], dim=1, out=self.table[:, :self.n_columns])
+        self.users = users.to(torch.int64).contiguous()
+        if seen is None:
+            n_user = int(self.users.max()) + 1 if n else 1
+            seen = engine.ItemSets.from_pairs(self.users, self.table[:, self.n_columns - 1].contiguous(), n_user, int(weights.numel()))
+        self.seen = seen
+        self.wsets = engine.negatives.WeightedSets(seen, weights)
+        self.n, self.batch_size = n, int(batch_size)
+        self.seed, self.epoch = int(seed), 0
+        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
+
+    def __len__(self) -> int:
+        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
+
+    def __iter__(self):
+        if self.n:
+            engine.negatives.weighted_unseen(self.wsets, self.users, self.m, fmix(self.seed + self.epoch),
+                                             out=self.table[:, self.n_columns:])
+        self.epoch += 1
+        return self._batches()
+
+    _batches = NegativesLoader._batches
