@@ -5,7 +5,7 @@
 
 // ---------------------------------------------------------------------------------------------
 // The draw itself - the case key, the partial Fisher-Yates map kept as (key, value) entries, ranks to items - is written out in
-// sample_device.h, which sample_hard.hip shares.
+// sample_device.h, which sample_hard.hip and sample_weighted.hip share.
 //
 // Mapping.  m == 1 (training triplets): a lane per case, no map.  m > 1: a wave per case, 64 steps per chunk; the entries of the
 // chunk in work live in the lanes, those of earlier chunks (m > 64 only) in the wave's LDS region [2][round_up(m, 64)].
@@ -86,21 +86,18 @@ extern "C" int ngcf_sample_unseen(const int64_t *seen_rowptr, const int32_t *see
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (m < 1 || m > NGCF_SAMPLE_M_MAX) return fail(NGCF_ERR_ARG, "sample_unseen: m=%d outside [1, %d]", m, NGCF_SAMPLE_M_MAX);
-    if (n_items < 1 || n_items >= (int64_t)1 << 31)
-        return fail(NGCF_ERR_ARG, "sample_unseen: n_items=%lld outside [1, 2^31)", (long long)n_items);
-    if (ld_out < m + (first ? 1 : 0))
-        return fail(NGCF_ERR_ARG, "sample_unseen: ld_out=%lld is below the %d columns of a row", (long long)ld_out, m + (first ? 1 : 0));
-    if (T < 0 || n_rows < 0) return fail(NGCF_ERR_ARG, "sample_unseen: bad argument");
+    if (int e = sample_check_items("sample_unseen", n_items)) return e;
+    if (int e = sample_check_ld("sample_unseen", "ld_out", ld_out, m + (first ? 1 : 0))) return e;
+    if (int e = sample_check_counts("sample_unseen", T, n_rows)) return e;
     if (T == 0) return NGCF_OK;
-    if (!seen_rowptr || !seen_colidx || !user_ids || !out || !status) return fail(NGCF_ERR_ARG, "sample_unseen: null argument");
+    if (int e = sample_check_pointers("sample_unseen", {seen_rowptr, seen_colidx, user_ids, out, status})) return e;
 
     if (m == 1) {
         sample_unseen_one_kernel<<<dim3((unsigned)grid_for(T, 256)), 256, 0, stream>>>(
             seen_rowptr, seen_colidx, col_offset, n_rows, n_items, user_ids, T, case_offset, seed, first, out, ld_out, status);
     } else {
         const size_t lds = m > 64 ? sizeof(int) * NGCF_SAMPLE_WAVES * 2 * (size_t)((m + 63) & ~63) : 0;      // at most 32 KiB
-        const int blocks = (int)std::min<int64_t>((T + NGCF_SAMPLE_WAVES - 1) / NGCF_SAMPLE_WAVES, 256 * 8);
-        sample_unseen_wave_kernel<<<dim3((unsigned)blocks), 64 * NGCF_SAMPLE_WAVES, lds, stream>>>(
+        sample_unseen_wave_kernel<<<dim3((unsigned)sample_blocks(T, NGCF_SAMPLE_WAVES)), 64 * NGCF_SAMPLE_WAVES, lds, stream>>>(
             seen_rowptr, seen_colidx, col_offset, n_rows, n_items, user_ids, T, case_offset, m, seed, first, out, ld_out, status);
     }
     LAUNCH_CHECK();

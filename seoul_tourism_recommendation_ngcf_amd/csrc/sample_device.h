@@ -1,5 +1,6 @@
-// Device-side building blocks of the unseen-item draw (shared by sample.hip and sample_hard.hip): the recipe of
-// ngcf_sample_unseen in include/ngcf_hip.h, defined once so that every kernel that draws gives the same items.
+// What the samplers share (sample.hip, sample_hard.hip, sample_weighted.hip).  Device side: the building blocks of
+// the unseen-item draw, the recipe of ngcf_sample_unseen in include/ngcf_hip.h, defined once so that every kernel that draws gives
+// the same items.  Host side, at the end: the argument checks the entry points state in the same words, and the cap of their grids.
 #ifndef NGCF_SAMPLE_DEVICE_H
 #define NGCF_SAMPLE_DEVICE_H
 
@@ -101,6 +102,41 @@ __device__ inline int sample_chunk(uint64_t a, int64_t n, int base, int cnt, int
     }
     if (lane < cnt && !in_lanes) R += seen_upto(seen, len, col_offset, R);
     return R;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Host side.  Every entry point checks its own limit of m first, then calls these in the order below, its own checks in between;
+// `entry` is the name its messages carry.  Nothing to do (no cases) is decided by the entry point, before the pointers are looked at.
+// ---------------------------------------------------------------------------------------------
+#define NGCF_SAMPLE_BLOCKS_MAX 2048       // workgroups of a launch: 8 per CU, the most that stay resident; more cases are strided
+
+// the grid of a kernel that gives every wave of its `waves`-wave workgroups one case at a time
+inline int sample_blocks(int64_t cases, int waves) { return (int)std::min<int64_t>((cases + waves - 1) / waves, NGCF_SAMPLE_BLOCKS_MAX); }
+
+inline int sample_check_items(const char *entry, int64_t n_items)
+{
+    if (n_items < 1 || n_items >= (int64_t)1 << 31) return fail(NGCF_ERR_ARG, "%s: n_items=%lld outside [1, 2^31)", entry, (long long)n_items);
+    return NGCF_OK;
+}
+
+// the leading dimension `ld` (named `what`) of an array that takes `width` columns per case
+inline int sample_check_ld(const char *entry, const char *what, int64_t ld, int width)
+{
+    if (ld < width) return fail(NGCF_ERR_ARG, "%s: %s=%lld is below the %d columns of a row", entry, what, (long long)ld, width);
+    return NGCF_OK;
+}
+
+inline int sample_check_counts(const char *entry, int64_t cases, int64_t n_rows)
+{
+    if (cases < 0 || n_rows < 0) return fail(NGCF_ERR_ARG, "%s: bad argument", entry);
+    return NGCF_OK;
+}
+
+inline int sample_check_pointers(const char *entry, std::initializer_list<const void *> required)
+{
+    for (const void *p : required)
+        if (!p) return fail(NGCF_ERR_ARG, "%s: null argument", entry);
+    return NGCF_OK;
 }
 
 }  // namespace

@@ -22,7 +22,6 @@
 // score's bits come back out of the word.
 // ---------------------------------------------------------------------------------------------
 #define NGCF_SAMPLE_HARD_WAVES 4
-#define NGCF_SAMPLE_HARD_BLOCKS_MAX 2048       // workgroups of a launch: 8 per CU, the most that stay resident; more cases are strided
 
 namespace {
 
@@ -110,8 +109,7 @@ extern "C" int ngcf_sample_hard_f32(const int64_t *seen_rowptr, const int32_t *s
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (m < 1 || m > NGCF_SAMPLE_HARD_M_MAX) return fail(NGCF_ERR_ARG, "sample_hard: m=%d outside [1, %d]", m, NGCF_SAMPLE_HARD_M_MAX);
-    if (n_items < 1 || n_items >= (int64_t)1 << 31)
-        return fail(NGCF_ERR_ARG, "sample_hard: n_items=%lld outside [1, 2^31)", (long long)n_items);
+    if (int e = sample_check_items("sample_hard", n_items)) return e;
     if (n_item_rows < n_items)
         return fail(NGCF_ERR_ARG, "sample_hard: %lld item rows for n_items=%lld", (long long)n_item_rows, (long long)n_items);
     if (n_rows < 0 || n_user_rows < n_rows)
@@ -119,14 +117,13 @@ extern "C" int ngcf_sample_hard_f32(const int64_t *seen_rowptr, const int32_t *s
     if (D < 1) return fail(NGCF_ERR_ARG, "sample_hard: D=%d below 1", D);
     if (T < 0 || ldu < D || ldi < D) return fail(NGCF_ERR_ARG, "sample_hard: bad argument");
     if (T == 0) return NGCF_OK;
-    if (!seen_rowptr || !seen_colidx || !users || !items || !user_ids || !neg || !status)
-        return fail(NGCF_ERR_ARG, "sample_hard: null argument");
+    if (int e = sample_check_pointers("sample_hard", {seen_rowptr, seen_colidx, users, items, user_ids, neg, status})) return e;
 
     const int Dp = (D + 3) & ~3;
     const bool ulds = Dp <= NGCF_CAND_LDS_FLOATS;
     const bool vec = aligned16(items) && ldi % 4 == 0;
     const size_t lds = ulds ? (size_t)NGCF_SAMPLE_HARD_WAVES * Dp * sizeof(float) : 0;      // at most 64 KiB
-    const int blocks = (int)std::min<int64_t>((T + NGCF_SAMPLE_HARD_WAVES - 1) / NGCF_SAMPLE_HARD_WAVES, NGCF_SAMPLE_HARD_BLOCKS_MAX);
+    const int blocks = sample_blocks(T, NGCF_SAMPLE_HARD_WAVES);
 #define NGCF_HARD_LAUNCH(VEC_, ULDS_)                                                                                              \
     sample_hard_kernel<VEC_, ULDS_><<<dim3((unsigned)blocks), 64 * NGCF_SAMPLE_HARD_WAVES, lds, stream>>>(                         \
         seen_rowptr, seen_colidx, col_offset, n_rows, n_items, users, ldu, items, ldi, D, user_ids, T, case_offset, m, seed, neg,  \

@@ -19,7 +19,6 @@
 // to 64 entries sits in the lanes as (gap_k, S_k): its search is a ballot.  cdf is read where it lies: 800 KB at 100 K items, L2.
 // ---------------------------------------------------------------------------------------------
 #define NGCF_SAMPLE_WEIGHTED_WAVES 4
-#define NGCF_SAMPLE_WEIGHTED_BLOCKS_MAX 2048     // workgroups of a launch: 8 per CU; more cases are strided
 
 namespace {
 
@@ -212,14 +211,11 @@ extern "C" int ngcf_weighted_prepare(const int64_t *seen_rowptr, const int32_t *
                                      int64_t n_items, const int64_t *cdf, int64_t *gap, int64_t *mass, int32_t *status, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n_items < 1 || n_items >= (int64_t)1 << 31)
-        return fail(NGCF_ERR_ARG, "weighted_prepare: n_items=%lld outside [1, 2^31)", (long long)n_items);
-    if (n_rows < 0) return fail(NGCF_ERR_ARG, "weighted_prepare: bad argument");
+    if (int e = sample_check_items("weighted_prepare", n_items)) return e;
+    if (int e = sample_check_counts("weighted_prepare", n_rows, n_rows)) return e;      // its cases are the rows
     if (n_rows == 0) return NGCF_OK;
-    if (!seen_rowptr || !seen_colidx || !cdf || !gap || !mass || !status) return fail(NGCF_ERR_ARG, "weighted_prepare: null argument");
-    const int blocks = (int)std::min<int64_t>((n_rows + NGCF_SAMPLE_WEIGHTED_WAVES - 1) / NGCF_SAMPLE_WEIGHTED_WAVES,
-                                              NGCF_SAMPLE_WEIGHTED_BLOCKS_MAX);
-    weighted_prepare_kernel<<<dim3((unsigned)blocks), 64 * NGCF_SAMPLE_WEIGHTED_WAVES, 0, stream>>>(
+    if (int e = sample_check_pointers("weighted_prepare", {seen_rowptr, seen_colidx, cdf, gap, mass, status})) return e;
+    weighted_prepare_kernel<<<dim3((unsigned)sample_blocks(n_rows, NGCF_SAMPLE_WEIGHTED_WAVES)), 64 * NGCF_SAMPLE_WEIGHTED_WAVES, 0, stream>>>(
         seen_rowptr, seen_colidx, col_offset, n_rows, n_items, cdf, gap, mass, status);
     LAUNCH_CHECK();
     return NGCF_OK;
@@ -234,24 +230,20 @@ extern "C" int ngcf_sample_weighted(const int64_t *seen_rowptr, const int32_t *s
     hipStream_t stream = (hipStream_t)stream_;
     if (m < 1 || m > NGCF_SAMPLE_WEIGHTED_M_MAX)
         return fail(NGCF_ERR_ARG, "sample_weighted: m=%d outside [1, %d]", m, NGCF_SAMPLE_WEIGHTED_M_MAX);
-    if (n_items < 1 || n_items >= (int64_t)1 << 31)
-        return fail(NGCF_ERR_ARG, "sample_weighted: n_items=%lld outside [1, 2^31)", (long long)n_items);
-    if (ld_out < m) return fail(NGCF_ERR_ARG, "sample_weighted: ld_out=%lld is below the %d columns of a row", (long long)ld_out, m);
-    if (draw_weight && ld_weight < m)
-        return fail(NGCF_ERR_ARG, "sample_weighted: ld_weight=%lld is below the %d columns of a row", (long long)ld_weight, m);
-    if (T < 0 || n_rows < 0) return fail(NGCF_ERR_ARG, "sample_weighted: bad argument");
+    if (int e = sample_check_items("sample_weighted", n_items)) return e;
+    if (int e = sample_check_ld("sample_weighted", "ld_out", ld_out, m)) return e;
+    if (draw_weight)
+        if (int e = sample_check_ld("sample_weighted", "ld_weight", ld_weight, m)) return e;
+    if (int e = sample_check_counts("sample_weighted", T, n_rows)) return e;
     if (T == 0) return NGCF_OK;
-    if (!seen_rowptr || !seen_colidx || !cdf || !gap || !mass || !user_ids || !out || !status)
-        return fail(NGCF_ERR_ARG, "sample_weighted: null argument");
+    if (int e = sample_check_pointers("sample_weighted", {seen_rowptr, seen_colidx, cdf, gap, mass, user_ids, out, status})) return e;
 
     if (m == 1) {
         sample_weighted_one_kernel<<<dim3((unsigned)grid_for(T, 256)), 256, 0, stream>>>(
             seen_rowptr, seen_colidx, col_offset, n_rows, n_items, cdf, gap, mass, user_ids, T, case_offset, seed, out, ld_out,
             draw_weight, ld_weight, case_mass, status);
     } else {
-        const int blocks = (int)std::min<int64_t>((T + NGCF_SAMPLE_WEIGHTED_WAVES - 1) / NGCF_SAMPLE_WEIGHTED_WAVES,
-                                                  NGCF_SAMPLE_WEIGHTED_BLOCKS_MAX);
-        sample_weighted_wave_kernel<<<dim3((unsigned)blocks), 64 * NGCF_SAMPLE_WEIGHTED_WAVES, 0, stream>>>(
+        sample_weighted_wave_kernel<<<dim3((unsigned)sample_blocks(T, NGCF_SAMPLE_WEIGHTED_WAVES)), 64 * NGCF_SAMPLE_WEIGHTED_WAVES, 0, stream>>>(
             seen_rowptr, seen_colidx, col_offset, n_rows, n_items, cdf, gap, mass, user_ids, T, case_offset, m, seed, out, ld_out,
             draw_weight, ld_weight, case_mass, status);
     }

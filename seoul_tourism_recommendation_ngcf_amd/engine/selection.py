@@ -1,5 +1,5 @@
-"""Exact draws on the device: unseen items per case (`ngcf_sample_unseen`: csrc/sample.hip; in the header's section
-"full-catalogue ranking and held-out metrics") and rows per group (`ngcf_select_*`: csrc/select.hip; "exact per-group sampling")."""
+"""Exact draws on the device: rows per group (`ngcf_select_*`: csrc/select.hip; in the header's section "exact per-group sampling").
+The draw of unseen items per case lives with its siblings in `engine.negatives`; its names are re-exported here."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,66 +9,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ._plumbing import _on, _ptr, _require_device, _require_dtype, _require_same_device, _row_major_ld, _status_word, _stream
-from .ranking import ItemSets, _check_sets
-
-# ---- unseen items per case, the reference's TourDataset._negative_sampling (ngcf_sample_unseen, csrc/sample.hip) -------------------
-SAMPLE_M_MAX = 1023
-
-
-def sample_unseen(seen: ItemSets, user_ids: torch.Tensor, m: int, seed: int, *, first: Optional[torch.Tensor] = None,
-                  case_offset: int = 0, out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`m` items per case that the case's user has no entry for in `seen`, uniform and without replacement (ngcf_sample_unseen):
-    case t of user `user_ids[t]` (int64 [T] on the sets' device) is a pure function of (seed, case_offset + t, the user's seen row)
-    - the draw is written out in include/ngcf_hip.h, so a case set drawn in chunks with `case_offset` equals the set drawn at
-    once.  This is the distribution of the reference's `np.random.choice(neg_items, ng_ratio, replace=False)` (utils.py:262), not
-    numpy's stream: the same seed does not give the reference's items.  Returns int64 [T, m], or [T, m + 1] with `first` (int64 [T],
-    e.g. the held-out items) in column 0 - then the `candidates` of `eval_candidates`.  `out`: an int64 row-major tensor of T rows
-    and at least that many columns to write into (the returned tensor is a view of its leading columns).  `seen` comes from
-    `ItemSets.from_pairs` or `ItemSets.from_laplacian`.  A user id outside the sets raises IndexError, a user with fewer than `m`
-    unseen items ValueError (np.random.choice raises there), after one host sync; the drawn slots of such a case are -1.  With a
-    caller's int32 `status` word the bits (1, 2) are only OR-ed into it and the call neither syncs nor raises."""
-    lib = _lib.load()
-    m, seed = int(m), int(seed) & 0xFFFFFFFFFFFFFFFF
-    if m < 1 or m > SAMPLE_M_MAX:
-        raise ValueError(f"sample_unseen: m={m} outside [1, {SAMPLE_M_MAX}]")
-    if seen.n_items < 1 or seen.n_items >= 2 ** 31:
-        raise ValueError(f"sample_unseen: n_items={seen.n_items} outside [1, 2^31)")
-    _require_dtype("sample_unseen", torch.int64, (("user_ids", user_ids), ("first", first), ("out", out)))
-    if user_ids.dim() != 1:
-        raise ValueError(f"sample_unseen: user_ids must be [T], got {tuple(user_ids.shape)}")
-    T = int(user_ids.numel())
-    if first is not None and (first.dim() != 1 or int(first.numel()) != T):
-        raise ValueError(f"sample_unseen: first must be [T = {T}], got {tuple(first.shape)}")
-    width = m + (first is not None)
-    if out is not None and (out.dim() != 2 or int(out.shape[0]) != T or int(out.shape[1]) < width):
-        raise ValueError(f"sample_unseen: out must be [T = {T}, >= {width}], got {tuple(out.shape)}")
-    _require_device(seen.rowptr, "the item sets")
-    dev = seen.rowptr.device
-    _check_sets(seen, dev, 0, "sample_unseen")
-    if seen.rowptr.dtype != torch.int64 or seen.colidx.dtype != torch.int32:
-        raise TypeError("sample_unseen: the item sets must be int64 row pointers and int32 columns")
-    _require_same_device("sample_unseen", (("user_ids", user_ids), ("first", first), ("out", out), ("status", status)),
-                         "the item sets", dev)
-    status, check_status = _status_word("sample_unseen", status, dev)
-    user_ids = user_ids.contiguous()
-    first = None if first is None else first.contiguous()
-    if out is None:
-        out = torch.empty((T, width), dtype=torch.int64, device=dev)
-    ld_out = _row_major_ld(out, "out")
-    # a set without entries has no column array to point at; its row pointers are all 0 and nothing is read through it
-    colidx = seen.colidx if seen.colidx.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
-    with _on(dev):
-        _lib.check(lib.ngcf_sample_unseen(_ptr(seen.rowptr), _ptr(colidx), seen.col_offset, seen.n_rows, seen.n_items, _ptr(user_ids), T,
-                                          int(case_offset), m, seed, _ptr(first), _ptr(out), ld_out, _ptr(status), _stream()))
-    if check_status and T:
-        bits = int(status.item())
-        if bits & 1:
-            raise IndexError(f"sample_unseen: a user id lies outside [0, {seen.n_rows})")
-        if bits & 2:
-            raise ValueError(f"sample_unseen: a user has fewer than m={m} unseen items among {seen.n_items}")
-    return out[:, :width]
-
+from ._plumbing import _on, _ptr, _require_device, _require_same_device, _stream
+from .negatives import SAMPLE_M_MAX, sample_unseen  # noqa: F401
 
 # ---- exact per-group sampling, the core of the reference's Preprocess.split_train_test (ngcf_select_per_group, csrc/select.hip) ------
 SELECT_GROUP, SELECT_QUOTA, SELECT_LOST = 1, 2, 4          # the status bits of include/ngcf_hip.h

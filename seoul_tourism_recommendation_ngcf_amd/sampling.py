@@ -101,7 +101,54 @@ def test_candidates(users: torch.Tensor, items: torch.Tensor, seen: Optional[eng
 test_candidates.__test__ = False          # a public name of the reference's vocabulary, not a test
 
 
-class TripletLoader:
+class _EpochLoader:
+    """What the four loaders share: the columns' validation, the id table `[columns, n]` (int64; its last rows are the items and,
+    with one negative per row, the negatives), `len()`, the epoch counter and the one permutation and gather per `iter()`.  A
+    loader is a constructor and `_draw`, which fills this epoch's negatives: the table's last row, or `self.neg` int64 [n, m] where a
+    row has m of them (None otherwise), which is gathered by the same permutation."""
+
+    def __init__(self, name: str, users: torch.Tensor, columns: Sequence[torch.Tensor], tail: Sequence[torch.Tensor], *, batch_size: int,
+                 shuffle: bool, drop_last: bool, generator: Optional[torch.Generator], m: Optional[int] = None, m_max: int = 0):
+        cols = (list(columns) if len(columns) else [users]) + list(tail)
+        n = int(users.numel())
+        for c in [users] + cols:
+            if c.dim() != 1 or int(c.numel()) != n:
+                raise ValueError(f"{name}: every column must be [n = {n}], got {tuple(c.shape)}")
+            if c.device != users.device:
+                raise RuntimeError(f"{name}: a column is on {c.device}, users on {users.device}")
+        if int(batch_size) < 1:
+            raise ValueError(f"{name}: batch_size={batch_size}")
+        if m is not None and (int(m) < 1 or int(m) > m_max):
+            raise ValueError(f"{name}: m={m} outside [1, {m_max}]")
+        self.table = torch.stack([c.to(torch.int64) for c in cols])            # [columns, n]
+        self.neg: Optional[torch.Tensor] = None
+        self.n, self.batch_size, self.m, self.epoch = n, int(batch_size), m if m is None else int(m), 0
+        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
+
+    def __len__(self) -> int:
+        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
+
+    def _draw(self):
+        """This epoch's negatives (epoch number `self.epoch`), written in place; nothing where they are given."""
+
+    def __iter__(self):
+        self._draw()
+        self.epoch += 1
+        return self._batches()
+
+    def _batches(self):
+        used = len(self) * self.batch_size if self.drop_last else self.n
+        table, neg = self.table, self.neg
+        if self.shuffle:
+            rows = torch.randperm(self.n, generator=self.generator, device=table.device)[:used]
+            table = table[:, rows]                                              # the epoch's one gathered copy
+            neg = None if neg is None else neg[rows]
+        for b0 in range(0, used, self.batch_size):
+            ids = tuple(table[:, b0:b0 + self.batch_size].unbind(0))
+            yield ids if neg is None else ids + (neg[b0:b0 + self.batch_size].reshape(-1),)
+
+
+class TripletLoader(_EpochLoader):
     """A device-side iterator in the shape of the reference's `DataLoader(train_dataset, batch_size, shuffle=True, drop_last=True)`
     (main.py:39-42) over the rows of `train_triplets`.  `columns` are the caller's per-row tensors in the reference's order (year,
     u_id, age, sex, month, day, dow): a batch is `(*columns[b], items[b], neg[b])`, so the loop body of `Experiment.train` runs
@@ -110,36 +157,14 @@ class TripletLoader:
     one int64 copy and yields its batches as views.  `len()` is the number of batches: n // batch_size with `drop_last`.  Plain
     torch: it runs wherever the tensors live."""
 
+
     def __init__(self, users: torch.Tensor, items: torch.Tensor, neg: torch.Tensor, columns: Sequence[torch.Tensor] = (), *,
                  batch_size: int, shuffle: bool = True, drop_last: bool = True, generator: Optional[torch.Generator] = None):
-        cols = list(columns) if len(columns) else [users]
-        cols += [items, neg]
-        n = int(users.numel())
-        for c in cols:
-            if c.dim() != 1 or int(c.numel()) != n:
-                raise ValueError(f"TripletLoader: every column must be [n = {n}], got {tuple(c.shape)}")
-            if c.device != users.device:
-                raise RuntimeError(f"TripletLoader: a column is on {c.device}, users on {users.device}")
-        if int(batch_size) < 1:
-            raise ValueError(f"TripletLoader: batch_size={batch_size}")
-        self.table = torch.stack([c.to(torch.int64) for c in cols])            # [columns, n]
-        self.n, self.batch_size = n, int(batch_size)
-        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
-
-    def __len__(self) -> int:
-        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
-
-    def __iter__(self):
-        used = len(self) * self.batch_size if self.drop_last else self.n
-        table = self.table
-        if self.shuffle:
-            perm = torch.randperm(self.n, generator=self.generator, device=table.device)
-            table = table[:, perm[:used]]                                       # the epoch's one gathered copy
-        for b0 in range(0, used, self.batch_size):
-            yield tuple(table[:, b0:b0 + self.batch_size].unbind(0))
+        super().__init__("TripletLoader", users, columns, (items, neg), batch_size=batch_size, shuffle=shuffle, drop_last=drop_last,
+                         generator=generator)
 
 
-class HardTripletLoader:
+class HardTripletLoader(_EpochLoader):
     """`TripletLoader` whose negatives are redrawn every epoch as hard negatives: the batch shape, `columns`, `shuffle`, `drop_last`
     and `generator` are `TripletLoader`'s, the `neg` column is `hard_triplets(..., m=m, seed=seed, epoch=e)`.  `tables` is a callable
     returning `(user_emb, item_emb)`, e.g. `lambda: (model.all_users_emb, model.all_items_emb)` after a propagation; every `iter()`
@@ -152,46 +177,20 @@ class HardTripletLoader:
     def __init__(self, users: torch.Tensor, items: torch.Tensor, columns: Sequence[torch.Tensor] = (), *, batch_size: int,
                  tables: Callable[[], Tuple[torch.Tensor, torch.Tensor]], m: int = 8, seed: int, shuffle: bool = True,
                  drop_last: bool = True, generator: Optional[torch.Generator] = None):
-        cols = list(columns) if len(columns) else [users]
-        cols += [items]
-        n = int(users.numel())
-        for c in [users] + cols:
-            if c.dim() != 1 or int(c.numel()) != n:
-                raise ValueError(f"HardTripletLoader: every column must be [n = {n}], got {tuple(c.shape)}")
-            if c.device != users.device:
-                raise RuntimeError(f"HardTripletLoader: a column is on {c.device}, users on {users.device}")
-        if int(batch_size) < 1:
-            raise ValueError(f"HardTripletLoader: batch_size={batch_size}")
-        if int(m) < 1 or int(m) > engine.negatives.HARD_M_MAX:
-            raise ValueError(f"HardTripletLoader: m={m} outside [1, {engine.negatives.HARD_M_MAX}]")
+        super().__init__("HardTripletLoader", users, columns, (items, torch.full_like(users, -1, dtype=torch.int64)),
+                         batch_size=batch_size, shuffle=shuffle, drop_last=drop_last, generator=generator, m=m,
+                         m_max=engine.negatives.HARD_M_MAX)
         if not callable(tables):
             raise TypeError("HardTripletLoader: tables must be a callable returning (user_emb, item_emb)")
-        self.table = torch.stack([c.to(torch.int64) for c in cols] + [torch.full_like(users, -1, dtype=torch.int64)])   # [columns, n]
         self.users, self.items = users.to(torch.int64), self.table[-2]
-        self.n, self.batch_size = n, int(batch_size)
-        self.tables, self.m, self.seed, self.epoch = tables, int(m), int(seed), 0
-        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
+        self.tables, self.seed = tables, int(seed)
         self._seen: Optional[engine.ItemSets] = None
 
-    def __len__(self) -> int:
-        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
-
-    def __iter__(self):
+    def _draw(self):
         user_emb, item_emb = self.tables()
         if self._seen is None:
             self._seen = engine.ItemSets.from_pairs(self.users, self.items, int(user_emb.shape[0]), int(item_emb.shape[0]))
         _hard_draw(self.users, user_emb, item_emb, self._seen, self.m, fmix(self.seed + self.epoch), out=self.table[-1])
-        self.epoch += 1
-        return self._batches()
-
-    def _batches(self):
-        used = len(self) * self.batch_size if self.drop_last else self.n
-        table = self.table
-        if self.shuffle:
-            perm = torch.randperm(self.n, generator=self.generator, device=table.device)
-            table = table[:, perm[:used]]                                       # the epoch's one gathered copy
-        for b0 in range(0, used, self.batch_size):
-            yield tuple(table[:, b0:b0 + self.batch_size].unbind(0))
 
 
 def train_negatives(users: torch.Tensor, items: torch.Tensor, seen: Optional[engine.ItemSets] = None, *, m: int, seed: int,
@@ -205,64 +204,33 @@ def train_negatives(users: torch.Tensor, items: torch.Tensor, seen: Optional[eng
     return users, items, engine.sample_unseen(seen, users, int(m), fmix(int(seed) + int(epoch)))
 
 
-class NegativesLoader:
+class NegativesLoader(_EpochLoader):
     """`TripletLoader` with `m` negatives per row, redrawn every epoch: the batch protocol, `columns`, `shuffle`, `drop_last` and
     `generator` are `TripletLoader`'s, and a batch is `(*columns[b], items[b], neg[b].reshape(-1))` - `batch_size` ids per column,
     `batch_size * m` negative ids, the m of a row next to each other - so the loop body of `Experiment.train` runs against it
     unchanged with `criterion = BPRMulti(weight_decay, batch_size, m)`.  Every `iter()` draws all negatives with epoch e = 0, 1, 2, ...
     (`.epoch` is the number of the next one): `neg` = `train_negatives(users, items, seen, m=m, seed=seed, epoch=e, ...)[2]`,
-    written straight into the loader's row table, then one `torch.randperm` and one gather of that table's rows; the batches are
-    views of the gathered copy.  `seen` (default: `ItemSets.from_pairs(users, items, users.max() + 1, items.max() + 1)`, the
+    written straight into the loader's `.neg` [n, m], then one `torch.randperm` by which the id table and `.neg` are gathered once
+    each; the batches are views of the gathered copies - without `shuffle`, of the loader's own arrays, which the next `iter()`
+    overwrites.  `seen` (default: `ItemSets.from_pairs(users, items, users.max() + 1, items.max() + 1)`, the
     positives themselves over the ids that occur, which costs one host sync at construction) says what counts as seen and how
     large the catalogue is: pass sets over the full catalogue when some items have no positive row."""
 
     def __init__(self, users: torch.Tensor, items: torch.Tensor, columns: Sequence[torch.Tensor] = (), *, batch_size: int, m: int,
                  seed: int, shuffle: bool = True, drop_last: bool = True, generator: Optional[torch.Generator] = None,
                  seen: Optional[engine.ItemSets] = None):
-        cols = list(columns) if len(columns) else [users]
-        cols += [items]
-        n = int(users.numel())
-        for c in [users] + cols:
-            if c.dim() != 1 or int(c.numel()) != n:
-                raise ValueError(f"NegativesLoader: every column must be [n = {n}], got {tuple(c.shape)}")
-            if c.device != users.device:
-                raise RuntimeError(f"NegativesLoader: a column is on {c.device}, users on {users.device}")
-        if int(batch_size) < 1:
-            raise ValueError(f"NegativesLoader: batch_size={batch_size}")
-        if int(m) < 1 or int(m) > engine.losses.M_MAX:
-            raise ValueError(f"NegativesLoader: m={m} outside [1, {engine.losses.M_MAX}]")
+        super().__init__("NegativesLoader", users, columns, (items,), batch_size=batch_size, shuffle=shuffle, drop_last=drop_last,
+                         generator=generator, m=m, m_max=engine.losses.M_MAX)
         engine._require_device(users, "users")
-        self.n_columns, self.m = len(cols), int(m)
-        self.table = torch.empty((n, self.n_columns + self.m), dtype=torch.int64, device=users.device)     # [n, columns | negatives]
-        torch.stack([c.to(torch.int64) for c in cols], dim=1, out=self.table[:, :self.n_columns])
+        self.neg = torch.empty((self.n, self.m), dtype=torch.int64, device=users.device)
         self.users = users.to(torch.int64).contiguous()
-        if seen is None and n:
-            seen = engine.ItemSets.from_pairs(self.users, self.table[:, self.n_columns - 1].contiguous(),
-                                              int(self.users.max()) + 1, int(self.table[:, self.n_columns - 1].max()) + 1)
-        self.seen = seen
-        self.n, self.batch_size = n, int(batch_size)
-        self.seed, self.epoch = int(seed), 0
-        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
+        if seen is None and self.n:
+            seen = engine.ItemSets.from_pairs(self.users, self.table[-1], int(self.users.max()) + 1, int(self.table[-1].max()) + 1)
+        self.seen, self.seed = seen, int(seed)
 
-    def __len__(self) -> int:
-        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
-
-    def __iter__(self):
+    def _draw(self):
         if self.n:
-            engine.sample_unseen(self.seen, self.users, self.m, fmix(self.seed + self.epoch), out=self.table[:, self.n_columns:])
-        self.epoch += 1
-        return self._batches()
-
-    def _batches(self):
-        used = len(self) * self.batch_size if self.drop_last else self.n
-        rows = self.table[:used]
-        if self.shuffle:
-            perm = torch.randperm(self.n, generator=self.generator, device=rows.device)
-            rows = self.table[perm[:used]]                                      # the epoch's one gathered copy
-        cols = rows[:, :self.n_columns].t().contiguous()                        # [columns, used]: a batch's ids are contiguous views
-        neg = rows[:, self.n_columns:].contiguous()                             # [used, m]
-        for b0 in range(0, used, self.batch_size):
-            yield tuple(cols[:, b0:b0 + self.batch_size].unbind(0)) + (neg[b0:b0 + self.batch_size].reshape(-1),)
+            engine.sample_unseen(self.seen, self.users, self.m, fmix(self.seed + self.epoch), out=self.neg)
 
 
 # ---- popularity-weighted negatives (engine.negatives.weighted_unseen) ----------------------------------------------------------------
@@ -337,53 +305,29 @@ def weighted_triplets(users: torch.Tensor, items: torch.Tensor, weights, seen: O
     return got[:2] + tuple(t[:, 0] for t in got[2:])
 
 
-class WeightedNegativesLoader:
+class WeightedNegativesLoader(_EpochLoader):
     """`NegativesLoader` with popularity-weighted negatives: the batch protocol, `columns`, `shuffle`, `drop_last` and `generator`
     are `TripletLoader`'s, a batch is `(*columns[b], items[b], neg[b].reshape(-1))`, and every `iter()` redraws all negatives with
     epoch e = 0, 1, 2, ... (`.epoch` is the number of the next one): `neg` = `weighted_negatives(users, items, weights, seen, m=m,
-    seed=seed, epoch=e, ...)[2]`, written straight into the loader's row table.  `weights`: int64, one per item of `seen`
+    seed=seed, epoch=e, ...)[2]`, written straight into the loader's `.neg` [n, m].  `weights`: int64, one per item of `seen`
     (default: `ItemSets.from_pairs` over the positives and `weights.numel()` items), prepared once at construction
     (`.wsets`, an `engine.negatives.WeightedSets`)."""
 
     def __init__(self, users: torch.Tensor, items: torch.Tensor, weights: torch.Tensor, columns: Sequence[torch.Tensor] = (), *,
                  batch_size: int, m: int, seed: int, shuffle: bool = True, drop_last: bool = True,
                  generator: Optional[torch.Generator] = None, seen: Optional[engine.ItemSets] = None):
-        cols = list(columns) if len(columns) else [users]
-        cols += [items]
-        n = int(users.numel())
-        for c in [users] + cols:
-            if c.dim() != 1 or int(c.numel()) != n:
-                raise ValueError(f"WeightedNegativesLoader: every column must be [n = {n}], got {tuple(c.shape)}")
-            if c.device != users.device:
-                raise RuntimeError(f"WeightedNegativesLoader: a column is on {c.device}, users on {users.device}")
-        if int(batch_size) < 1:
-            raise ValueError(f"WeightedNegativesLoader: batch_size={batch_size}")
-        if int(m) < 1 or int(m) > engine.negatives.WEIGHTED_M_MAX:
-            raise ValueError(f"WeightedNegativesLoader: m={m} outside [1, {engine.negatives.WEIGHTED_M_MAX}]")
+        super().__init__("WeightedNegativesLoader", users, columns, (items,), batch_size=batch_size, shuffle=shuffle,
+                         drop_last=drop_last, generator=generator, m=m, m_max=engine.negatives.WEIGHTED_M_MAX)
         if weights.dtype != torch.int64 or weights.dim() != 1:
             raise TypeError(f"WeightedNegativesLoader: weights must be an int64 [n_item] tensor, got {weights.dtype} {tuple(weights.shape)}")
         engine._require_device(users, "users")
-        self.n_columns, self.m = len(cols), int(m)
-        self.table = torch.empty((n, self.n_columns + self.m), dtype=torch.int64, device=users.device)     # [n, columns | negatives]
-        torch.stack([c.to(torch.int64) for c in cols], dim=1, out=self.table[:, :self.n_columns])
+        self.neg = torch.empty((self.n, self.m), dtype=torch.int64, device=users.device)
         self.users = users.to(torch.int64).contiguous()
         if seen is None:
-            n_user = int(self.users.max()) + 1 if n else 1
-            seen = engine.ItemSets.from_pairs(self.users, self.table[:, self.n_columns - 1].contiguous(), n_user, int(weights.numel()))
-        self.seen = seen
+            seen = engine.ItemSets.from_pairs(self.users, self.table[-1], int(self.users.max()) + 1 if self.n else 1, int(weights.numel()))
+        self.seen, self.seed = seen, int(seed)
         self.wsets = engine.negatives.WeightedSets(seen, weights)
-        self.n, self.batch_size = n, int(batch_size)
-        self.seed, self.epoch = int(seed), 0
-        self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
 
-    def __len__(self) -> int:
-        return self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
-
-    def __iter__(self):
+    def _draw(self):
         if self.n:
-            engine.negatives.weighted_unseen(self.wsets, self.users, self.m, fmix(self.seed + self.epoch),
-                                             out=self.table[:, self.n_columns:])
-        self.epoch += 1
-        return self._batches()
-
-    _batches = NegativesLoader._batches
+            engine.negatives.weighted_unseen(self.wsets, self.users, self.m, fmix(self.seed + self.epoch), out=self.neg)

@@ -152,7 +152,7 @@ def test_user_row_at_the_lds_budget(where):
 
 def test_grid_stride():
     """Five cases more than one pass of the capped grid takes (cap and waves per workgroup read from the source)."""
-    per_pass = _source_constant("NGCF_SAMPLE_HARD_BLOCKS_MAX", "sample_hard.hip") * _source_constant("NGCF_SAMPLE_HARD_WAVES", "sample_hard.hip")
+    per_pass = _source_constant("NGCF_SAMPLE_BLOCKS_MAX", "sample_device.h") * _source_constant("NGCF_SAMPLE_HARD_WAVES", "sample_hard.hip")
     T = per_pass + 5
     U, I, _, _ = _tables(4)
     uid = torch.randint(0, 7, (T,), generator=torch.Generator().manual_seed(5)).to(DEV)       # users 0..6: at least 2 unseen items

@@ -169,7 +169,7 @@ def test_chunks_equal_the_whole_and_runs_repeat(m):
 
 def test_grid_stride_of_the_wave_kernel():
     """Five cases more than one pass of the capped grid takes (cap and waves per workgroup read from the source)."""
-    per_pass = _source_constant("NGCF_SAMPLE_WEIGHTED_BLOCKS_MAX", "sample_weighted.hip") * _source_constant(
+    per_pass = _source_constant("NGCF_SAMPLE_BLOCKS_MAX", "sample_device.h") * _source_constant(
         "NGCF_SAMPLE_WEIGHTED_WAVES", "sample_weighted.hip")
     uid = torch.randint(0, 7, (per_pass + 5,), generator=torch.Generator().manual_seed(5))        # users 0..6: at least 24 unseen items
     check(_wsets("zipf"), _weights("zipf"), _seen_rows(), uid, 2)
@@ -337,3 +337,36 @@ def test_weighted_negatives_loader():
         served = torch.cat((su[:, None], si[:, None], sn), 1)
         assert {tuple(r) for r in served.tolist()} <= {tuple(r) for r in table.tolist()}
         assert len({tuple(r) for r in served.tolist()}) > 1400
+
+
+@pytest.mark.parametrize("name", ("NegativesLoader", "WeightedNegativesLoader"))
+def test_loader_batches_are_the_epochs_draw_at_the_generators_permutation(name):
+    """Both loaders with m negatives per row: an unshuffled epoch is the module function's draw of that epoch number, row for row,
+    and a shuffled one is that draw at the rows `torch.randperm` gives from an equally seeded device generator."""
+    from seoul_tourism_recommendation_ngcf_amd import engine, sampling
+    users, items = _positives()
+    m, bs = 4, 512
+    used = N_POS // bs * bs
+    seen = engine.ItemSets.from_pairs(users, items, N_USER, N_ITEM)
+    kw = dict(m=m, seed=99)
+    if name == "NegativesLoader":
+        make = lambda **options: sampling.NegativesLoader(users, items, batch_size=bs, seen=seen, **kw, **options)  # noqa: E731
+        draw = lambda e: sampling.train_negatives(users, items, seen, epoch=e, n_user=N_USER, n_item=N_ITEM, **kw)[2]  # noqa: E731
+    else:
+        weights = sampling.popularity_weights(items, N_ITEM)
+        make = lambda **options: sampling.WeightedNegativesLoader(users, items, weights, batch_size=bs, seen=seen, **kw, **options)  # noqa: E731
+        draw = lambda e: sampling.weighted_negatives(users, items, weights, seen, epoch=e, n_user=N_USER, n_item=N_ITEM, **kw)[2]  # noqa: E731
+    ordered = make(shuffle=False, drop_last=False)
+    shuffled = make(generator=torch.Generator(device=DEV).manual_seed(4))
+    again = torch.Generator(device=DEV).manual_seed(4)
+    for e in range(2):
+        want = draw(e)
+        got = list(ordered)
+        assert ordered.epoch == e + 1 and [int(b[0].numel()) for b in got] == [bs] * (N_POS // bs) + [N_POS - used]
+        assert torch.equal(torch.cat([b[0] for b in got]), users) and torch.equal(torch.cat([b[1] for b in got]), items)
+        assert torch.equal(torch.cat([b[2] for b in got]).view(N_POS, m), want)
+        rows = torch.randperm(N_POS, generator=again, device=DEV)[:used]
+        got = list(shuffled)
+        assert len(got) == used // bs
+        assert torch.equal(torch.cat([b[0] for b in got]), users[rows]) and torch.equal(torch.cat([b[1] for b in got]), items[rows])
+        assert torch.equal(torch.cat([b[2] for b in got]).view(used, m), want[rows])
