@@ -342,6 +342,53 @@ int ngcf_bpr_multi_backward_f32(const float *u, int64_t Bu, const float *p, int6
                                 int reduction, float weight_decay, float batch_size, const float *grad_out, float *du,
                                 float *dp, float *dn, void *stream);
 
+/* ---- Sampled softmax with logQ correction (csrc/sampled_softmax.hip) --------------------------- */
+/*
+ * The softmax of a positive among its m sampled negatives, every score corrected by the log of the probability with which its item
+ * was proposed, at a temperature.  Operands as in ngcf_bpr_multi_f32: u: [B, D], p: [B, D], n: [B*m, D], fp32 and contiguous, rows
+ * b*m .. b*m + m - 1 of n the negatives of row b; logq: fp32 [B*m], logq[b*m + j - 1] belongs to negative j = 1..m of row b;
+ * pos_logq: fp32 [B] or NULL (then c_b is exactly 0).  Nothing broadcasts: Bu == Bp == B >= 1, Bn == B*m,
+ * 1 <= m <= NGCF_SAMPLED_SOFTMAX_M_MAX, D >= 1, inv_tau > 0 and finite; anything else is NGCF_ERR_ARG before any launch.  Scores
+ * are plain (no abs, as in the full-catalogue softmax below).  logq and pos_logq are data: they get no gradient, and non-finite
+ * values in them are undefined and not checked.
+ *   z_0 = (u_b.p_b) * inv_tau - c_b          z_j = (u_b.n_bj) * inv_tau - logq[b*m + j - 1]
+ *   l_b = logsumexp(z_0, .., z_m) - z_0
+ *   loss = (sum_b l_b + wd*(sum|u|^2 + sum|p|^2 + (1/m) sum|n|^2)) / batch_size            (regulariser and divisor: ngcf_bpr_multi_f32's)
+ * The recipe, operation by operation where it decides bits (fp32, no contraction but the fmaf named):
+ *   dots     u.p, u.n_j, |u|^2, |p|^2, |n_j|^2 are those of ngcf_bpr_multi_f32: fmaf over a lane's columns (stride 64, ascending),
+ *            then the xor butterfly 32, 16, .., 1 over the wave; sum_j |n_j|^2 with j ascending.
+ *   z        one multiply and one subtract each, rounded twice (no fma).
+ *   forward  M = max_{j>=1} z_j;  lse = M + logf(sum_{j>=1} expf(z_j - M))  (butterfly sums; over the negatives only);
+ *            l_b = -logsigmoid(z_0 - lse),  logsigmoid(x) = fminf(x, 0) - log1pf(expf(-|x|)).  Four rows make a workgroup partial
+ *            (r0 + r1) + (r2 + r3), the second stage is the BPR losses' (thread t adds the partials t, t + 256, ..).
+ *   backward M' = max(z_0, M);  den = expf(z_0 - M') + sum_{j>=1} expf(z_j - M');  s_j = -(expf(z_j - M') / den) * inv_tau;
+ *            S = sum_j s_j (butterfly);  with g = *grad_out / batch_size:
+ *            dp_b  = g * fmaf(S, u_b, 2 wd p_b)
+ *            dn_bj = g * fmaf(-s_j, u_b, (2 wd / m) n_bj)
+ *            du_b  = g * ((c0 + c1) + (c2 + c3)): chain q takes the negatives j = q mod 4 in ascending order, one
+ *                    fmaf(s_j, p_b - n_bj, chain) each, chain 0 starts from 2 wd u_b (the four chains of ngcf_bpr_multi_backward_f32).
+ *            That is dl_b/d(u.n_j) = a_j inv_tau and dl_b/d(u.p) = -A inv_tau with a_j = exp(z_j) / sum_{k>=0} exp(z_k), A = sum_j a_j.
+ *            The scores are recomputed; nothing of the forward is kept.
+ * The identity that fixes the recipe: with inv_tau = 1, logq all zero, pos_logq NULL and inputs whose dot products are all positive,
+ * the loss and the three gradients are those of ngcf_bpr_multi_f32 / ngcf_bpr_multi_backward_f32 under NGCF_BPR_MULTI_SOFTMAX bit
+ * for bit (x * 1 - 0 is x, and the sign factors there are exactly 1).
+ * What logq is: the LOG OF THE PROPOSAL PROBABILITY OF THE SLOT AS THE SAMPLER DREW IT - for ngcf_sample_weighted's successive
+ * sampling the conditional probability log(w_j / U_j) given the slots before it, not the marginal probability that the item is
+ * among the m.  No unbiasedness of the resulting estimator of the full softmax is claimed.  Adding one constant to a row's logq and
+ * pos_logq changes nothing mathematically.
+ * One wave per positive row, four per workgroup; lane j keeps z_j, its logq value (loaded once, coalesced across the wave) and s_j,
+ * hence m <= 64.  No atomics and no host synchronisation: results are identical from run to run and both calls can be captured.
+ * `loss` is one device float; workspace: ngcf_sampled_softmax_workspace_bytes(B) bytes (NGCF_ERR_WORKSPACE when shorter; -1 for B < 0).
+ */
+#define NGCF_SAMPLED_SOFTMAX_M_MAX 64
+int64_t ngcf_sampled_softmax_workspace_bytes(int64_t B);
+int ngcf_sampled_softmax_f32(const float *u, int64_t Bu, const float *p, int64_t Bp, const float *n, int64_t Bn, int m, int D,
+                             const float *logq, const float *pos_logq, float inv_tau, float weight_decay, float batch_size,
+                             float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int ngcf_sampled_softmax_backward_f32(const float *u, int64_t Bu, const float *p, int64_t Bp, const float *n, int64_t Bn, int m,
+                                      int D, const float *logq, const float *pos_logq, float inv_tau, float weight_decay,
+                                      float batch_size, const float *grad_out, float *du, float *dp, float *dn, void *stream);
+
 /* ---- Full-catalogue softmax (csrc/softmax_full.hip) ------------------------------------------- */
 /*
  * The softmax loss over the whole catalogue, the limit of the sampled losses above, without a [B, n_items] matrix in memory:

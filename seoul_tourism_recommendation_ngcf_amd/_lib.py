@@ -75,6 +75,11 @@ PROTOTYPES = {
     "ngcf_bpr_multi_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_int, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _i64, _vp]),
     "ngcf_bpr_multi_backward_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_int, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _vp, _vp,
                                               _vp]),
+    "ngcf_sampled_softmax_workspace_bytes": (_i64, [_i64]),
+    "ngcf_sampled_softmax_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _i64,
+                                           _vp]),
+    "ngcf_sampled_softmax_backward_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _f32, _f32, _f32, _vp, _vp,
+                                                    _vp, _vp, _vp]),
     "ngcf_softmax_full_plan": (C.c_int, [_i64, _i64, C.c_int, C.POINTER(_i64)]),
     "ngcf_softmax_full_workspace_bytes": (_i64, [_i64, _i64, C.c_int]),
     "ngcf_softmax_full_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i64,

@@ -1,7 +1,7 @@
 """Forward drivers of the propagation engine and the autograd seam for training.
 
 `propagate_forward` issues the HIP layer kernels for NGCF.py:120-147 (inference path, nothing saved).
-`Propagate` / `GatherTriple` / `BPRLoss` / `BPRMultiLoss` / `SoftmaxFullLoss` are `torch.autograd.Function`s so that `loss.backward()`
+`Propagate` / `GatherTriple` / `BPRLoss` / `BPRMultiLoss` / `SampledSoftmaxLoss` / `SoftmaxFullLoss` are `torch.autograd.Function`s so that `loss.backward()`
 (experiment.py:57) reaches every parameter: their backward runs the HIP kernels of the "backward pass" section
 of include/ngcf_hip.h - weight and input gradients on the fp32 matrix cores, `L^T . dLE` on the SpMM kernels; no library
 GEMM at any width.
@@ -506,6 +506,28 @@ class BPRMultiLoss(torch.autograd.Function):
         u, p, n = ctx.saved_tensors
         du, dp, dn = _eng.losses.bpr_multi_backward(u, p, n, ctx.m, ctx.wd, ctx.bs, g.to(torch.float32).contiguous(), ctx.reduction)
         return du, dp, dn, None, None, None, None, None
+
+
+class SampledSoftmaxLoss(torch.autograd.Function):
+    """The sampled softmax with logQ correction (engine.losses) with its gradient kernel; `logq` and `pos_logq` are data."""
+
+    @staticmethod
+    def forward(ctx, u, p, n, logq, pos_logq, m, inv_tau, weight_decay, batch_size, ws):
+        u, p, n = u.contiguous(), p.contiguous(), n.contiguous()
+        ctx.m, ctx.inv_tau, ctx.wd, ctx.bs = int(m), float(inv_tau), float(weight_decay), float(batch_size)
+        # a float64 correction is cast here, once for both directions (any other type is left to the wrapper's refusal)
+        logq, pos_logq = (t.to(torch.float32) if t is not None and t.dtype == torch.float64 else t for t in (logq, pos_logq))
+        ctx.has_pos = pos_logq is not None
+        ctx.save_for_backward(u, p, n, logq, *((pos_logq,) if ctx.has_pos else ()))
+        return _eng.losses.sampled_softmax_loss(u, p, n, logq, m, inv_tau, weight_decay, batch_size, ws, pos_logq)
+
+    @staticmethod
+    def backward(ctx, g):
+        u, p, n, logq = ctx.saved_tensors[:4]
+        pos_logq = ctx.saved_tensors[4] if ctx.has_pos else None
+        du, dp, dn = _eng.losses.sampled_softmax_backward(u, p, n, logq, ctx.m, ctx.inv_tau, ctx.wd, ctx.bs,
+                                                          g.to(torch.float32).contiguous(), pos_logq)
+        return du, dp, dn, None, None, None, None, None, None, None
 
 
 class SoftmaxFullLoss(torch.autograd.Function):

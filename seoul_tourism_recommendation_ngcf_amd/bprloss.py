@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import engine as _eng
-from .autograd import BPRLoss, BPRMultiLoss, SoftmaxFullLoss
+from .autograd import BPRLoss, BPRMultiLoss, SampledSoftmaxLoss, SoftmaxFullLoss
 
 
 class BPR(nn.Module):
@@ -54,6 +54,43 @@ class BPRMulti(nn.Module):
             return BPRMultiLoss.apply(u_idx, pos_idx, neg_idx, self.m, self.weight_decay, self.batch_size, self._ws, self.reduction)
         return _eng.losses.bpr_multi_loss(u_idx.detach().contiguous(), pos_idx.detach().contiguous(), neg_idx.detach().contiguous(),
                                           self.m, self.weight_decay, self.batch_size, self._ws, self.reduction)
+
+
+class SampledSoftmax(nn.Module):
+    """The sampled softmax loss with the logQ correction, on the fused HIP kernels of `engine.losses`: the consumer of the `logq`
+    that `sampling.weighted_negatives(..., return_logq=True)` and `sampling.LogQNegativesLoader` deliver.
+    `forward(u, pos, neg, logq, pos_logq=None)` -> 0-dim tensor with `u`, `pos` [B, D] and `neg` [B*m, D] as `BPRMulti` takes them
+    (what `model(..., neg_item=neg.reshape(-1))` returns), `logq` [B, m] or [B*m] and `pos_logq` [B] (float32 or float64).  With
+    plain scores (no `abs`, as in `SoftmaxFull`) z_0 = <u_b, p_b> / temperature - pos_logq[b] and
+    z_j = <u_b, n_bj> / temperature - logq[b, j - 1], a row gives logsumexp(z_0 .. z_m) - z_0: a popular item, proposed often,
+    has its score lowered by the log of how often.  The regulariser and the divisor are `BPRMulti`'s: weight_decay (|u|^2 + |p|^2
+    + |n|^2 / m) and the constructor's `batch_size`.
+
+    `logq` is the log proposal probability of every slot AS ITS SAMPLER DREW IT: for the successive sampling of
+    `weighted_negatives` the conditional log(w_j / U_j) given the slots before, not the marginal probability that the item is among
+    the m.  No unbiasedness of the estimator of `SoftmaxFull` is claimed.  The corrections carry no gradient; non-finite values
+    in them are undefined."""
+
+    def __init__(self, weight_decay, batch_size, m, temperature=1.0):
+        super().__init__()
+        if int(m) != m or m < 1 or m > _eng.losses.M_MAX:
+            raise ValueError(f"SampledSoftmax: m={m} outside [1, {_eng.losses.M_MAX}]")
+        t = float(temperature)
+        if not (t > 0 and t < float("inf")):
+            raise ValueError(f"SampledSoftmax: temperature={temperature} is not a positive finite number")
+        self.weight_decay = weight_decay
+        self.batch_size = batch_size
+        self.m = int(m)
+        self.temperature = t
+        self._ws = _eng.Workspace()
+
+    def forward(self, u_idx, pos_idx, neg_idx, logq, pos_logq=None):
+        inv_tau = 1.0 / self.temperature
+        if torch.is_grad_enabled() and (u_idx.requires_grad or pos_idx.requires_grad or neg_idx.requires_grad):
+            return SampledSoftmaxLoss.apply(u_idx, pos_idx, neg_idx, logq, pos_logq, self.m, inv_tau, self.weight_decay, self.batch_size,
+                                            self._ws)
+        return _eng.losses.sampled_softmax_loss(u_idx.detach().contiguous(), pos_idx.detach().contiguous(), neg_idx.detach().contiguous(),
+                                                logq, self.m, inv_tau, self.weight_decay, self.batch_size, self._ws, pos_logq)
 
 
 class SoftmaxFull(nn.Module):

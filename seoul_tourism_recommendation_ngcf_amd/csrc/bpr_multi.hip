@@ -15,115 +15,13 @@
 
 #pragma clang fp contract(off)
 
+#include "loss_rows_device.h"          // URow, RowBatch, score_row, wave_max, lane_value, LOSS_ROWS_DISPATCH
+
 namespace {
 
 constexpr int kMeanReduction = 0, kSoftmaxReduction = 1;
 
-__device__ inline float wave_max(float x)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x = fmaxf(x, __shfl_xor(x, m));
-    return x;
-}
-
-// lane `j` (wave-uniform) of x
-__device__ inline float lane_value(float x, int j)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
-}
-
 __device__ inline float sign_of(float t) { return t > 0.f ? 1.f : (t < 0.f ? -1.f : 0.f); }      // d|t|/dt, 0 at 0 like torch.abs
-
-// The u row of a wave: KU registers per lane, column lane + 64 k in register k; KU = 0 reads the row from memory every time
-// (D > 2048: the row is a cache hit after its first use).
-template <int KU>
-struct URow {
-    float v[KU > 0 ? KU : 1];
-    const float *row;
-    int D, lane;
-
-    __device__ URow(const float *__restrict__ ur, int D_, int lane_) : row(ur), D(D_), lane(lane_)
-    {
-        if (KU > 0) {
-#pragma unroll
-            for (int k = 0; k < KU; ++k) {
-                const int j = lane + 64 * k;
-                v[k] = j < D ? ur[j] : 0.f;
-            }
-        }
-    }
-
-    // f(column, u value) for the lane's columns in ascending order
-    template <class F>
-    __device__ __forceinline__ void for_columns(F &&f) const
-    {
-        if (KU > 0) {
-#pragma unroll
-            for (int k = 0; k < KU; ++k) {
-                const int j = lane + 64 * k;
-                if (j < D) f(j, v[k]);
-            }
-        } else {
-            for (int j = lane; j < D; j += 64) f(j, row[j]);
-        }
-    }
-};
-
-// What a wave knows of its row after the score pass.  Wave-uniform: up = u.p, the squared norms uu, pp and nn = sum_j |n_j|^2
-// (j ascending).  Per lane j < m: un = u.n_j (0 in the lanes from m on).
-struct Scores {
-    float up, uu, pp, nn, un;
-};
-
-// rows per batch of the score pass: R x KU loads in flight per lane
-template <int KU>
-struct RowBatch {
-    static constexpr int R = KU == 0 ? 2 : (KU <= 8 ? 4 : (KU <= 16 ? 2 : 1));
-};
-
-template <int KU>
-__device__ __forceinline__ Scores score_row(const URow<KU> &u, const float *__restrict__ pr, const float *__restrict__ nr, int m, int D,
-                                            int lane)
-{
-    Scores s;
-    float up = 0.f, uu = 0.f, pp = 0.f;
-    u.for_columns([&](int j, float a) {
-        const float b = pr[j];
-        up = fmaf(a, b, up);
-        uu = fmaf(a, a, uu);
-        pp = fmaf(b, b, pp);
-    });
-    s.up = wave_sum(up);
-    s.uu = wave_sum(uu);
-    s.pp = wave_sum(pp);
-    s.nn = 0.f;
-    s.un = 0.f;
-    constexpr int R = RowBatch<KU>::R;
-    for (int j0 = 0; j0 < m; j0 += R) {
-        float un[R], nn[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {       // a batch's rows past m read row m - 1 again (no branch between the rows' loads) and are dropped below
-            const float *nj = nr + (int64_t)min(j0 + r, m - 1) * D;
-            float d = 0.f, q = 0.f;
-            u.for_columns([&](int j, float a) {
-                const float c = nj[j];
-                d = fmaf(a, c, d);
-                q = fmaf(c, c, q);
-            });
-            un[r] = d;
-            nn[r] = q;
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float d = wave_sum(un[r]), q = wave_sum(nn[r]);
-            if (j0 + r < m) {
-                if (lane == j0 + r) s.un = d;
-                s.nn += q;
-            }
-        }
-    }
-    return s;
-}
 
 // l_b of the row from the lanes' scores
 __device__ __forceinline__ float row_loss(const Scores &s, int m, float inv_m, int reduction, int lane)
@@ -289,14 +187,6 @@ int launch_backward(const float *u, const float *p, const float *n, int64_t B, i
     return NGCF_OK;
 }
 
-// the u row's registers per lane for a width: the next power of two of ceil(D / 64) up to 32, 0 (memory) beyond
-int registers_for(int D)
-{
-    for (int ku = 1; ku <= 32; ku *= 2)
-        if (D <= 64 * ku) return ku;
-    return 0;
-}
-
 int check_shapes(const char *what, int64_t Bu, int64_t Bp, int64_t Bn, int m, int D, int reduction)
 {
     if (D <= 0) return fail(NGCF_ERR_ARG, "%s: D=%d", what, D);
@@ -311,17 +201,6 @@ int check_shapes(const char *what, int64_t Bu, int64_t Bp, int64_t Bn, int m, in
 
 }  // namespace
 
-#define BPR_MULTI_DISPATCH(fn, ...)                          \
-    switch (registers_for(D)) {                              \
-    case 1: return fn<1>(__VA_ARGS__);                       \
-    case 2: return fn<2>(__VA_ARGS__);                       \
-    case 4: return fn<4>(__VA_ARGS__);                       \
-    case 8: return fn<8>(__VA_ARGS__);                       \
-    case 16: return fn<16>(__VA_ARGS__);                     \
-    case 32: return fn<32>(__VA_ARGS__);                     \
-    default: return fn<0>(__VA_ARGS__);                      \
-    }
-
 extern "C" int64_t ngcf_bpr_multi_workspace_bytes(int64_t B)
 {
     if (B < 0) return -1;
@@ -331,13 +210,13 @@ extern "C" int64_t ngcf_bpr_multi_workspace_bytes(int64_t B)
 static int forward_kernel(const float *u, const float *p, const float *n, int64_t B, int m, int D, int reduction, float *part,
                           hipStream_t stream)
 {
-    BPR_MULTI_DISPATCH(launch_forward, u, p, n, B, m, D, reduction, part, stream)
+    LOSS_ROWS_DISPATCH(launch_forward, u, p, n, B, m, D, reduction, part, stream)
 }
 
 static int backward_kernel(const float *u, const float *p, const float *n, int64_t B, int m, int D, int reduction, float wd,
                            float batch_size, const float *gout, float *du, float *dp, float *dn, hipStream_t stream)
 {
-    BPR_MULTI_DISPATCH(launch_backward, u, p, n, B, m, D, reduction, wd, batch_size, gout, du, dp, dn, stream)
+    LOSS_ROWS_DISPATCH(launch_backward, u, p, n, B, m, D, reduction, wd, batch_size, gout, du, dp, dn, stream)
 }
 
 extern "C" int ngcf_bpr_multi_f32(const float *u, int64_t Bu, const float *p, int64_t Bp, const float *n, int64_t Bn, int m, int D,

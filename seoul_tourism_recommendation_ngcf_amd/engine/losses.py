@@ -1,6 +1,7 @@
 """BPR against `m` negatives per positive row (`ngcf_bpr_multi_f32` / `ngcf_bpr_multi_backward_f32`: csrc/bpr_multi.hip; in the
 header next to the BPR section): the loss of `[B, D]` users and positives and `[B*m, D]` negatives without expanding the batch to
-`B*m` triplets, and its three gradients; and the limit of that series, the softmax over the WHOLE catalogue (`ngcf_softmax_full_f32`
+`B*m` triplets, and its three gradients; the sampled softmax over the same operands with the logQ correction and a temperature
+(`ngcf_sampled_softmax_f32` / `ngcf_sampled_softmax_backward_f32`: csrc/sampled_softmax.hip); and the limit of that series, the softmax over the WHOLE catalogue (`ngcf_softmax_full_f32`
 / `ngcf_softmax_full_backward_f32`: csrc/softmax_full.hip), whose [B, n_items] score matrix is never in memory.  Like the wrappers
 of `layers`, no check here costs a host sync."""
 from __future__ import annotations
@@ -70,6 +71,68 @@ def bpr_multi_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int
     with _on(u.device):
         _lib.check(lib.ngcf_bpr_multi_backward_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, red, float(weight_decay),
                                                    float(batch_size), _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
+    return du, dp, dn
+
+
+# ---- the sampled softmax with logQ correction (`ngcf_sampled_softmax_f32` / `ngcf_sampled_softmax_backward_f32`: csrc/sampled_softmax.hip)
+def _corrections(fn: str, u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, logq: torch.Tensor, pos_logq: Optional[torch.Tensor],
+                 m: int, inv_tau: float) -> Tuple[int, int, torch.Tensor, Optional[torch.Tensor]]:
+    """The refusals of both sampled-softmax calls, before anything reaches the device, in the order of `_operands`, whose own come
+    last because they end with the device: sizes (ValueError), types (TypeError), the temperature, the operands, the devices
+    (RuntimeError).  -> (B, D, logq, pos_logq), the two corrections as contiguous float32 (a float64 one is cast once, here)."""
+    if u.dim() == 2 and int(m) == m and m >= 1:                                 # (anything else: `_operands` below says so)
+        rows = int(u.shape[0])
+        if tuple(logq.shape) not in ((rows, int(m)), (rows * int(m),)):
+            raise ValueError(f"{fn}: logq must be [B, m] or [B*m] with B={rows}, m={m}, got shape {tuple(logq.shape)}")
+        if pos_logq is not None and tuple(pos_logq.shape) != (rows,):
+            raise ValueError(f"{fn}: pos_logq must be [B] with B={rows}, got shape {tuple(pos_logq.shape)}")
+    for nm, t in (("logq", logq), ("pos_logq", pos_logq)):
+        if t is not None and t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{fn}: {nm} must be float32 or float64, got {t.dtype}")
+    if not (inv_tau > 0 and inv_tau < float("inf")):
+        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+    B, D, _ = _operands(fn, u, p, n, m, "softmax")
+    _require_same_device(fn, (("logq", logq), ("pos_logq", pos_logq)), "u", u.device)
+    logq = logq.to(torch.float32).reshape(-1).contiguous()
+    return B, D, logq, None if pos_logq is None else pos_logq.to(torch.float32).contiguous()
+
+
+def sampled_softmax_loss(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, logq: torch.Tensor, m: int, inv_tau: float,
+                         weight_decay: float, batch_size: float, ws: Workspace, pos_logq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sampled softmax loss with the logQ correction of `u` [B, D], `p` [B, D] and `n` [B*m, D] (rows b*m .. b*m + m - 1: the
+    negatives of row b; float32 and contiguous, as `bpr_multi_loss` takes them), as a 0-dim device tensor.  `logq` ([B, m] or [B*m],
+    float32 or float64) holds the log proposal probability of every negative as its sampler drew it - for
+    `sampling.weighted_negatives(..., return_logq=True)` the conditional log(w_j / U_j) of successive sampling, not a marginal
+    inclusion probability - and `pos_logq` [B] the positives' correction (None: exactly 0).  With plain scores (no `abs`),
+    z_0 = (u_b.p_b) inv_tau - pos_logq[b] and z_j = (u_b.n_bj) inv_tau - logq[b, j - 1], a row gives logsumexp(z_0 .. z_m) - z_0;
+    the loss is (sum of the rows + weight_decay (|u|^2 + |p|^2 + |n|^2 / m)) / batch_size, `bpr_multi_loss`'s regulariser and
+    divisor.  With inv_tau = 1, zero corrections and positive dot products it is `bpr_multi_loss(..., reduction="softmax")` bit
+    for bit.  The corrections are data (no gradient); non-finite values in them are undefined.  `m` in [1, 64]."""
+    B, D, logq, pos_logq = _corrections("sampled_softmax_loss", u, p, n, logq, pos_logq, m, inv_tau)
+    lib = _lib.load()
+    w = ws.get(int(lib.ngcf_sampled_softmax_workspace_bytes(B)), u.device)
+    loss = torch.empty((), dtype=torch.float32, device=u.device)
+    with _on(u.device):
+        _lib.check(lib.ngcf_sampled_softmax_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, _ptr(logq), _ptr(pos_logq),
+                                                float(inv_tau), float(weight_decay), float(batch_size), _ptr(loss), _ptr(w), w.numel(),
+                                                _stream()))
+    return loss
+
+
+def sampled_softmax_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, logq: torch.Tensor, m: int, inv_tau: float,
+                             weight_decay: float, batch_size: float, grad_out: torch.Tensor, pos_logq: Optional[torch.Tensor] = None
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(du, dp, dn) of `sampled_softmax_loss` times the upstream scalar `grad_out` (a float32 device tensor of one element); row
+    b*m + j of dn belongs to the pair (b, j).  The scores are recomputed, nothing of the forward is kept."""
+    B, D, logq, pos_logq = _corrections("sampled_softmax_backward", u, p, n, logq, pos_logq, m, inv_tau)
+    if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != u.device:
+        raise ValueError(f"sampled_softmax_backward: grad_out must be one float32 on {u.device}")
+    lib = _lib.load()
+    du, dp, dn = torch.empty_like(u), torch.empty_like(p), torch.empty_like(n)
+    with _on(u.device):
+        _lib.check(lib.ngcf_sampled_softmax_backward_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, _ptr(logq),
+                                                         _ptr(pos_logq), float(inv_tau), float(weight_decay), float(batch_size),
+                                                         _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
     return du, dp, dn
 
 

@@ -102,10 +102,11 @@ test_candidates.__test__ = False          # a public name of the reference's voc
 
 
 class _EpochLoader:
-    """What the four loaders share: the columns' validation, the id table `[columns, n]` (int64; its last rows are the items and,
+    """What the five loaders share: the columns' validation, the id table `[columns, n]` (int64; its last rows are the items and,
     with one negative per row, the negatives), `len()`, the epoch counter and the one permutation and gather per `iter()`.  A
     loader is a constructor and `_draw`, which fills this epoch's negatives: the table's last row, or `self.neg` int64 [n, m] where a
-    row has m of them (None otherwise), which is gathered by the same permutation."""
+    row has m of them (None otherwise), which is gathered by the same permutation - and so is `self.logq`, a float array [n, m]
+    that goes with `self.neg` slot by slot (None otherwise) and ends the batch."""
 
     def __init__(self, name: str, users: torch.Tensor, columns: Sequence[torch.Tensor], tail: Sequence[torch.Tensor], *, batch_size: int,
                  shuffle: bool, drop_last: bool, generator: Optional[torch.Generator], m: Optional[int] = None, m_max: int = 0):
@@ -122,6 +123,7 @@ class _EpochLoader:
             raise ValueError(f"{name}: m={m} outside [1, {m_max}]")
         self.table = torch.stack([c.to(torch.int64) for c in cols])            # [columns, n]
         self.neg: Optional[torch.Tensor] = None
+        self.logq: Optional[torch.Tensor] = None
         self.n, self.batch_size, self.m, self.epoch = n, int(batch_size), m if m is None else int(m), 0
         self.shuffle, self.drop_last, self.generator = bool(shuffle), bool(drop_last), generator
 
@@ -138,14 +140,14 @@ class _EpochLoader:
 
     def _batches(self):
         used = len(self) * self.batch_size if self.drop_last else self.n
-        table, neg = self.table, self.neg
+        table, per_slot = self.table, [a for a in (self.neg, self.logq) if a is not None]
         if self.shuffle:
             rows = torch.randperm(self.n, generator=self.generator, device=table.device)[:used]
             table = table[:, rows]                                              # the epoch's one gathered copy
-            neg = None if neg is None else neg[rows]
+            per_slot = [a[rows] for a in per_slot]
         for b0 in range(0, used, self.batch_size):
             ids = tuple(table[:, b0:b0 + self.batch_size].unbind(0))
-            yield ids if neg is None else ids + (neg[b0:b0 + self.batch_size].reshape(-1),)
+            yield ids + tuple(a[b0:b0 + self.batch_size].reshape(-1) for a in per_slot)
 
 
 class TripletLoader(_EpochLoader):
@@ -275,7 +277,8 @@ def weighted_negatives(users: torch.Tensor, items: torch.Tensor, weights, seen: 
     distribution, not anyone's random stream; with all-ones weights it is uniform but does not return `train_negatives`' items.
     With `return_logq` a fourth tensor, float64 [T, m]: logq[t, j] = log(w_j / U_j), the log proposal probability of slot j given
     the slots before it, formed in torch from the kernel's exact integers - what a sampled softmax subtracts from the negatives'
-    scores (the corrected loss itself is not part of this package yet).  `m` in [1, 64].  A user id outside the sets raises
+    scores: `SampledSoftmax` takes it as it is (the conditional probability of successive sampling, not the marginal probability
+    that the item is among the m).  `m` in [1, 64].  A user id outside the sets raises
     IndexError, a user with fewer than `m` positive-weight unseen items ValueError."""
     m = int(m)
     if m < 1 or m > engine.negatives.WEIGHTED_M_MAX:
@@ -316,10 +319,10 @@ class WeightedNegativesLoader(_EpochLoader):
     def __init__(self, users: torch.Tensor, items: torch.Tensor, weights: torch.Tensor, columns: Sequence[torch.Tensor] = (), *,
                  batch_size: int, m: int, seed: int, shuffle: bool = True, drop_last: bool = True,
                  generator: Optional[torch.Generator] = None, seen: Optional[engine.ItemSets] = None):
-        super().__init__("WeightedNegativesLoader", users, columns, (items,), batch_size=batch_size, shuffle=shuffle,
+        super().__init__(type(self).__name__, users, columns, (items,), batch_size=batch_size, shuffle=shuffle,
                          drop_last=drop_last, generator=generator, m=m, m_max=engine.negatives.WEIGHTED_M_MAX)
         if weights.dtype != torch.int64 or weights.dim() != 1:
-            raise TypeError(f"WeightedNegativesLoader: weights must be an int64 [n_item] tensor, got {weights.dtype} {tuple(weights.shape)}")
+            raise TypeError(f"{type(self).__name__}: weights must be an int64 [n_item] tensor, got {weights.dtype} {tuple(weights.shape)}")
         engine._require_device(users, "users")
         self.neg = torch.empty((self.n, self.m), dtype=torch.int64, device=users.device)
         self.users = users.to(torch.int64).contiguous()
@@ -331,3 +334,23 @@ class WeightedNegativesLoader(_EpochLoader):
     def _draw(self):
         if self.n:
             engine.negatives.weighted_unseen(self.wsets, self.users, self.m, fmix(self.seed + self.epoch), out=self.neg)
+
+
+class LogQNegativesLoader(WeightedNegativesLoader):
+    """`WeightedNegativesLoader` that also delivers the log proposal probability of every negative, for a `SampledSoftmax`
+    criterion: same constructor, and a batch is `(*columns[b], items[b], neg[b].reshape(-1), logq[b].reshape(-1))` with `logq`
+    float32, `batch_size * m` values next to the ids they belong to - so the loop body of `Experiment.train` runs against it with
+    one more argument, `criterion(u, p, n, logq)`.  Every `iter()` calls `engine.negatives.weighted_unseen(..., return_weights=True)`
+    once, written into the loader's `.neg` [n, m], and forms `.logq` [n, m] = log(w_j / U_j) exactly as `weighted_negatives` does -
+    U_j from an int64 `cumsum`, the quotient and `log` in float64, then one cast to float32 - so under the epoch's permutation it
+    equals `weighted_negatives(..., epoch=e, return_logq=True)[3].float()`.  It is the conditional probability of slot j given the
+    slots before it (successive sampling), not the marginal probability that the item is among the m.  `.neg` is gathered by the
+    permutation as in the other loaders and `.logq` next to it."""
+
+    def _draw(self):
+        if not self.n:
+            return
+        _, w, mass = engine.negatives.weighted_unseen(self.wsets, self.users, self.m, fmix(self.seed + self.epoch), return_weights=True,
+                                                      out=self.neg)
+        left = mass[:, None] - (torch.cumsum(w, 1) - w)                                     # U_j, exact in int64
+        self.logq = torch.log(w.to(torch.float64) / left.to(torch.float64)).to(torch.float32)
