@@ -329,6 +329,11 @@ class Propagate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_all):
         n, widths, U = ctx.n_layer, ctx.widths, ctx.U
+        lease = getattr(ctx.csrs, "lease", None)           # reference-mode node dropout: the thinned CSRs are this forward's on loan
+        if lease is not None and lease.recycled:
+            raise RuntimeError("NGCF: a second backward through a forward with host-drawn node dropout, after a later forward took over "
+                               "its thinned Laplacians (they are handed on once a backward has run); run the backward passes before the "
+                               "next forward, or set node_dropout_mode = 'device'")
         saved = ctx.saved_tensors
         all_E = saved[0]
         les, carries = saved[1:1 + n], saved[1 + n:1 + 2 * n]
@@ -398,6 +403,8 @@ class Propagate(torch.autograd.Function):
             del S
             dC = dE
         dE0 = dC
+        if lease is not None:
+            lease.done = True                              # the next forward may take the thinned CSRs over
         if rows is not None:
             dE0.index_add_(0, rows, gv[:, :widths[0]])                           # the all_E block of E0 itself, R rows
         else:

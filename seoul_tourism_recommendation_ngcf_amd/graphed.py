@@ -13,6 +13,8 @@ all_items_emb` are the graph's static buffers: valid until the next replay (the 
 """
 from __future__ import annotations
 
+from itertools import chain
+
 import torch
 
 from . import engine as _eng
@@ -177,14 +179,33 @@ class GraphedForward:
             self.check_status()
 
 
+_data_ptr = torch.Tensor.data_ptr
+
+
+def _param_ptrs(model):
+    """The addresses of the parameter tensors as they are NOW.  Walking the module tree costs 25 us, more than the replay's launch:
+    `model._plist` caches the `_parameters` / `_modules` dicts of the tree (the dict objects survive `.to()`, `load_state_dict()` and
+    an assignment like `model.item_embedding.weight = nn.Parameter(...)`, which all write INTO them), and every call reads the
+    Parameter objects out of those dicts afresh - a replaced Parameter is seen at once, not only at the next rebuild.  A replaced
+    SUBMODULE brings dicts of its own: the children are compared by identity on every call, and the cache is rebuilt when one
+    differs.  Dicts that were EMPTY when the cache was built are left out: a Parameter or child registered later on a module that had
+    none is seen only after the next rebuild (`train()` / `eval()`, `.to()`, `load_state_dict()`) - nothing `NGCF.forward` reads."""
+    c = model._plist
+    if c is not None and [list(d.values()) for d in c[0]] != c[2]:     # (modules compare by identity)
+        c = None
+    if c is None:
+        mods = list(model.modules())
+        kids = [d for d in (m._modules for m in mods) if d]
+        c = model._plist = (kids, [d for d in (m._parameters for m in mods) if d], [list(d.values()) for d in kids])
+    params = list(chain.from_iterable(map(dict.values, c[1])))
+    try:
+        return tuple(map(_data_ptr, params))
+    except TypeError:                                                   # a None entry (`bias=False`)
+        return tuple(p.data_ptr() for p in params if p is not None)
+
+
 def _graph_key(model, dev, sizes, year_idx):
-    # the parameter tensors' addresses: from a cached list of the Parameter objects (walking the module tree costs 25 us, more
-    # than the replay's launch) that is rebuilt after train() / eval(), .to() / .cuda(), load_state_dict() and every 16th call
-    model._key_calls = getattr(model, "_key_calls", 0) + 1           # (its own counter: `_graph_calls` only moves on inference replays)
-    if model._plist is None or model._key_calls % 16 == 0:
-        model._plist = list(model.parameters())
-    ptrs = tuple(p.data_ptr() for p in model._plist)
-    return (sizes, year_idx, id(model.lap_list[year_idx]), str(dev), ptrs, float(model.emb_ratio))     # (emb_ratio is a kernel argument)
+    return (sizes, year_idx, id(model.lap_list[year_idx]), str(dev), _param_ptrs(model), float(model.emb_ratio))     # (emb_ratio is a kernel argument)
 
 
 def forward_graphed(model, dev, year, u_id, age, sex, month, day, dow, pos_item, neg_item):

@@ -121,6 +121,7 @@ class _DrawAhead:
         self.turn = 0
         self.spare = {}                     # (program, set index) -> a set put aside when another program came (year slices alternate)
         self.miss_streak = self.pause = 0   # three misses in a row (batches whose programs do not repeat): no helper for 32 forwards
+        self.lease_refs = {}                # year slice -> weak reference to the `_Lease` of the last forward's thinned CSRs (here: a copy of the model starts without)
 
     def __reduce__(self):                  # copy.deepcopy(model), torch.save(model): a copy starts without a helper
         return (_DrawAhead, ())
@@ -237,6 +238,42 @@ class _DrawAhead:
         return result
 
 
+class _Lease:
+    """Who may still need the thinned CSRs of ONE forward.  The next forward takes their device buffers over (`filtered(...,
+    reuse=...)` moves the handle and leaves the old object empty) - which is only right when the forward they were made for can no
+    longer run a backward: its autograd node is gone (the lease is dead: only the CSR lists on the node hold it), or its backward has
+    run (`done`).  While a forward still awaits its backward - two forwards before one backward - the next one gets buffers of its
+    own.  `recycled`: the buffers WERE handed on after a backward; a second backward through that forward (`retain_graph=True`)
+    says so instead of multiplying with another step's matrix."""
+    __slots__ = ("done", "recycled", "__weakref__")
+
+    def __init__(self):
+        self.done = self.recycled = False
+
+
+class _LeasedCSRs(list):
+    """The per-layer CSRs of one forward (`Propagate` keeps the list for its backward) with the lease of their buffers."""
+    lease: Optional[_Lease] = None
+
+
+def lease_of(csrs) -> Optional[_Lease]:
+    return getattr(csrs, "lease", None)
+
+
+def _take_over_allowed(ahead, year_idx: int):
+    """(may this forward recycle the thinned CSRs of the previous reference-mode forward on this year slice?, the lease of its
+    own) - see `_Lease`.  The buffers are kept per year slice (`model._filt`), and so are the leases."""
+    import weakref
+    ref = ahead.lease_refs.get(year_idx)
+    prev = ref() if ref is not None else None
+    ok = prev is None or prev.done
+    if prev is not None and ok:
+        prev.recycled = True
+    lease = _Lease()
+    ahead.lease_refs[year_idx] = weakref.ref(lease)
+    return ok, lease
+
+
 def reference_draws(model, year_idx: int, node_ref: bool, drop, mess_ref: bool):
     """Everything the reference draws from torch's default CPU generator during one forward, in its order
     (NGCF.py:123-142): per layer first the node-dropout keep mask (`nn.Dropout(p)` on float64 ones, on the
@@ -272,20 +309,23 @@ def reference_draws(model, year_idx: int, node_ref: bool, drop, mess_ref: bool):
 
 
 def _reference_draws_body(model, year_idx, node_ref, drop, mess_ref, src, dev, N, widths):
-    csrs, flags, masks = [], [], []
+    csrs, flags, masks = _LeasedCSRs(), [], []
     program = (src.nnz if node_ref else 0, float(model.node_dropout) if node_ref else None,
                tuple(float(x) for x in drop) if mess_ref else None, N, tuple(widths))
     ahead = model.__dict__.get("_draw_ahead")
     if ahead is None:
         ahead = model.__dict__["_draw_ahead"] = _DrawAhead()
     draws = ahead.take(program)                          # drawn by the helper thread during the previous step, or None
+    take_over = True
+    if node_ref:
+        take_over, csrs.lease = _take_over_allowed(ahead, year_idx)
     ahead_hit = draws is not None                        # (then the masks sit in page-locked buffers: asynchronous copies)
     for k, (keep, n_kept, noise) in enumerate(draws if ahead_hit else _draw_program(program)):
         if node_ref:
             # one flag per entry of the matrix as the previous layers left it (cumulative, NGCF.py:126); the thinned CSR is a
             # device compaction of the previous one into buffers this module keeps from step to step (ngcf_csr_filter)
             keep = keep.to(dev, non_blocking=ahead_hit)
-            src = src.filtered(keep, None, n_kept, reuse=model._filt.pop(("L", year_idx, k), None))
+            src = src.filtered(keep, None, n_kept, reuse=model._filt.pop(("L", year_idx, k), None) if take_over else None)
             model._filt[("L", year_idx, k)] = src
             csrs.append(src)
             flags.append(keep)
@@ -294,23 +334,25 @@ def _reference_draws_body(model, year_idx, node_ref, drop, mess_ref, src, dev, N
         ahead.copied()
     ahead.start(program)                                 # the next forward's masks, from the state this one leaves behind
     # the thinned matrices are not symmetric: their transposes are built only if a backward needs them
-    return (csrs if node_ref else None, (lambda: _thinned_transposes(model, year_idx, csrs, flags)) if node_ref else None,
+    return (csrs if node_ref else None, (lambda: _thinned_transposes(model, year_idx, csrs, flags, take_over)) if node_ref else None,
             masks if mess_ref else None)
 
 
-def _thinned_transposes(model, year_idx: int, csrs, flags):
+def _thinned_transposes(model, year_idx: int, csrs, flags, take_over: bool = True):
     """(thinned L_k)^T for every layer, as device compactions of the cached L^T (and of each other): entry j of the transpose
-    is kept iff the flag of its twin in L_k-1 is set, found through an entry map that is carried from layer to layer."""
+    is kept iff the flag of its twin in L_k-1 is set, found through an entry map that is carried from layer to layer.
+    `take_over`: the previous forward's transposes may be recycled (`_Lease`); the returned list shares the lease of `csrs`."""
     dev = model._dev()
     src_t = model.laplacian_csr_t(year_idx)
     emap = model._csr_cache.get(("Tmap", year_idx, id(model.lap_list[year_idx]), str(dev)))
     if emap is None:
         raise RuntimeError("reference-mode node dropout: more than 2^31 stored entries")
     lib = _eng._lib.load()
-    out = []
+    out = _LeasedCSRs()
+    out.lease = lease_of(csrs)
     for k, (csr_k, keep) in enumerate(zip(csrs, flags)):
         n_src = src_t.nnz
-        t = src_t.filtered(keep, emap, csr_k.nnz, reuse=model._filt.pop(("T", year_idx, k), None))
+        t = src_t.filtered(keep, emap, csr_k.nnz, reuse=model._filt.pop(("T", year_idx, k), None) if take_over else None)
         model._filt[("T", year_idx, k)] = t
         out.append(t)
         if k + 1 < len(csrs):

@@ -244,14 +244,17 @@ def forward_train_graphed(model, dev, year, u_id, age, sex, month, day, dow, pos
             return None
         for k in list(model._train_graphs)[:max(0, len(model._train_graphs) - 3)]:     # a handful of shapes (full batch, last batch)
             model._train_graphs.pop(k, None)
-        if getattr(model, "_seed_state", None) is None:
-            model._device_seeds()                                  # (created outside the capture; nothing has drawn from it yet)
+        # A forward that draws masks has created the seed state in its first (eager) call.  One that draws none must not create it:
+        # the first drawing forward after `torch.manual_seed` uses the seeds as handed out, every later one steps them first
+        # (`NGCF._device_seeds`), so a state made here would put every later mask one step ahead of the eager run's.  (When the state
+        # appears later, `intact()` sees a baked pointer change and these graphs are captured once more.)
+        seed_state = model._seed_state.clone() if getattr(model, "_seed_state", None) is not None else None
         model._scratch_buf(dev)
-        seed_state = model._seed_state.clone()
         model._status_buf(dev)
         with _eng._on(dev):                                        # (streams and graphs belong to the model's device)
             g = _TrainGraphs(model, year_idx, bool(node_flag), has_neg, args)
-        model._seed_state.copy_(seed_state)                        # the warm-up forwards stepped it
+        if seed_state is not None:
+            model._seed_state.copy_(seed_state)                    # the warm-up forwards stepped it
         if model.check_indices:
             model._raise_if_status()
     model._train_graphs[key] = g

@@ -148,7 +148,8 @@ def test_unchanged_callers_get_the_graph_replay(dev):
     for _ in range(3):
         same(eval_batch(year=19))                                      # the other year slice: its own graph
     assert len(auto._graphs) == 3
-    auto.user_embedding.weight = torch.nn.Parameter(auto.user_embedding.weight.detach().clone())   # a replaced parameter: re-capture
+    for m in (plain, auto):                                            # a replaced parameter with OTHER values: re-capture
+        m.user_embedding.weight = torch.nn.Parameter(m.user_embedding.weight.detach() + 0.5)
     for _ in range(3):
         same(eval_batch())
     assert len(auto._graphs) == 3
