@@ -447,7 +447,24 @@ __device__ inline float log_sigmoid(float x)      // F.logsigmoid (bprloss.py:19
     return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
 }
 
-// The second stage of both BPR losses (ops.hip, bpr_multi.hip), one workgroup of 256: the workgroups' partials
+// The first stage's tail in the row losses (ops.hip, loss_rows_device.h), a wave per row and four waves per workgroup: the waves'
+// (nl, sq) = (the row's loss, its sum of squares; 0 in a wave without a row) -> the workgroup's two partials part[2*block + 0 / 1].
+// (wave, lane: the thread's, which every caller has at hand.)
+__device__ inline void bpr_block_partials(int wave, int lane, float nl, float sq, float *__restrict__ part)
+{
+    __shared__ float sh[8];
+    if (lane == 0) {
+        sh[wave * 2] = nl;
+        sh[wave * 2 + 1] = sq;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[2 * (int64_t)blockIdx.x] = (sh[0] + sh[2]) + (sh[4] + sh[6]);
+        part[2 * (int64_t)blockIdx.x + 1] = (sh[1] + sh[3]) + (sh[5] + sh[7]);
+    }
+}
+
+// The second stage of the row losses (ops.hip, loss_rows_device.h), one workgroup of 256: the workgroups' partials
 // part[2*i] = -sum logsigmoid, part[2*i + 1] = sum of squares in a fixed order -> *loss (bprloss.py:20-22).
 __device__ inline void bpr_finish_block(const float *__restrict__ part, int64_t n_blocks, float wd, float batch_size,
                                         float *__restrict__ loss)

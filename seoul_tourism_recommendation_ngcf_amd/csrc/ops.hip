@@ -283,7 +283,6 @@ __global__ __launch_bounds__(256) void bpr_rows_kernel(const float *__restrict__
                                                        int64_t Bp, const float *__restrict__ n, int64_t Bn, int64_t R,
                                                        int D, float *__restrict__ part)
 {
-    __shared__ float sh[8];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + wave;
     float nl = 0.f, sq = 0.f;
@@ -309,21 +308,13 @@ __global__ __launch_bounds__(256) void bpr_rows_kernel(const float *__restrict__
         // each tensor's own rows are counted once (a broadcast row only at r == 0)
         sq = (r < Bu ? uu : 0.f) + (r < Bp ? pp : 0.f) + (r < Bn ? nn : 0.f);
     }
-    if (lane == 0) {
-        sh[wave * 2] = nl;
-        sh[wave * 2 + 1] = sq;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * (int64_t)blockIdx.x] = (sh[0] + sh[2]) + (sh[4] + sh[6]);
-        part[2 * (int64_t)blockIdx.x + 1] = (sh[1] + sh[3]) + (sh[5] + sh[7]);
-    }
+    bpr_block_partials(wave, lane, nl, sq, part);                               // (common.h: shared with loss_rows_device.h, as is the next)
 }
 
 __global__ __launch_bounds__(256) void bpr_finish_kernel(const float *__restrict__ part, int64_t n_blocks, float wd,
                                                          float batch_size, float *__restrict__ loss)
 {
-    bpr_finish_block(part, n_blocks, wd, batch_size, loss);         // (common.h: shared with bpr_multi.hip)
+    bpr_finish_block(part, n_blocks, wd, batch_size, loss);
 }
 
 extern "C" int64_t ngcf_bpr_workspace_bytes(int64_t R)

@@ -42,6 +42,12 @@ def _operands(fn: str, u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int
     return B, D, REDUCTIONS[reduction]
 
 
+def _require_grad_out(fn: str, grad_out: torch.Tensor, device: torch.device) -> None:
+    """The upstream gradient of a scalar loss, as every backward here takes it."""
+    if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != device:
+        raise ValueError(f"{fn}: grad_out must be one float32 on {device}")
+
+
 def bpr_multi_loss(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int, weight_decay: float, batch_size: float,
                    ws: Workspace, reduction: str = "mean") -> torch.Tensor:
     """The loss of `u` [B, D], `p` [B, D] and `n` [B*m, D] (rows b*m .. b*m + m - 1: the negatives of row b), float32 and
@@ -64,8 +70,7 @@ def bpr_multi_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int
     """(du, dp, dn) of `bpr_multi_loss` times the upstream scalar `grad_out` (a float32 device tensor of one element); row
     b*m + j of dn belongs to the pair (b, j).  The scores are recomputed, nothing of the forward is kept."""
     B, D, red = _operands("bpr_multi_backward", u, p, n, m, reduction)
-    if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != u.device:
-        raise ValueError(f"bpr_multi_backward: grad_out must be one float32 on {u.device}")
+    _require_grad_out("bpr_multi_backward", grad_out, u.device)
     lib = _lib.load()
     du, dp, dn = torch.empty_like(u), torch.empty_like(p), torch.empty_like(n)
     with _on(u.device):
@@ -125,8 +130,7 @@ def sampled_softmax_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, 
     """(du, dp, dn) of `sampled_softmax_loss` times the upstream scalar `grad_out` (a float32 device tensor of one element); row
     b*m + j of dn belongs to the pair (b, j).  The scores are recomputed, nothing of the forward is kept."""
     B, D, logq, pos_logq = _corrections("sampled_softmax_backward", u, p, n, logq, pos_logq, m, inv_tau)
-    if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != u.device:
-        raise ValueError(f"sampled_softmax_backward: grad_out must be one float32 on {u.device}")
+    _require_grad_out("sampled_softmax_backward", grad_out, u.device)
     lib = _lib.load()
     du, dp, dn = torch.empty_like(u), torch.empty_like(p), torch.empty_like(n)
     with _on(u.device):
@@ -217,8 +221,7 @@ def softmax_full_backward(u: torch.Tensor, items: torch.Tensor, pos: torch.Tenso
     dev = u.device
     if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or lse.device != dev or not lse.is_contiguous():
         raise ValueError(f"softmax_full_backward: lse must be a contiguous float32 tensor of {B} elements on {dev}")
-    if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != dev:
-        raise ValueError(f"softmax_full_backward: grad_out must be one float32 on {dev}")
+    _require_grad_out("softmax_full_backward", grad_out, dev)
     if not (need_u or need_items):
         return None, None
     lib = _lib.load()

@@ -140,6 +140,20 @@ def test_values_at_the_widest_concatenation(reduction, dev):
         print("\nbpr_multi ratios wide: " + " ".join(f"{k}={v:.3f}" for k, v in ratios.items()))
 
 
+@pytest.mark.parametrize("reduction", ["mean", "softmax"])
+@pytest.mark.parametrize("D", (200, 600, 1539, 2049))
+def test_every_register_width_and_row_batch(D, reduction, dev):
+    """The widths the grid above leaves out: 4, 16 (the only one that walks two rows at a time) and 32 registers of u per lane and
+    the kernel without, each at m = 1, 3, 5, 6 and 64 - a group of four negatives cut in the middle, cut at a batch of two, and
+    complete.  B = 5: two workgroups, the second with one live wave."""
+    pkg = _pkg()
+    ratios = {}
+    for m in (1, 3, 5, 6, 64):
+        _check_values(pkg, dev, 5, m, D, reduction, ratios)
+    if ratios:
+        print(f"\nbpr_multi ratios D={D}: " + " ".join(f"{k}={v:.3f}" for k, v in ratios.items()))
+
+
 def test_softmax_near_300_is_finite_and_the_oracles(dev):
     """Scores of exactly 297 .. 303 (small integers: every product and partial sum is exact in float32, in any order), both signs
     of the dot products: exp of any of them overflows float32, the loss and the gradients do not."""

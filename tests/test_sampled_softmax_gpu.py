@@ -95,13 +95,24 @@ def test_values_at_the_widest_concatenation(dev):
     _check_values(pkg, dev, 3, 2, 2049)
 
 
+@pytest.mark.parametrize("D", (200, 600, 1539, 2049))
+def test_every_register_width_and_row_batch(D, dev):
+    """The widths the grid above leaves out: 4, 16 (the only one that walks two rows at a time) and 32 registers of u per lane and
+    the kernel without, each at m = 1, 3, 5, 6 and 64 - a group of four negatives cut in the middle, cut at a batch of two, and
+    complete.  B = 5: two workgroups, the second with one live wave."""
+    pkg = _pkg()
+    for m in (1, 3, 5, 6, 64):
+        _check_values(pkg, dev, 5, m, D)
+
+
 # ---- the identity with the multi-negative softmax ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", (1, 5, 1025))
 def test_without_correction_it_is_the_multi_negative_softmax_bit_for_bit(B, dev):
-    """inv_tau = 1, logq = 0, no pos_logq, every dot product positive: x * 1 - 0 is x and BPRMulti's sign factors are exactly 1."""
+    """inv_tau = 1, logq = 0, no pos_logq, every dot product positive: x * 1 - 0 is x and BPRMulti's sign factors are exactly 1.
+    (D = 600, 1 539, 2 049 at m = 5: two rows at a time, 32 registers of u, and none.)"""
     pkg = _pkg()
-    for D in (63, 65, 260):
-        for m in (1, 3, 64):
+    for D, ms in ((63, (1, 3, 64)), (65, (1, 3, 64)), (260, (1, 3, 64)), (600, (5,)), (1539, (5,)), (2049, (5,))):
+        for m in ms:
             rng = np.random.default_rng(B * 1000 + D * 10 + m)
             u, p, n = (np.abs(rng.standard_normal(s)).astype(np.float32) / D ** 0.25 for s in ((B, D), (B, D), (B * m, D)))
             u64 = u.astype(np.float64)

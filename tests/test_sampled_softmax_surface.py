@@ -36,17 +36,28 @@ def test_symbols_are_declared_bound_and_exported():
 
 
 def test_the_row_machinery_is_defined_once():
-    """URow, RowBatch, the score pass, wave_max and lane_value live in csrc/loss_rows_device.h, which both loss files include."""
+    """URow, RowBatch, the score pass, wave_max and lane_value, the softmax over the lanes, the backward's walk over the negatives,
+    the operand check, the workspace and the finish launch live in csrc/loss_rows_device.h, which both loss files include; the
+    forward's partials tail in csrc/common.h, next to the second stage."""
     from seoul_tourism_recommendation_ngcf_amd import _build
     text = {}
-    for name in ("loss_rows_device.h", "bpr_multi.hip", "sampled_softmax.hip"):
+    for name in ("loss_rows_device.h", "bpr_multi.hip", "sampled_softmax.hip", "common.h"):
         with open(os.path.join(_build.CSRC, name)) as f:
             text[name] = f.read()
-    for definition in ("struct URow {", "struct RowBatch {", "Scores score_row(", "float wave_max(float", "float lane_value(float"):
+    for definition in ("struct URow {", "struct RowBatch {", "Scores score_row(", "float wave_max(float", "float lane_value(float",
+                       "void gradient_walk(", "float lanes_lse(float", "float softmax_weight(float", "int check_rows(const char",
+                       "int64_t partials_workspace_bytes(int64_t", "int partials_in(const char", "int finish_loss(const float",
+                       "void loss_rows_finish_kernel(", "#define LOSS_ROWS_LAUNCH("):
         assert text["loss_rows_device.h"].count(definition) == 1, definition
         assert definition not in text["bpr_multi.hip"] and definition not in text["sampled_softmax.hip"], definition
+    assert text["common.h"].count("void bpr_block_partials(") == 1
     for name in ("bpr_multi.hip", "sampled_softmax.hip"):
         assert '#include "loss_rows_device.h"' in text[name]
+        assert "bpr_block_partials(wave, lane, nl, sq, part);" in text[name] and "gradient_walk<KU>(" in text[name]
+        # what the shared definitions replaced: no partials array, walk, finish kernel, size formula, dispatch layer or log-sum-exp
+        # of the file's own
+        for gone in ("__shared__", "acc[", "_finish_kernel", "align_up(", "launch_forward", "launch_backward", "logf(", "wave_max("):
+            assert gone not in text[name], (name, gone)
 
 
 def test_workspace_is_the_two_float_partials_of_four_rows():
