@@ -448,6 +448,57 @@ int ngcf_softmax_full_backward_f32(const float *users, int64_t ldu, int64_t B, c
                                    float batch_size, const float *grad_out, float *du, int64_t lddu, float *ditems, int64_t lddi,
                                    void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- In-batch softmax (csrc/inbatch_softmax.hip) ----------------------------------------------- */
+/*
+ * The softmax loss with SHARED negatives: every row's positive is a negative of every other row, E extra rows are appended to the
+ * columns; per-column logQ corrections and a mask of false negatives; without a [B, B + E] matrix in memory.
+ *   u: [B, D] fp32 rows (ldu), p: [B, D] the positives' rows (ldp), x: [E, D] extra rows (ldx; NULL when E = 0)
+ *   columns c_j = p_j (j < B), x_(j-B) (B <= j < C = B + E);  ids cid_j = ids[j] / xids[j - B] (int64);  q_j = logq[j] / xlogq[j - B]
+ *   ids, xids, logq, xlogq, pos_logq may be NULL: no mask / a correction of exactly 0
+ *   s_bj = <u_b, c_j> * inv_tau                       plain score, as in the full-catalogue section
+ *   z_bb = s_bb - pos_logq[b]         z_bj = s_bj - q_j  (j != b)          one fp32 subtraction, rounded once
+ *   masked(b, j) = ids given and j != b and cid_j == ids[b]                 out of the softmax, zero gradient; never the diagonal
+ *   L_b  = lse over unmasked j of z_bj  -  z_bb
+ *   loss = (sum_b L_b + wd * (sum_b |u_b|^2 + sum_b |p_b|^2)) / batch_size    the extras are not regularised
+ * Ids are only compared, never an index: no range check and no status word.  B >= 1, E >= 0, C < 2^31, D >= 1, inv_tau > 0 and
+ * finite, batch_size > 0, xids given whenever ids are and E > 0; anything else is NGCF_ERR_ARG before any launch.
+ *
+ * The recipe is the full-catalogue section's with n_items = C, operation by operation (the kernels are the same templates,
+ * csrc/softmax_tile_device.h), with these differences:
+ *   score    the same chain and s_bj = acc * inv_tau; then z = s - q, q as above (0.f for a NULL array).
+ *   forward  a score enters the lane's (tm, l) only if unmasked; the positive's score is z_bb, picked up by the lane that holds
+ *            column b (workspace, not exported).
+ *   sums     L_b = (double)lse_b - (double)z_bb;  |u_b|^2 and |p_b|^2 as there.
+ *   Without ids and corrections loss, lse, dU and dp over dx have the bits of ngcf_softmax_full_* on the rows p over x with
+ *   pos[b] = b; all-zero corrections have the bits of NULL ones.
+ *
+ * Gradients, times *grad_out (one device float):  g0 = grad_out / batch_size,  c = g0 * inv_tau  (in that order)
+ *   g_bj = masked ? 0 : c * (expf(z_bj - lse_b) - [j == b])          z_bj recomputed by the recipe above
+ *   dU_b = sum_j g_bj c_j + (2 wd g0) u_b
+ *   dC_j = sum_b g_bj u_b + [j < B] (2 wd g0) p_j          rows j < B to dp, the others to dx
+ * by the role-swapped kernel of the full-catalogue section: one chain fmaf(g, w, acc) per output element over the walked rows
+ * ascending, the weight-decay term last as fmaf(2 wd g0, x, acc) - for dU in piece 0, for dC in the piece that walks user j.
+ * Any of du / dp / dx may be NULL (not all; dx is ignored when E = 0): that gradient is not stored, the others keep their bits.
+ * No float atomics; loss, lse, dU, dp and dx are bit-identical from run to run; no host synchronisation, so both calls can be
+ * captured.
+ *
+ * ngcf_inbatch_softmax_plan (host only): out = {forward pieces, 1, dU pieces, dU column slabs, dC pieces, dC column slabs} - that of
+ * ngcf_softmax_full_plan(B, B + E, D).  Workspace for both calls: ngcf_inbatch_softmax_workspace_bytes(B, E, D) = that of the full
+ * catalogue at (B, B + E, D) plus B floats (NGCF_ERR_WORKSPACE when shorter; -1 for a bad shape).
+ */
+int ngcf_inbatch_softmax_plan(int64_t B, int64_t E, int D, int64_t out[6]);
+int64_t ngcf_inbatch_softmax_workspace_bytes(int64_t B, int64_t E, int D);
+int ngcf_inbatch_softmax_f32(const float *u, int64_t ldu, int64_t B, const float *p, int64_t ldp, const float *x, int64_t ldx,
+                             int64_t E, int D, const int64_t *ids, const int64_t *xids, const float *logq, const float *xlogq,
+                             const float *pos_logq, float inv_tau, float weight_decay, float batch_size, float *loss, float *lse,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int ngcf_inbatch_softmax_backward_f32(const float *u, int64_t ldu, int64_t B, const float *p, int64_t ldp, const float *x,
+                                      int64_t ldx, int64_t E, int D, const int64_t *ids, const int64_t *xids, const float *logq,
+                                      const float *xlogq, const float *pos_logq, const float *lse, float inv_tau,
+                                      float weight_decay, float batch_size, const float *grad_out, float *du, int64_t lddu,
+                                      float *dp, int64_t lddp, float *dx, int64_t lddx, void *workspace, int64_t workspace_bytes,
+                                      void *stream);
+
 /* ---- backward pass (`loss.backward()` of experiment.py:57; driven by autograd.py) -------------- */
 /* Everything `loss.backward()` runs: no library GEMM at any width.  L^T.dLE re-uses ngcf_spmm_csr_f32 on the CSR of L^T. */
 /* du/dp/dn of the BPR loss (bprloss.py:15-22) times the upstream scalar *grad_out (device). */

@@ -5,7 +5,7 @@ Drop-in for the hot path of haesungpyun/seoul_tourism_recommendation_NGCF:
 `from NGCF import NGCF` / `from bprloss import BPR` in main.py, experiment.py and demo.py.
 """
 from .NGCF import NGCF
-from .bprloss import BPR, BPRMulti, SampledSoftmax, SoftmaxFull
+from .bprloss import BPR, BPRMulti, InBatchSoftmax, SampledSoftmax, SoftmaxFull
 from .graphed import GraphedForward, GraphedTrainStep
 from . import engine, graphs
 from . import evaluate
@@ -14,4 +14,4 @@ from . import sampling
 from . import preprocess
 from . import optim
 
-__all__ = ["NGCF", "BPR", "BPRMulti", "SampledSoftmax", "SoftmaxFull", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling", "preprocess", "optim"]
+__all__ = ["NGCF", "BPR", "BPRMulti", "SampledSoftmax", "SoftmaxFull", "InBatchSoftmax", "GraphedForward", "GraphedTrainStep", "engine", "graphs", "evaluate", "recommend", "sampling", "preprocess", "optim"]

@@ -86,6 +86,12 @@ PROTOTYPES = {
                                         _vp]),
     "ngcf_softmax_full_backward_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _i64,
                                                  _vp, _i64, _vp, _i64, _vp]),
+    "ngcf_inbatch_softmax_plan": (C.c_int, [_i64, _i64, C.c_int, C.POINTER(_i64)]),
+    "ngcf_inbatch_softmax_workspace_bytes": (_i64, [_i64, _i64, C.c_int]),
+    "ngcf_inbatch_softmax_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32,
+                                           _vp, _vp, _vp, _i64, _vp]),
+    "ngcf_inbatch_softmax_backward_f32": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
+                                                    _f32, _f32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ngcf_rows_sort_unique": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ngcf_segment_sum_rows_f32": (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp]),
     "ngcf_layer_bwd_pre_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, C.c_int, _f32, _f32, _u64, _vp, _i64,

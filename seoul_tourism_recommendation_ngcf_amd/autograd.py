@@ -556,6 +556,35 @@ class SoftmaxFullLoss(torch.autograd.Function):
         return du, di, None, None, None, None, None, None
 
 
+class InBatchSoftmaxLoss(torch.autograd.Function):
+    """The softmax with shared (in-batch) negatives (engine.losses): the forward keeps `lse`, the backward recomputes the scores and
+    computes only the gradients autograd asks for.  The ids and the corrections are data; `extra` may be None."""
+
+    @staticmethod
+    def forward(ctx, u, p, extra, ids, logq, pos_logq, extra_ids, extra_logq, inv_tau, weight_decay, batch_size, ws):
+        ctx.inv_tau, ctx.wd, ctx.bs, ctx.ws = float(inv_tau), float(weight_decay), float(batch_size), ws
+        # a float64 correction is cast here, once for both directions (any other type is left to the wrapper's refusal)
+        logq, pos_logq, extra_logq = (t.to(torch.float32) if t is not None and t.dtype == torch.float64 else t
+                                      for t in (logq, pos_logq, extra_logq))
+        opt = (extra, ids, logq, pos_logq, extra_ids, extra_logq)
+        ctx.given = tuple(t is not None for t in opt)
+        loss, lse = _eng.losses.inbatch_softmax_loss(u, p, inv_tau, weight_decay, batch_size, ws, ids=ids, logq=logq, pos_logq=pos_logq,
+                                                     extra=extra, extra_ids=extra_ids, extra_logq=extra_logq)
+        ctx.save_for_backward(u, p, lse, *(t for t in opt if t is not None))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        u, p, lse = ctx.saved_tensors[:3]
+        rest = iter(ctx.saved_tensors[3:])
+        extra, ids, logq, pos_logq, extra_ids, extra_logq = (next(rest) if has else None for has in ctx.given)
+        du, dp, dx = _eng.losses.inbatch_softmax_backward(u, p, ctx.inv_tau, ctx.wd, ctx.bs, lse, g.to(torch.float32).contiguous(), ctx.ws,
+                                                          ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2],
+                                                          ids=ids, logq=logq, pos_logq=pos_logq, extra=extra, extra_ids=extra_ids,
+                                                          extra_logq=extra_logq)
+        return (du, dp, dx) + (None,) * 9
+
+
 def propagate_with_grad(owner, csrs, csrs_t_fn, user_w, item_w, w1, b1, w2, b2, drop, seeds, edge_drops=None,
                         masks=None, keep_alive=None) -> torch.Tensor:
     """Inference path unless a gradient can flow; then the autograd Function (needs the CSRs of L^T)."""

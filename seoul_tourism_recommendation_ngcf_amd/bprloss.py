@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import engine as _eng
-from .autograd import BPRLoss, BPRMultiLoss, SampledSoftmaxLoss, SoftmaxFullLoss
+from .autograd import BPRLoss, BPRMultiLoss, InBatchSoftmaxLoss, SampledSoftmaxLoss, SoftmaxFullLoss
 
 
 class BPR(nn.Module):
@@ -143,4 +143,55 @@ class SoftmaxFull(nn.Module):
             self.status.zero_()
             bad = pos_item[(pos_item < 0) | (pos_item >= item_table.shape[0])]
             raise IndexError(f"SoftmaxFull: pos_item holds {int(bad[0])}, outside the catalogue of {int(item_table.shape[0])} items")
+        return loss
+
+
+class InBatchSoftmax(nn.Module):
+    """The softmax loss with SHARED (in-batch) negatives, the default of two-tower recommenders, on the fused HIP kernels of
+    `engine.losses`: every row's positive item is a negative of every other row of the batch, so no sampler is needed, a batch
+    gathers 2 B rows and every row has B - 1 negatives; the [B, B + E] score matrix and its gradient are never in memory.
+
+    `forward(u, pos, item_ids=None, logq=None, pos_logq=None, extra=None, extra_ids=None, extra_logq=None)` -> 0-dim tensor with
+    `u`, `pos` [B, D] the rows the model returns and `extra` [E, D] further rows shared by the whole batch (mixed negative sampling:
+    drawn by the caller, e.g. uniformly, so that an item nobody bought can be a negative too).  The columns are the positives, then
+    the extras.  With plain scores (no `abs`, as in `SoftmaxFull`) s_bj = <u_b, c_j> / temperature:
+        z_bb = s_bb - pos_logq[b]        z_bj = s_bj - logq[j]  or  s_bj - extra_logq[j - B]        (a correction left out is 0)
+        row b gives logsumexp over its unmasked columns of z_bj, minus z_bb
+    and the loss is (sum of the rows + weight_decay (|u|^2 + |pos|^2)) / batch_size: the extras are not regularised.  `logq` is the
+    log of the chance that the column's item is in a batch, its popularity (`sampling.item_logq`, delivered per batch by
+    `sampling.InBatchLoader`); `pos_logq = logq` is the form of Yi et al. (2019).  With `item_ids` [B] int64 (and `extra_ids` [E],
+    required next to them when there are extras) a column whose item is row b's own positive - another row of the batch that bought
+    the same item, or an extra that drew it - is a false negative: it leaves row b's softmax and gets no gradient from it.  The
+    diagonal is never masked.  Ids are only compared, never an index; the ids and corrections carry no gradient.
+
+    Only the gathered rows are touched, which carry their gradients through the model's captured training graphs: a loop keeps
+    `model.auto_train_graph` at its default, unlike `SoftmaxFull`:
+
+        for year, u_id, age, sex, month, day, dow, pos_item, lq in loader:                  # sampling.InBatchLoader(..., logq=table)
+            u, p, x = model(year, u_id, age, sex, month, day, dow, pos_item, extra_ids, True)
+            loss = crit(u, p, item_ids=pos_item, logq=lq, extra=x, extra_ids=extra_ids, extra_logq=xlq)
+
+    Not done: masking a user's OTHER seen items, a symmetric item-to-user term, the loss inside `GraphedTrainStep`."""
+
+    def __init__(self, weight_decay, batch_size, temperature=1.0):
+        super().__init__()
+        t = float(temperature)
+        if not (t > 0 and t < float("inf")):
+            raise ValueError(f"InBatchSoftmax: temperature={temperature} is not a positive finite number")
+        self.weight_decay = weight_decay
+        self.batch_size = batch_size
+        self.temperature = t
+        self._ws = _eng.Workspace()
+
+    def forward(self, u, pos, item_ids=None, logq=None, pos_logq=None, extra=None, extra_ids=None, extra_logq=None):
+        inv_tau = 1.0 / self.temperature
+        if extra is not None and extra.shape[0] == 0:
+            extra = extra_ids = extra_logq = None
+        if torch.is_grad_enabled() and (u.requires_grad or pos.requires_grad or (extra is not None and extra.requires_grad)):
+            return InBatchSoftmaxLoss.apply(u, pos, extra, item_ids, logq, pos_logq, extra_ids, extra_logq, inv_tau, self.weight_decay,
+                                            self.batch_size, self._ws)
+        loss, _ = _eng.losses.inbatch_softmax_loss(u.detach(), pos.detach(), inv_tau, self.weight_decay, self.batch_size, self._ws,
+                                                   ids=item_ids, logq=logq, pos_logq=pos_logq,
+                                                   extra=None if extra is None else extra.detach(), extra_ids=extra_ids,
+                                                   extra_logq=extra_logq)
         return loss

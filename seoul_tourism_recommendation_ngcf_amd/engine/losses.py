@@ -2,8 +2,9 @@
 header next to the BPR section): the loss of `[B, D]` users and positives and `[B*m, D]` negatives without expanding the batch to
 `B*m` triplets, and its three gradients; the sampled softmax over the same operands with the logQ correction and a temperature
 (`ngcf_sampled_softmax_f32` / `ngcf_sampled_softmax_backward_f32`: csrc/sampled_softmax.hip); and the limit of that series, the softmax over the WHOLE catalogue (`ngcf_softmax_full_f32`
-/ `ngcf_softmax_full_backward_f32`: csrc/softmax_full.hip), whose [B, n_items] score matrix is never in memory.  Like the wrappers
-of `layers`, no check here costs a host sync."""
+/ `ngcf_softmax_full_backward_f32`: csrc/softmax_full.hip), whose [B, n_items] score matrix is never in memory; and the softmax with
+shared (in-batch) negatives on the same kernels (`ngcf_inbatch_softmax_f32` / `ngcf_inbatch_softmax_backward_f32`:
+csrc/inbatch_softmax.hip).  Like the wrappers of `layers`, no check here costs a host sync."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -234,3 +235,122 @@ def softmax_full_backward(u: torch.Tensor, items: torch.Tensor, pos: torch.Tenso
                                                       float(inv_tau), float(weight_decay), float(batch_size), _ptr(grad_out),
                                                       _ptr(du), D, _ptr(di), D, _ptr(w), w.numel(), _stream()))
     return du, di
+
+
+# ---- the softmax with shared (in-batch) negatives (`ngcf_inbatch_softmax_f32` / `ngcf_inbatch_softmax_backward_f32`: csrc/inbatch_softmax.hip)
+def _inbatch_operands(fn: str, u: torch.Tensor, p: torch.Tensor, inv_tau: float, ids, logq, pos_logq, extra, extra_ids, extra_logq):
+    """The refusals of both in-batch calls, before anything reaches the device, in the order of `_full_operands` and `_corrections`:
+    sizes (ValueError), types (TypeError), the temperature, the devices (RuntimeError).
+    -> (B, E, D, extra or None, ids, extra_ids, logq, extra_logq, pos_logq), the corrections as contiguous float32 (a float64 one is
+    cast once, here), the ids contiguous; what goes with the extras is None when there are none."""
+    for nm, t in (("u", u), ("pos", p), ("extra", extra)):
+        if t is not None and t.dim() != 2:
+            raise ValueError(f"{fn}: {nm} must be 2-D, got shape {tuple(t.shape)}")
+    B, D = int(u.shape[0]), int(u.shape[1])
+    if B < 1 or D < 1:
+        raise ValueError(f"{fn}: u is {tuple(u.shape)}: at least one row and one column expected")
+    if tuple(p.shape) != (B, D):
+        raise ValueError(f"{fn}: u {tuple(u.shape)} and pos {tuple(p.shape)} are not both [B, D]")
+    E = 0 if extra is None else int(extra.shape[0])
+    if extra is not None and int(extra.shape[1]) != D:
+        raise ValueError(f"{fn}: u {tuple(u.shape)} and extra {tuple(extra.shape)} differ in width")
+    if B + E >= 2 ** 31:
+        raise ValueError(f"{fn}: B + E = {B + E} columns, below 2^31 expected")
+    for nm, t, n, of in (("ids", ids, B, "B"), ("logq", logq, B, "B"), ("pos_logq", pos_logq, B, "B"), ("extra_ids", extra_ids, E, "E"),
+                         ("extra_logq", extra_logq, E, "E")):
+        if t is not None and tuple(t.shape) != (n,):
+            raise ValueError(f"{fn}: {nm} must be [{of}] with {of}={n}, got shape {tuple(t.shape)}")
+    if ids is not None and E > 0 and extra_ids is None:
+        raise ValueError(f"{fn}: ids given with {E} extra rows and no extra_ids: the mask needs the extras' ids too")
+    rows = (("u", u), ("pos", p), ("extra", extra))
+    _require_dtype(fn, torch.float32, rows)
+    _require_dtype(fn, torch.int64, (("ids", ids), ("extra_ids", extra_ids)))
+    for nm, t in (("logq", logq), ("pos_logq", pos_logq), ("extra_logq", extra_logq)):
+        if t is not None and t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{fn}: {nm} must be float32 or float64, got {t.dtype}")
+    for nm, t in rows:
+        if t is None:
+            continue
+        if D > 1 and t.stride(1) != 1:
+            raise ValueError(f"{fn}: {nm} must have unit stride in its last dimension, got strides {t.stride()}")
+        if int(t.shape[0]) > 1 and t.stride(0) < D:
+            raise ValueError(f"{fn}: the rows of {nm} overlap, strides {t.stride()}")
+    if not (inv_tau > 0 and inv_tau < float("inf")):
+        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+    _require_device(u, "u")
+    _require_same_device(fn, (("pos", p), ("extra", extra), ("ids", ids), ("extra_ids", extra_ids), ("logq", logq),
+                              ("pos_logq", pos_logq), ("extra_logq", extra_logq)), "u", u.device)
+    f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+    i64 = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    if E == 0:
+        extra = extra_ids = extra_logq = None
+    return B, E, D, extra, i64(ids), i64(extra_ids), f32(logq), f32(extra_logq), f32(pos_logq)
+
+
+def inbatch_softmax_plan(B: int, E: int, D: int) -> dict:
+    """How the three launches cut a shape (host only): pieces of the walked side and column slabs of the forward, dU and the columns'
+    gradient (dp over dx) - `softmax_full_plan(B, B + E, D)`."""
+    import ctypes as C
+    out = (C.c_int64 * 6)()
+    _lib.check(_lib.load().ngcf_inbatch_softmax_plan(int(B), int(E), int(D), out))
+    return {"forward": (out[0], out[1]), "du": (out[2], out[3]), "dcolumns": (out[4], out[5])}
+
+
+def inbatch_softmax_loss(u: torch.Tensor, p: torch.Tensor, inv_tau: float, weight_decay: float, batch_size: float, ws: Workspace, *,
+                         ids: Optional[torch.Tensor] = None, logq: Optional[torch.Tensor] = None,
+                         pos_logq: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None,
+                         extra_ids: Optional[torch.Tensor] = None, extra_logq: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`(loss, lse)` of the softmax with shared (in-batch) negatives: `u` [B, D] user rows and `p` [B, D] their positives' rows,
+    `extra` [E, D] further rows that every row of the batch takes as negatives (float32, unit inner stride, any row stride).  The
+    columns are c_j = p_j (j < B), then the extras; `ids` [B] / `extra_ids` [E] int64 are their item ids, `logq` [B] / `extra_logq`
+    [E] their corrections, `pos_logq` [B] the diagonal's (float32 or float64; None is exactly 0).  With plain scores
+    s_bj = <u_b, c_j> * inv_tau: z_bb = s_bb - pos_logq[b], z_bj = s_bj - q_j off the diagonal; with `ids`, a column j != b whose id is
+    ids[b] is a false negative and leaves row b's softmax.  `lse` [B] is the logsumexp of a row's unmasked z, the loss
+    (sum_b (lse_b - z_bb) + weight_decay (|u|^2 + |p|^2)) / batch_size as a 0-dim device tensor - the extras are not regularised.
+    No [B, B + E] matrix exists.  Ids are only compared, never an index.  Without ids and corrections it is
+    `softmax_full_loss(u, cat(p, extra), arange(B), ...)` bit for bit."""
+    B, E, D, x, ids, xids, logq, xlogq, pos_logq = _inbatch_operands("inbatch_softmax_loss", u, p, inv_tau, ids, logq, pos_logq, extra,
+                                                                     extra_ids, extra_logq)
+    dev = u.device
+    lib = _lib.load()
+    w = ws.get(int(lib.ngcf_inbatch_softmax_workspace_bytes(B, E, D)), dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(lib.ngcf_inbatch_softmax_f32(_ptr(u), _ld(u), B, _ptr(p), _ld(p), _ptr(x), _ld(x) if E else D, E, D, _ptr(ids),
+                                                _ptr(xids), _ptr(logq), _ptr(xlogq), _ptr(pos_logq), float(inv_tau), float(weight_decay),
+                                                float(batch_size), _ptr(loss), _ptr(lse), _ptr(w), w.numel(), _stream()))
+    return loss, lse
+
+
+def inbatch_softmax_backward(u: torch.Tensor, p: torch.Tensor, inv_tau: float, weight_decay: float, batch_size: float, lse: torch.Tensor,
+                             grad_out: torch.Tensor, ws: Workspace, need_u: bool = True, need_p: bool = True, need_extra: bool = True, *,
+                             ids: Optional[torch.Tensor] = None, logq: Optional[torch.Tensor] = None,
+                             pos_logq: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None,
+                             extra_ids: Optional[torch.Tensor] = None, extra_logq: Optional[torch.Tensor] = None
+                             ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """`(du, dp, dx)` of `inbatch_softmax_loss` times the upstream scalar `grad_out` (one float32 on the device), from the `lse` the
+    forward returned: the scores are recomputed, two launches of one kernel with the roles swapped.  A gradient that is not needed
+    (`need_u` / `need_p` / `need_extra` False) is not stored and comes back as None, and so does `dx` without extras; the others
+    keep their bits.  The ids and corrections carry no gradient."""
+    fn = "inbatch_softmax_backward"
+    B, E, D, x, ids, xids, logq, xlogq, pos_logq = _inbatch_operands(fn, u, p, inv_tau, ids, logq, pos_logq, extra, extra_ids, extra_logq)
+    dev = u.device
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or lse.device != dev or not lse.is_contiguous():
+        raise ValueError(f"{fn}: lse must be a contiguous float32 tensor of {B} elements on {dev}")
+    _require_grad_out(fn, grad_out, dev)
+    need_extra = bool(need_extra) and E > 0
+    if not (need_u or need_p or need_extra):
+        return None, None, None
+    lib = _lib.load()
+    w = ws.get(int(lib.ngcf_inbatch_softmax_workspace_bytes(B, E, D)), dev)
+    du = torch.empty((B, D), dtype=torch.float32, device=dev) if need_u else None
+    dp = torch.empty((B, D), dtype=torch.float32, device=dev) if need_p else None
+    dx = torch.empty((E, D), dtype=torch.float32, device=dev) if need_extra else None
+    with _on(dev):
+        _lib.check(lib.ngcf_inbatch_softmax_backward_f32(_ptr(u), _ld(u), B, _ptr(p), _ld(p), _ptr(x), _ld(x) if E else D, E, D, _ptr(ids),
+                                                         _ptr(xids), _ptr(logq), _ptr(xlogq), _ptr(pos_logq), _ptr(lse), float(inv_tau),
+                                                         float(weight_decay), float(batch_size), _ptr(grad_out), _ptr(du), D, _ptr(dp), D,
+                                                         _ptr(dx), D, _ptr(w), w.numel(), _stream()))
+    return du, dp, dx

@@ -102,7 +102,7 @@ test_candidates.__test__ = False          # a public name of the reference's voc
 
 
 class _EpochLoader:
-    """What the five loaders share: the columns' validation, the id table `[columns, n]` (int64; its last rows are the items and,
+    """What the six loaders share: the columns' validation, the id table `[columns, n]` (int64; its last rows are the items and,
     with one negative per row, the negatives), `len()`, the epoch counter and the one permutation and gather per `iter()`.  A
     loader is a constructor and `_draw`, which fills this epoch's negatives: the table's last row, or `self.neg` int64 [n, m] where a
     row has m of them (None otherwise), which is gathered by the same permutation - and so is `self.logq`, a float array [n, m]
@@ -354,3 +354,41 @@ class LogQNegativesLoader(WeightedNegativesLoader):
                                                       out=self.neg)
         left = mass[:, None] - (torch.cumsum(w, 1) - w)                                     # U_j, exact in int64
         self.logq = torch.log(w.to(torch.float64) / left.to(torch.float64)).to(torch.float32)
+
+
+# ---- shared (in-batch) negatives: no sampler, the batch's own positives (bprloss.InBatchSoftmax) ---------------------------------------
+def item_logq(items: torch.Tensor, n_item: int) -> torch.Tensor:
+    """The logQ table of in-batch negatives, float32 [n_item] on the tensor's device: log(count_i / T) for the T ids of `items` (the
+    positives' item column; ids in [0, n_item)), the log of the chance that a row of a batch carries item i - formed in float64 from
+    the exact integer counts, then cast once.  An item that never occurs gets -inf: it is never a batch column, and it MUST NOT be
+    drawn as an extra under this table (a correction of -inf makes its z +inf); give drawn extras their own proposal's log
+    probability, e.g. -log(n_item) for `torch.randint`.  Plain torch: it runs wherever `items` lives."""
+    n_item = int(n_item)
+    if items.dim() != 1 or items.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"item_logq: items must be an integer [T] tensor, got {items.dtype} {tuple(items.shape)}")
+    if n_item < 1 or items.numel() < 1:
+        raise ValueError(f"item_logq: n_item={n_item}, {items.numel()} ids")
+    if int(items.min()) < 0 or int(items.max()) >= n_item:
+        raise IndexError(f"item_logq: an item id lies outside [0, {n_item})")
+    counts = torch.bincount(items.to(torch.int64), minlength=n_item)
+    return torch.log(counts.to(torch.float64) / float(items.numel())).to(torch.float32)
+
+
+class InBatchLoader(_EpochLoader):
+    """`TripletLoader` without negatives, for an `InBatchSoftmax` criterion: the batch protocol, `columns`, `shuffle`, `drop_last` and
+    `generator` are `TripletLoader`'s, and a batch is `(*columns[b], items[b])` - with `logq`, a float [n_item] table per item
+    (`item_logq(items, n_item)`), followed by `logq[items[b]]` as float32, the column corrections of the batch.  The table is read
+    once, at construction; every `iter()` draws one `torch.randperm` by which the id table and the corrections are gathered once
+    each, and the batches are views.  Drawing extra shared negatives stays with the caller."""
+
+    def __init__(self, users: torch.Tensor, items: torch.Tensor, columns: Sequence[torch.Tensor] = (), *, batch_size: int,
+                 logq: Optional[torch.Tensor] = None, shuffle: bool = True, drop_last: bool = True,
+                 generator: Optional[torch.Generator] = None):
+        super().__init__("InBatchLoader", users, columns, (items,), batch_size=batch_size, shuffle=shuffle, drop_last=drop_last,
+                         generator=generator)
+        if logq is not None:
+            if logq.dim() != 1 or not logq.is_floating_point():
+                raise ValueError(f"InBatchLoader: logq must be a float [n_item] table, got {logq.dtype} {tuple(logq.shape)}")
+            if logq.device != users.device:
+                raise RuntimeError(f"InBatchLoader: logq is on {logq.device}, users on {users.device}")
+            self.logq = logq[self.table[-1]].to(torch.float32)                  # [n]: row t's column correction
