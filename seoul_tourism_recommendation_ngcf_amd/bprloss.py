@@ -11,18 +11,27 @@ import torch
 import torch.nn as nn
 
 from . import engine as _eng
-from .autograd import BPRLoss, BPRMultiLoss, InBatchSoftmaxLoss, SampledSoftmaxLoss, SoftmaxFullLoss
+from .loss_functions import BPRLoss, BPRMultiLoss, InBatchSoftmaxLoss, SampledSoftmaxLoss, SoftmaxFullLoss
+
+
+def _require_temperature(name, temperature) -> float:
+    t = float(temperature)
+    if not (t > 0 and t < float("inf")):
+        raise ValueError(f"{name}: temperature={temperature} is not a positive finite number")
+    return t
+
+
+def _needs_grad(*rows) -> bool:                  # (can a gradient flow into an operand?  Then the module applies its Function)
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in rows)
 
 
 class BPR(nn.Module):
     def __init__(self, weight_decay, batch_size):
         super().__init__()
-        self.weight_decay = weight_decay
-        self.batch_size = batch_size
-        self._ws = _eng.Workspace()
+        self.weight_decay, self.batch_size, self._ws = weight_decay, batch_size, _eng.Workspace()
 
     def forward(self, u_idx, pos_idx, neg_idx):
-        if torch.is_grad_enabled() and (u_idx.requires_grad or pos_idx.requires_grad or neg_idx.requires_grad):
+        if _needs_grad(u_idx, pos_idx, neg_idx):
             return BPRLoss.apply(u_idx, pos_idx, neg_idx, self.weight_decay, self.batch_size, self._ws)
         return _eng.bpr_loss(u_idx.detach(), pos_idx.detach(), neg_idx.detach(), self.weight_decay,
                              self.batch_size, self._ws)
@@ -39,18 +48,13 @@ class BPRMulti(nn.Module):
 
     def __init__(self, weight_decay, batch_size, m, reduction="mean"):
         super().__init__()
-        if int(m) != m or m < 1 or m > _eng.losses.M_MAX:
-            raise ValueError(f"BPRMulti: m={m} outside [1, {_eng.losses.M_MAX}]")
+        self.m = _eng.losses._require_m("BPRMulti", m)
         if reduction not in _eng.losses.REDUCTIONS:
             raise ValueError(f"BPRMulti: reduction={reduction!r} is not one of {sorted(_eng.losses.REDUCTIONS)}")
-        self.weight_decay = weight_decay
-        self.batch_size = batch_size
-        self.m = int(m)
-        self.reduction = reduction
-        self._ws = _eng.Workspace()
+        self.weight_decay, self.batch_size, self.reduction, self._ws = weight_decay, batch_size, reduction, _eng.Workspace()
 
     def forward(self, u_idx, pos_idx, neg_idx):
-        if torch.is_grad_enabled() and (u_idx.requires_grad or pos_idx.requires_grad or neg_idx.requires_grad):
+        if _needs_grad(u_idx, pos_idx, neg_idx):
             return BPRMultiLoss.apply(u_idx, pos_idx, neg_idx, self.m, self.weight_decay, self.batch_size, self._ws, self.reduction)
         return _eng.losses.bpr_multi_loss(u_idx.detach().contiguous(), pos_idx.detach().contiguous(), neg_idx.detach().contiguous(),
                                           self.m, self.weight_decay, self.batch_size, self._ws, self.reduction)
@@ -73,20 +77,12 @@ class SampledSoftmax(nn.Module):
 
     def __init__(self, weight_decay, batch_size, m, temperature=1.0):
         super().__init__()
-        if int(m) != m or m < 1 or m > _eng.losses.M_MAX:
-            raise ValueError(f"SampledSoftmax: m={m} outside [1, {_eng.losses.M_MAX}]")
-        t = float(temperature)
-        if not (t > 0 and t < float("inf")):
-            raise ValueError(f"SampledSoftmax: temperature={temperature} is not a positive finite number")
-        self.weight_decay = weight_decay
-        self.batch_size = batch_size
-        self.m = int(m)
-        self.temperature = t
-        self._ws = _eng.Workspace()
+        self.m, self.temperature = _eng.losses._require_m("SampledSoftmax", m), _require_temperature("SampledSoftmax", temperature)
+        self.weight_decay, self.batch_size, self._ws = weight_decay, batch_size, _eng.Workspace()
 
     def forward(self, u_idx, pos_idx, neg_idx, logq, pos_logq=None):
         inv_tau = 1.0 / self.temperature
-        if torch.is_grad_enabled() and (u_idx.requires_grad or pos_idx.requires_grad or neg_idx.requires_grad):
+        if _needs_grad(u_idx, pos_idx, neg_idx):
             return SampledSoftmaxLoss.apply(u_idx, pos_idx, neg_idx, logq, pos_logq, self.m, inv_tau, self.weight_decay, self.batch_size,
                                             self._ws)
         return _eng.losses.sampled_softmax_loss(u_idx.detach().contiguous(), pos_idx.detach().contiguous(), neg_idx.detach().contiguous(),
@@ -115,18 +111,12 @@ class SoftmaxFull(nn.Module):
 
     def __init__(self, weight_decay, batch_size, temperature=1.0, check_indices=True):
         super().__init__()
-        t = float(temperature)
-        if not (t > 0 and t < float("inf")):
-            raise ValueError(f"SoftmaxFull: temperature={temperature} is not a positive finite number")
-        self.weight_decay = weight_decay
-        self.batch_size = batch_size
-        self.temperature = t
-        self.check_indices = bool(check_indices)
-        self.status = None
-        self._ws = _eng.Workspace()
+        self.temperature = _require_temperature("SoftmaxFull", temperature)
+        self.weight_decay, self.batch_size, self._ws = weight_decay, batch_size, _eng.Workspace()
+        self.check_indices, self.status = bool(check_indices), None
 
     def forward(self, u_embeds, pos_item, item_table):
-        grad = torch.is_grad_enabled() and (u_embeds.requires_grad or item_table.requires_grad)
+        grad = _needs_grad(u_embeds, item_table)
         if grad and u_embeds.requires_grad and item_table.grad_fn is None and not item_table.requires_grad:
             raise RuntimeError("SoftmaxFull: item_table carries no gradient although u_embeds does - a forward replayed from the "
                                "captured training graphs returns a detached model.all_items_emb; set model.auto_train_graph = False "
@@ -175,23 +165,16 @@ class InBatchSoftmax(nn.Module):
 
     def __init__(self, weight_decay, batch_size, temperature=1.0):
         super().__init__()
-        t = float(temperature)
-        if not (t > 0 and t < float("inf")):
-            raise ValueError(f"InBatchSoftmax: temperature={temperature} is not a positive finite number")
-        self.weight_decay = weight_decay
-        self.batch_size = batch_size
-        self.temperature = t
-        self._ws = _eng.Workspace()
+        self.temperature = _require_temperature("InBatchSoftmax", temperature)
+        self.weight_decay, self.batch_size, self._ws = weight_decay, batch_size, _eng.Workspace()
 
     def forward(self, u, pos, item_ids=None, logq=None, pos_logq=None, extra=None, extra_ids=None, extra_logq=None):
         inv_tau = 1.0 / self.temperature
         if extra is not None and extra.shape[0] == 0:
             extra = extra_ids = extra_logq = None
-        if torch.is_grad_enabled() and (u.requires_grad or pos.requires_grad or (extra is not None and extra.requires_grad)):
+        if _needs_grad(u, pos, extra):
             return InBatchSoftmaxLoss.apply(u, pos, extra, item_ids, logq, pos_logq, extra_ids, extra_logq, inv_tau, self.weight_decay,
                                             self.batch_size, self._ws)
-        loss, _ = _eng.losses.inbatch_softmax_loss(u.detach(), pos.detach(), inv_tau, self.weight_decay, self.batch_size, self._ws,
-                                                   ids=item_ids, logq=logq, pos_logq=pos_logq,
-                                                   extra=None if extra is None else extra.detach(), extra_ids=extra_ids,
-                                                   extra_logq=extra_logq)
-        return loss
+        return _eng.losses.inbatch_softmax_loss(u.detach(), pos.detach(), inv_tau, self.weight_decay, self.batch_size, self._ws,
+                                                ids=item_ids, logq=logq, pos_logq=pos_logq, extra=None if extra is None else extra.detach(),
+                                                extra_ids=extra_ids, extra_logq=extra_logq)[0]

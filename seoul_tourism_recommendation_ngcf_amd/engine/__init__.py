@@ -3,6 +3,7 @@
 Everything here hands `tensor.data_ptr()` + the current HIP stream to libngcf_hip.so.  torch is used for device memory and
 streams only; no tensor arithmetic of the hot path happens in torch.  Importing the package neither loads the library nor touches
 the device: `_lib.load()` runs inside the calls.  Callers reach every name below, the private ones included, as `engine.<name>`;
+the backward pass (csrc/bwd_dense.hip, csrc/bwd_gather.hip: `engine.backward.<name>`, and `engine.layers.bpr_backward` next to `bpr_loss`),
 the trip-context family (csrc/context.hip), the delimited-text family (csrc/text.hip), the optimizer step (csrc/adam.hip), the exact
 held-out positions (csrc/rank_position.hip), the hard and the popularity-weighted negatives (csrc/sample_hard.hip, csrc/sample_weighted.hip), the loss against m negatives per positive
 (csrc/bpr_multi.hip) and the beyond-accuracy list figures with the diversifying re-rank (csrc/list_quality.hip, csrc/list_rerank.hip) keep their modules' names: `engine.context.<name>`,
@@ -12,7 +13,7 @@ held-out positions (csrc/rank_position.hip), the hard and the popularity-weighte
 import ctypes as C  # noqa: F401  (NGCF.py builds its pointers with `engine.C`)
 
 from .. import _lib  # noqa: F401
-from . import context, lists, losses, negatives, optim, ranks, text  # noqa: F401
+from . import backward, context, layers, lists, losses, negatives, optim, ranks, text  # noqa: F401
 from ._plumbing import Workspace, _device_view, _f32c, _on, _ptr, _require_device, _row_major_ld, _stream
 from .csr import LaplacianCSR, shard_plan
 from .groupby import (DECIMAL_MAX_CHARS, GROUPBY_FULL, GROUPBY_LDS_SLOTS, GROUPBY_LOST, GROUPBY_MAX_KEYS, GROUPBY_MAX_VALUES,

@@ -243,3 +243,15 @@ def bpr_loss(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, weight_decay: fl
                                           float(weight_decay), float(batch_size), _ptr(loss), _ptr(w), w.numel(),
                                           _stream()))
     return loss
+
+
+def bpr_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, weight_decay: float, batch_size: float, grad_out: torch.Tensor):
+    """(du, dp, dn) of `bpr_loss` times the upstream scalar `grad_out`, through ngcf_bpr_backward_f32."""
+    lib = _lib.load()
+    u, p, n = u.contiguous(), p.contiguous(), n.contiguous()
+    du, dp, dn = torch.empty_like(u), torch.empty_like(p), torch.empty_like(n)
+    g = grad_out.to(torch.float32).contiguous()
+    with _on(u.device):
+        _lib.check(lib.ngcf_bpr_backward_f32(_ptr(u), u.shape[0], _ptr(p), p.shape[0], _ptr(n), n.shape[0], u.shape[1],
+                                             float(weight_decay), float(batch_size), _ptr(g), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
+    return du, dp, dn

@@ -18,19 +18,77 @@ M_MAX = 64                                       # NGCF_BPR_MULTI_M_MAX: lane j 
 REDUCTIONS = {"mean": 0, "softmax": 1}           # NGCF_BPR_MULTI_MEAN, NGCF_BPR_MULTI_SOFTMAX
 
 
+# ---- stated once for several calls (`fn`, `pairs`: as in `_plumbing`); the order of refusals in the `_*operands` below is behaviour
+def _require_m(fn: str, m) -> int:
+    if int(m) != m or m < 1 or m > M_MAX:
+        raise ValueError(f"{fn}: m={m} outside [1, {M_MAX}]")
+    return int(m)
+
+
+def _rows_cols(fn: str, pairs) -> Tuple[int, int]:
+    """Every table of `pairs` is 2-D; (B, D) of the first, `u`, neither of them 0."""
+    for nm, t in pairs:
+        if t is not None and t.dim() != 2:
+            raise ValueError(f"{fn}: {nm} must be 2-D, got shape {tuple(t.shape)}")
+    u = pairs[0][1]
+    B, D = int(u.shape[0]), int(u.shape[1])
+    if B < 1 or D < 1:
+        raise ValueError(f"{fn}: u is {tuple(u.shape)}: at least one row and one column expected")
+    return B, D
+
+
+def _require_rows(fn: str, pairs) -> None:
+    """The strided layout of the full and in-batch calls' 2-D float32 tables (dimensions and types: refused before, with the sizes)."""
+    for nm, t in pairs:
+        if t is not None and t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError(f"{fn}: {nm} must have unit stride in its last dimension, got strides {t.stride()}")
+        if t is not None and t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+            raise ValueError(f"{fn}: the rows of {nm} overlap, strides {t.stride()}")
+
+
+def _require_corrections(fn: str, pairs) -> None:
+    for nm, t in pairs:
+        if t is not None and t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{fn}: {nm} must be float32 or float64, got {t.dtype}")
+
+
+def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:     # (a correction as the kernels read it: the one cast per call)
+    return None if t is None else t.to(torch.float32).contiguous()
+
+
+def _require_inv_tau(fn: str, inv_tau: float) -> None:
+    if not (inv_tau > 0 and inv_tau < float("inf")):
+        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+
+
+def _require_lse(fn: str, lse: torch.Tensor, B: int, dev, nm: str = "lse") -> None:
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or lse.device != dev or not lse.is_contiguous():
+        raise ValueError(f"{fn}: {nm} must be a contiguous float32 tensor of {B} elements on {dev}")
+
+
+def _plan(entry: str, *shape: int):                                 # (the three (pieces, slabs) pairs of a host-only plan entry)
+    import ctypes as C
+    out = (C.c_int64 * 6)()
+    _lib.check(getattr(_lib.load(), entry)(*(int(x) for x in shape), out))
+    return (out[0], out[1]), (out[2], out[3]), (out[4], out[5])
+
+
+def _launch(dev, entry, *args) -> None:                             # (`entry(*args, stream)` on `dev`, checked)
+    with _on(dev):
+        _lib.check(entry(*args, _stream()))
+
+
+def _empty(dev, *shape: int, need: bool = True) -> Optional[torch.Tensor]:      # (an output; None for a gradient nobody needs)
+    return torch.empty(shape, dtype=torch.float32, device=dev) if need else None
+
+
 def _operands(fn: str, u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int, reduction: str) -> Tuple[int, int, int]:
     """The refusals of both calls, before anything reaches the device: (B, D, the reduction's code)."""
     if reduction not in REDUCTIONS:
         raise ValueError(f"{fn}: reduction={reduction!r} is not one of {sorted(REDUCTIONS)}")
-    if int(m) != m or m < 1 or m > M_MAX:
-        raise ValueError(f"{fn}: m={m} outside [1, {M_MAX}]")
+    _require_m(fn, m)
     pairs = (("u", u), ("pos", p), ("neg", n))
-    for nm, t in pairs:
-        if t.dim() != 2:
-            raise ValueError(f"{fn}: {nm} must be 2-D, got shape {tuple(t.shape)}")
-    B, D = int(u.shape[0]), int(u.shape[1])
-    if B < 1 or D < 1:
-        raise ValueError(f"{fn}: u is {tuple(u.shape)}: at least one row and one column expected")
+    B, D = _rows_cols(fn, pairs)
     if tuple(p.shape) != (B, D) or tuple(n.shape) != (B * int(m), D):
         raise ValueError(f"{fn}: u {tuple(u.shape)}, pos {tuple(p.shape)} and neg {tuple(n.shape)} are not [B, D], [B, D] and "
                          f"[B*m, D] with m={m} (no operand broadcasts)")
@@ -44,7 +102,6 @@ def _operands(fn: str, u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int
 
 
 def _require_grad_out(fn: str, grad_out: torch.Tensor, device: torch.device) -> None:
-    """The upstream gradient of a scalar loss, as every backward here takes it."""
     if grad_out.numel() != 1 or grad_out.dtype != torch.float32 or grad_out.device != device:
         raise ValueError(f"{fn}: grad_out must be one float32 on {device}")
 
@@ -59,10 +116,9 @@ def bpr_multi_loss(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int, we
     B, D, red = _operands("bpr_multi_loss", u, p, n, m, reduction)
     lib = _lib.load()
     w = ws.get(int(lib.ngcf_bpr_multi_workspace_bytes(B)), u.device)
-    loss = torch.empty((), dtype=torch.float32, device=u.device)
-    with _on(u.device):
-        _lib.check(lib.ngcf_bpr_multi_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, red, float(weight_decay),
-                                          float(batch_size), _ptr(loss), _ptr(w), w.numel(), _stream()))
+    loss = _empty(u.device)
+    _launch(u.device, lib.ngcf_bpr_multi_f32, _ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, red, float(weight_decay),
+            float(batch_size), _ptr(loss), _ptr(w), w.numel())
     return loss
 
 
@@ -74,9 +130,8 @@ def bpr_multi_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, m: int
     _require_grad_out("bpr_multi_backward", grad_out, u.device)
     lib = _lib.load()
     du, dp, dn = torch.empty_like(u), torch.empty_like(p), torch.empty_like(n)
-    with _on(u.device):
-        _lib.check(lib.ngcf_bpr_multi_backward_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, red, float(weight_decay),
-                                                   float(batch_size), _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
+    _launch(u.device, lib.ngcf_bpr_multi_backward_f32, _ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, red, float(weight_decay),
+            float(batch_size), _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn))
     return du, dp, dn
 
 
@@ -92,15 +147,11 @@ def _corrections(fn: str, u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, log
             raise ValueError(f"{fn}: logq must be [B, m] or [B*m] with B={rows}, m={m}, got shape {tuple(logq.shape)}")
         if pos_logq is not None and tuple(pos_logq.shape) != (rows,):
             raise ValueError(f"{fn}: pos_logq must be [B] with B={rows}, got shape {tuple(pos_logq.shape)}")
-    for nm, t in (("logq", logq), ("pos_logq", pos_logq)):
-        if t is not None and t.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{fn}: {nm} must be float32 or float64, got {t.dtype}")
-    if not (inv_tau > 0 and inv_tau < float("inf")):
-        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+    _require_corrections(fn, (("logq", logq), ("pos_logq", pos_logq)))
+    _require_inv_tau(fn, inv_tau)
     B, D, _ = _operands(fn, u, p, n, m, "softmax")
     _require_same_device(fn, (("logq", logq), ("pos_logq", pos_logq)), "u", u.device)
-    logq = logq.to(torch.float32).reshape(-1).contiguous()
-    return B, D, logq, None if pos_logq is None else pos_logq.to(torch.float32).contiguous()
+    return B, D, _f32(logq.reshape(-1)), _f32(pos_logq)
 
 
 def sampled_softmax_loss(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, logq: torch.Tensor, m: int, inv_tau: float,
@@ -117,11 +168,9 @@ def sampled_softmax_loss(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, logq
     B, D, logq, pos_logq = _corrections("sampled_softmax_loss", u, p, n, logq, pos_logq, m, inv_tau)
     lib = _lib.load()
     w = ws.get(int(lib.ngcf_sampled_softmax_workspace_bytes(B)), u.device)
-    loss = torch.empty((), dtype=torch.float32, device=u.device)
-    with _on(u.device):
-        _lib.check(lib.ngcf_sampled_softmax_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, _ptr(logq), _ptr(pos_logq),
-                                                float(inv_tau), float(weight_decay), float(batch_size), _ptr(loss), _ptr(w), w.numel(),
-                                                _stream()))
+    loss = _empty(u.device)
+    _launch(u.device, lib.ngcf_sampled_softmax_f32, _ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, _ptr(logq), _ptr(pos_logq),
+            float(inv_tau), float(weight_decay), float(batch_size), _ptr(loss), _ptr(w), w.numel())
     return loss
 
 
@@ -134,42 +183,31 @@ def sampled_softmax_backward(u: torch.Tensor, p: torch.Tensor, n: torch.Tensor, 
     _require_grad_out("sampled_softmax_backward", grad_out, u.device)
     lib = _lib.load()
     du, dp, dn = torch.empty_like(u), torch.empty_like(p), torch.empty_like(n)
-    with _on(u.device):
-        _lib.check(lib.ngcf_sampled_softmax_backward_f32(_ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, _ptr(logq),
-                                                         _ptr(pos_logq), float(inv_tau), float(weight_decay), float(batch_size),
-                                                         _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn), _stream()))
+    _launch(u.device, lib.ngcf_sampled_softmax_backward_f32, _ptr(u), B, _ptr(p), B, _ptr(n), B * int(m), int(m), D, _ptr(logq),
+            _ptr(pos_logq), float(inv_tau), float(weight_decay), float(batch_size), _ptr(grad_out), _ptr(du), _ptr(dp), _ptr(dn))
     return du, dp, dn
 
 
 # ---- the softmax over the whole catalogue (`ngcf_softmax_full_f32` / `ngcf_softmax_full_backward_f32`: csrc/softmax_full.hip) ------
 def _full_operands(fn: str, u: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, inv_tau: float) -> Tuple[int, int, int]:
-    """The refusals of both full-catalogue calls, before anything reaches the device: (B, n_items, D)."""
-    for nm, t in (("u", u), ("items", items)):
-        if t.dim() != 2:
-            raise ValueError(f"{fn}: {nm} must be 2-D, got shape {tuple(t.shape)}")
+    """The refusals of both full-catalogue calls, before anything reaches the device: (B, n_items, D, pos contiguous)."""
+    rows = (("u", u), ("items", items))
+    (B, D), n_items = _rows_cols(fn, rows), int(items.shape[0])
     if pos.dim() != 1:
         raise ValueError(f"{fn}: pos must be 1-D, got shape {tuple(pos.shape)}")
-    B, D, n_items = int(u.shape[0]), int(u.shape[1]), int(items.shape[0])
-    if B < 1 or D < 1:
-        raise ValueError(f"{fn}: u is {tuple(u.shape)}: at least one row and one column expected")
     if n_items < 1:
         raise ValueError(f"{fn}: items is {tuple(items.shape)}: at least one item expected")
     if int(items.shape[1]) != D:
         raise ValueError(f"{fn}: u {tuple(u.shape)} and items {tuple(items.shape)} differ in width")
     if int(pos.shape[0]) != B:
         raise ValueError(f"{fn}: pos has {int(pos.shape[0])} ids for {B} rows of u")
-    _require_dtype(fn, torch.float32, (("u", u), ("items", items)))
+    _require_dtype(fn, torch.float32, rows)
     _require_dtype(fn, torch.int64, (("pos", pos),))
-    for nm, t in (("u", u), ("items", items)):
-        if D > 1 and t.stride(1) != 1:
-            raise ValueError(f"{fn}: {nm} must have unit stride in its last dimension, got strides {t.stride()}")
-        if int(t.shape[0]) > 1 and t.stride(0) < D:
-            raise ValueError(f"{fn}: the rows of {nm} overlap, strides {t.stride()}")
-    if not (inv_tau > 0 and inv_tau < float("inf")):
-        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+    _require_rows(fn, rows)
+    _require_inv_tau(fn, inv_tau)
     _require_device(u, "u")
     _require_same_device(fn, (("items", items), ("pos", pos)), "u", u.device)
-    return B, n_items, D
+    return B, n_items, D, pos.contiguous()
 
 
 def _ld(t: torch.Tensor) -> int:
@@ -178,10 +216,7 @@ def _ld(t: torch.Tensor) -> int:
 
 def softmax_full_plan(B: int, n_items: int, D: int) -> dict:
     """How the three launches cut a shape (host only): pieces of the walked side and column slabs of the forward, dU and dI."""
-    import ctypes as C
-    out = (C.c_int64 * 6)()
-    _lib.check(_lib.load().ngcf_softmax_full_plan(int(B), int(n_items), int(D), out))
-    return {"forward": (out[0], out[1]), "du": (out[2], out[3]), "ditems": (out[4], out[5])}
+    return dict(zip(("forward", "du", "ditems"), _plan("ngcf_softmax_full_plan", B, n_items, D)))
 
 
 def softmax_full_loss(u: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, inv_tau: float, weight_decay: float, batch_size: float,
@@ -193,22 +228,18 @@ def softmax_full_loss(u: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, i
     [B, n_items] matrix exists.  An id of `pos` outside the catalogue is never an index: its row has no positive term and bit 0 of
     `status` (an int32 device word, sticky; None: a word nobody reads) is set - no check here costs a host sync.  `spos` [B]
     float32, when given, receives the positives' scores."""
-    B, n_items, D = _full_operands("softmax_full_loss", u, items, pos, inv_tau)
+    B, n_items, D, pos = _full_operands("softmax_full_loss", u, items, pos, inv_tau)
     dev = u.device
     status, _ = _status_word("softmax_full_loss", status, dev)
     if spos is None:
-        spos = torch.empty(B, dtype=torch.float32, device=dev)
-    elif spos.dtype != torch.float32 or tuple(spos.shape) != (B,) or spos.device != dev or not spos.is_contiguous():
-        raise ValueError(f"softmax_full_loss: spos must be a contiguous float32 tensor of {B} elements on {dev}")
+        spos = _empty(dev, B)
+    else:
+        _require_lse("softmax_full_loss", spos, B, dev, "spos")
     lib = _lib.load()
     w = ws.get(int(lib.ngcf_softmax_full_workspace_bytes(B, n_items, D)), dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    lse = torch.empty(B, dtype=torch.float32, device=dev)
-    pos = pos.contiguous()
-    with _on(dev):
-        _lib.check(lib.ngcf_softmax_full_f32(_ptr(u), _ld(u), B, _ptr(items), _ld(items), n_items, D, _ptr(pos), float(inv_tau),
-                                             float(weight_decay), float(batch_size), _ptr(loss), _ptr(lse), _ptr(spos), _ptr(status),
-                                             _ptr(w), w.numel(), _stream()))
+    loss, lse = _empty(dev), _empty(dev, B)
+    _launch(dev, lib.ngcf_softmax_full_f32, _ptr(u), _ld(u), B, _ptr(items), _ld(items), n_items, D, _ptr(pos), float(inv_tau),
+            float(weight_decay), float(batch_size), _ptr(loss), _ptr(lse), _ptr(spos), _ptr(status), _ptr(w), w.numel())
     return loss, lse
 
 
@@ -218,22 +249,17 @@ def softmax_full_backward(u: torch.Tensor, items: torch.Tensor, pos: torch.Tenso
     """`(du, ditems)` of `softmax_full_loss` times the upstream scalar `grad_out` (one float32 on the device), from the `lse` the
     forward returned: the scores are recomputed, two launches of one kernel with the roles swapped.  `ditems` is dense, [n_items, D]
     contiguous; a gradient that is not needed (`need_u` / `need_items` False) is not computed and comes back as None."""
-    B, n_items, D = _full_operands("softmax_full_backward", u, items, pos, inv_tau)
+    B, n_items, D, pos = _full_operands("softmax_full_backward", u, items, pos, inv_tau)
     dev = u.device
-    if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or lse.device != dev or not lse.is_contiguous():
-        raise ValueError(f"softmax_full_backward: lse must be a contiguous float32 tensor of {B} elements on {dev}")
+    _require_lse("softmax_full_backward", lse, B, dev)
     _require_grad_out("softmax_full_backward", grad_out, dev)
     if not (need_u or need_items):
         return None, None
     lib = _lib.load()
     w = ws.get(int(lib.ngcf_softmax_full_workspace_bytes(B, n_items, D)), dev)
-    du = torch.empty((B, D), dtype=torch.float32, device=dev) if need_u else None
-    di = torch.empty((n_items, D), dtype=torch.float32, device=dev) if need_items else None
-    pos = pos.contiguous()
-    with _on(dev):
-        _lib.check(lib.ngcf_softmax_full_backward_f32(_ptr(u), _ld(u), B, _ptr(items), _ld(items), n_items, D, _ptr(pos), _ptr(lse),
-                                                      float(inv_tau), float(weight_decay), float(batch_size), _ptr(grad_out),
-                                                      _ptr(du), D, _ptr(di), D, _ptr(w), w.numel(), _stream()))
+    du, di = _empty(dev, B, D, need=need_u), _empty(dev, n_items, D, need=need_items)
+    _launch(dev, lib.ngcf_softmax_full_backward_f32, _ptr(u), _ld(u), B, _ptr(items), _ld(items), n_items, D, _ptr(pos), _ptr(lse),
+            float(inv_tau), float(weight_decay), float(batch_size), _ptr(grad_out), _ptr(du), D, _ptr(di), D, _ptr(w), w.numel())
     return du, di
 
 
@@ -243,12 +269,8 @@ def _inbatch_operands(fn: str, u: torch.Tensor, p: torch.Tensor, inv_tau: float,
     sizes (ValueError), types (TypeError), the temperature, the devices (RuntimeError).
     -> (B, E, D, extra or None, ids, extra_ids, logq, extra_logq, pos_logq), the corrections as contiguous float32 (a float64 one is
     cast once, here), the ids contiguous; what goes with the extras is None when there are none."""
-    for nm, t in (("u", u), ("pos", p), ("extra", extra)):
-        if t is not None and t.dim() != 2:
-            raise ValueError(f"{fn}: {nm} must be 2-D, got shape {tuple(t.shape)}")
-    B, D = int(u.shape[0]), int(u.shape[1])
-    if B < 1 or D < 1:
-        raise ValueError(f"{fn}: u is {tuple(u.shape)}: at least one row and one column expected")
+    rows = (("u", u), ("pos", p), ("extra", extra))
+    B, D = _rows_cols(fn, rows)
     if tuple(p.shape) != (B, D):
         raise ValueError(f"{fn}: u {tuple(u.shape)} and pos {tuple(p.shape)} are not both [B, D]")
     E = 0 if extra is None else int(extra.shape[0])
@@ -262,38 +284,24 @@ def _inbatch_operands(fn: str, u: torch.Tensor, p: torch.Tensor, inv_tau: float,
             raise ValueError(f"{fn}: {nm} must be [{of}] with {of}={n}, got shape {tuple(t.shape)}")
     if ids is not None and E > 0 and extra_ids is None:
         raise ValueError(f"{fn}: ids given with {E} extra rows and no extra_ids: the mask needs the extras' ids too")
-    rows = (("u", u), ("pos", p), ("extra", extra))
     _require_dtype(fn, torch.float32, rows)
     _require_dtype(fn, torch.int64, (("ids", ids), ("extra_ids", extra_ids)))
-    for nm, t in (("logq", logq), ("pos_logq", pos_logq), ("extra_logq", extra_logq)):
-        if t is not None and t.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{fn}: {nm} must be float32 or float64, got {t.dtype}")
-    for nm, t in rows:
-        if t is None:
-            continue
-        if D > 1 and t.stride(1) != 1:
-            raise ValueError(f"{fn}: {nm} must have unit stride in its last dimension, got strides {t.stride()}")
-        if int(t.shape[0]) > 1 and t.stride(0) < D:
-            raise ValueError(f"{fn}: the rows of {nm} overlap, strides {t.stride()}")
-    if not (inv_tau > 0 and inv_tau < float("inf")):
-        raise ValueError(f"{fn}: inv_tau={inv_tau} is not a positive finite number")
+    _require_corrections(fn, (("logq", logq), ("pos_logq", pos_logq), ("extra_logq", extra_logq)))
+    _require_rows(fn, rows)
+    _require_inv_tau(fn, inv_tau)
     _require_device(u, "u")
     _require_same_device(fn, (("pos", p), ("extra", extra), ("ids", ids), ("extra_ids", extra_ids), ("logq", logq),
                               ("pos_logq", pos_logq), ("extra_logq", extra_logq)), "u", u.device)
-    f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
     i64 = lambda t: None if t is None else t.contiguous()  # noqa: E731
     if E == 0:
         extra = extra_ids = extra_logq = None
-    return B, E, D, extra, i64(ids), i64(extra_ids), f32(logq), f32(extra_logq), f32(pos_logq)
+    return B, E, D, extra, i64(ids), i64(extra_ids), _f32(logq), _f32(extra_logq), _f32(pos_logq)
 
 
 def inbatch_softmax_plan(B: int, E: int, D: int) -> dict:
     """How the three launches cut a shape (host only): pieces of the walked side and column slabs of the forward, dU and the columns'
     gradient (dp over dx) - `softmax_full_plan(B, B + E, D)`."""
-    import ctypes as C
-    out = (C.c_int64 * 6)()
-    _lib.check(_lib.load().ngcf_inbatch_softmax_plan(int(B), int(E), int(D), out))
-    return {"forward": (out[0], out[1]), "du": (out[2], out[3]), "dcolumns": (out[4], out[5])}
+    return dict(zip(("forward", "du", "dcolumns"), _plan("ngcf_inbatch_softmax_plan", B, E, D)))
 
 
 def inbatch_softmax_loss(u: torch.Tensor, p: torch.Tensor, inv_tau: float, weight_decay: float, batch_size: float, ws: Workspace, *,
@@ -315,12 +323,10 @@ def inbatch_softmax_loss(u: torch.Tensor, p: torch.Tensor, inv_tau: float, weigh
     dev = u.device
     lib = _lib.load()
     w = ws.get(int(lib.ngcf_inbatch_softmax_workspace_bytes(B, E, D)), dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    lse = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on(dev):
-        _lib.check(lib.ngcf_inbatch_softmax_f32(_ptr(u), _ld(u), B, _ptr(p), _ld(p), _ptr(x), _ld(x) if E else D, E, D, _ptr(ids),
-                                                _ptr(xids), _ptr(logq), _ptr(xlogq), _ptr(pos_logq), float(inv_tau), float(weight_decay),
-                                                float(batch_size), _ptr(loss), _ptr(lse), _ptr(w), w.numel(), _stream()))
+    loss, lse = _empty(dev), _empty(dev, B)
+    _launch(dev, lib.ngcf_inbatch_softmax_f32, _ptr(u), _ld(u), B, _ptr(p), _ld(p), _ptr(x), _ld(x) if E else D, E, D, _ptr(ids),
+            _ptr(xids), _ptr(logq), _ptr(xlogq), _ptr(pos_logq), float(inv_tau), float(weight_decay), float(batch_size), _ptr(loss),
+            _ptr(lse), _ptr(w), w.numel())
     return loss, lse
 
 
@@ -337,20 +343,15 @@ def inbatch_softmax_backward(u: torch.Tensor, p: torch.Tensor, inv_tau: float, w
     fn = "inbatch_softmax_backward"
     B, E, D, x, ids, xids, logq, xlogq, pos_logq = _inbatch_operands(fn, u, p, inv_tau, ids, logq, pos_logq, extra, extra_ids, extra_logq)
     dev = u.device
-    if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or lse.device != dev or not lse.is_contiguous():
-        raise ValueError(f"{fn}: lse must be a contiguous float32 tensor of {B} elements on {dev}")
+    _require_lse(fn, lse, B, dev)
     _require_grad_out(fn, grad_out, dev)
     need_extra = bool(need_extra) and E > 0
     if not (need_u or need_p or need_extra):
         return None, None, None
     lib = _lib.load()
     w = ws.get(int(lib.ngcf_inbatch_softmax_workspace_bytes(B, E, D)), dev)
-    du = torch.empty((B, D), dtype=torch.float32, device=dev) if need_u else None
-    dp = torch.empty((B, D), dtype=torch.float32, device=dev) if need_p else None
-    dx = torch.empty((E, D), dtype=torch.float32, device=dev) if need_extra else None
-    with _on(dev):
-        _lib.check(lib.ngcf_inbatch_softmax_backward_f32(_ptr(u), _ld(u), B, _ptr(p), _ld(p), _ptr(x), _ld(x) if E else D, E, D, _ptr(ids),
-                                                         _ptr(xids), _ptr(logq), _ptr(xlogq), _ptr(pos_logq), _ptr(lse), float(inv_tau),
-                                                         float(weight_decay), float(batch_size), _ptr(grad_out), _ptr(du), D, _ptr(dp), D,
-                                                         _ptr(dx), D, _ptr(w), w.numel(), _stream()))
+    du, dp, dx = _empty(dev, B, D, need=need_u), _empty(dev, B, D, need=need_p), _empty(dev, E, D, need=need_extra)
+    _launch(dev, lib.ngcf_inbatch_softmax_backward_f32, _ptr(u), _ld(u), B, _ptr(p), _ld(p), _ptr(x), _ld(x) if E else D, E, D, _ptr(ids),
+            _ptr(xids), _ptr(logq), _ptr(xlogq), _ptr(pos_logq), _ptr(lse), float(inv_tau), float(weight_decay), float(batch_size),
+            _ptr(grad_out), _ptr(du), D, _ptr(dp), D, _ptr(dx), D, _ptr(w), w.numel())
     return du, dp, dx

@@ -19,7 +19,8 @@ import torch
 
 from . import engine as _eng
 from .NGCF import _raise_bad_index
-from .autograd import _static_result_held, propagate_forward, static_result_baseline
+from .all_e import _static_result_held, static_result_baseline
+from .autograd import propagate_forward
 
 
 def _batch_sizes(u_id, age, sex, month, day, dow, pos_item, neg_item):

@@ -5,7 +5,7 @@ import torch
 import torch.distributed as dist
 
 from .. import engine as _eng
-from ..autograd import E0Cache
+from ..all_e import E0Cache
 from .functions import AllGatherRows, DenseLayerFn, ReduceScatterRows, SpmmFn, _SumGrads
 from .p2p import P2PCollectives, sum_slots
 from .partition import ld32
@@ -82,7 +82,7 @@ def propagate_bipartite(sh):
     uwp, iwp = m.user_embedding.weight, m.item_embedding.weight
     # r04: ONE result buffer [nu + ni, D] (users first; the three served gathers then read one table in one launch), and the
     # previous pass's buffer is written again - its block 0 (E0, NGCF.py:120) NOT copied again - while both tables are the same
-    # tensors at the same version and nobody else holds the previous result (autograd.E0Cache.only_the_modules: a caller who
+    # tensors at the same version and nobody else holds the previous result (all_e.E0Cache.only_the_modules: a caller who
     # kept it gets a fresh buffer, as before).  At W = 8 that is the rank's share of the E0 copy per pass (23 us of a 2 ms step).
     e0_tag = (uwp.data_ptr(), int(uwp._version), iwp.data_ptr(), int(iwp._version), tuple(widths), nu, ni)
     cache = sh.__dict__.setdefault("_e0", E0Cache())

@@ -6,7 +6,8 @@ import ctypes as C
 import torch
 import torch.distributed as dist
 
-from .. import _lib, autograd as ag, engine as _eng
+from .. import _lib, engine as _eng
+from ..all_e import _padded_rows
 from .p2p import P2PCollectives
 
 
@@ -125,19 +126,19 @@ class SpmmFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        gp = ag._padded_rows(g.shape[0], g.shape[1], g.device)
+        gp = _padded_rows(g.shape[0], g.shape[1], g.device)
         gp.copy_(g)                                                # 128-byte aligned rows for the gather
         return _eng.spmm(ctx.csr_t, gp, ws=ctx.ws), None, None, None
 
 
 class DenseLayerFn(torch.autograd.Function):
     """(carry, norm) of one layer's dense half (NGCF.py:131-146, eval-mode: no message dropout) for a slab of rows, with the
-    hand-written backward kernels of autograd.py (normalise / LeakyReLU backward, MFMA weight and input gradients)."""
+    hand-written backward kernels of engine.backward (normalise / LeakyReLU backward, MFMA weight and input gradients)."""
 
     @staticmethod
     def forward(ctx, LE, E, W1, b1, W2, b2, ws):
         n, d_out = LE.shape[0], W1.shape[0]
-        carry = ag._padded_rows(n, d_out, LE.device)
+        carry = _padded_rows(n, d_out, LE.device)
         norm = torch.empty((n, d_out), dtype=torch.float32, device=LE.device)
         if n:
             _eng.layer_dense(LE.detach(), E.detach(), W1.detach(), b1.detach(), W2.detach(), b2.detach(), carry, norm, ws)
@@ -152,10 +153,10 @@ class DenseLayerFn(torch.autograd.Function):
         if n == 0:
             z = torch.zeros_like
             return z(LE), z(E), z(W1), W1.new_zeros(W1.shape[0]), z(W2), W2.new_zeros(W2.shape[0]), None
-        dM = ag._bwd_pre(dN.contiguous() if dN is not None else None, dC.contiguous() if dC is not None else None, carry,
+        dM = _eng.backward.bwd_pre(dN.contiguous() if dN is not None else None, dC.contiguous() if dC is not None else None, carry,
                          _eng.LEAKY_SLOPE, 0.0, 0)
-        gW1, gb1, gW2, gb2 = ag._bwd_weight(dM, LE, E, ctx.ws)
-        dLE, dE = ag._bwd_input(dM, W1, W2, LE, E, ctx.ws)
+        gW1, gb1, gW2, gb2 = _eng.backward.bwd_weight(dM, LE, E, ctx.ws)
+        dLE, dE = _eng.backward.bwd_input(dM, W1, W2, LE, E, ctx.ws)
         return dLE, dE, gW1, gb1, gW2, gb2, None
 
 

@@ -8,7 +8,7 @@ from .. import engine as _eng
 
 
 def ld32(d: int) -> int:
-    """Leading dimension of a row of `d` floats padded to a 128-byte line (32 floats), as `autograd._padded_rows` allocates."""
+    """Leading dimension of a row of `d` floats padded to a 128-byte line (32 floats), as `all_e._padded_rows` allocates."""
     return (d + 31) // 32 * 32
 
 

@@ -159,7 +159,7 @@ class ShardedPropagation:
         if self.backend == "cabi":
             self._cabi = _CabiAllGather(group, dev)
 
-    # this rank's rows of all_E (NGCF.py:147-149): stored under the attribute names autograd.E0Cache looks at, so that the same
+    # this rank's rows of all_E (NGCF.py:147-149): stored under the attribute names all_e.E0Cache looks at, so that the same
     # hold detection decides whether the previous pass's buffer may be written again
     allE_u, allE_i = _alias("all_users_emb"), _alias("all_items_emb")
 

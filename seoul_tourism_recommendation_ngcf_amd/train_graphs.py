@@ -15,7 +15,7 @@ import torch
 
 from . import engine as _eng
 from .NGCF import NGCF
-from .autograd import _static_result_held, static_result_baseline
+from .all_e import _static_result_held, static_result_baseline
 from .graphed import _batch_sizes, _graph_key
 
 

@@ -202,7 +202,7 @@ def address(ld, col0, guard=GUARD_ROWS, base=A0):
 
 
 def input_ldm(c):
-    """dM of an input-gradient case: 16-byte aligned rows padded to a multiple of 4 floats (pad4) or of 32 as _bwd_pre makes them."""
+    """dM of an input-gradient case: 16-byte aligned rows padded to a multiple of 4 floats (pad4) or of 32 as engine.backward.bwd_pre makes them."""
     q = 4 if c.ldm == "pad4" else 32
     return (c.d_out + q - 1) // q * q
 
@@ -244,7 +244,7 @@ _W = [
 WEIGHT_CASES = [WCase(*row, seed=100 + i) for i, row in enumerate(_W)]
 WEIGHT_FP64 = [WCase("mfma_aligned", 16423, 65, 100, "padded", "both", 901), WCase("mfma_unaligned", 1000, 33, 65, "odd_LE", "both", 902),
                WCase("narrow", 70001, 3, 100, "padded", "both", 903)]
-WRAPPER_CASES = [(300, 515, 200, 951), (333, 515, 200, 952)]          # autograd._bwd_weight: 2 x 5 blocks of at most 128 x 128
+WRAPPER_CASES = [(300, 515, 200, 951), (333, 515, 200, 952)]          # engine.backward.bwd_weight: 2 x 5 blocks of at most 128 x 128
 
 # input gradient.  panels: the kernel of every panel, in column order; ldm: pad4 | pad32; opts on top of DEFAULTS
 ICase = namedtuple("ICase", "panels n d_in d_out ldm opts seed")

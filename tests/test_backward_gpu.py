@@ -128,7 +128,6 @@ def test_training_step_with_adam_runs_and_lowers_the_loss(dev):
 def test_dropout_backward_matches_autograd_on_the_realised_mask(dev):
     """Message dropout: the backward must use exactly the forward's keep mask (recomputed from the seed)."""
     pkg = _pkg()
-    from seoul_tourism_recommendation_ngcf_amd import autograd as ag
     eng = pkg.engine
     n, d, p = 300, 96, 0.3
     gen = torch.Generator().manual_seed(2)
@@ -140,7 +139,7 @@ def test_dropout_backward_matches_autograd_on_the_realised_mask(dev):
     nb = torch.empty((n, d), device=dev)
     eng.layer_dense(LE.to(dev), E.to(dev), W1.to(dev), b1.to(dev), W2.to(dev), b2.to(dev), carry, nb, eng.Workspace(),
                     drop_p=p, drop_seed=99)
-    dM = ag._bwd_pre(dN.to(dev), dC.to(dev), carry, 0.2, p, 99).cpu()
+    dM = eng.backward.bwd_pre(dN.to(dev), dC.to(dev), carry, 0.2, p, 99).cpu()
     # reference: autograd through leaky -> (mask/(1-p)) -> normalise with the realised mask
     M = (torch.nn.functional.linear(LE, W1, b1) + torch.nn.functional.linear(E, W1, b1)
          + torch.nn.functional.linear(LE * E, W2, b2)).requires_grad_(True)
@@ -198,7 +197,7 @@ def test_weight_gradient_kernel_matches_fp64(n_rows, d_in, d_out, strided, dev):
     """gW = dM^T . [LE+E | LE*E] and gb = column sums of dM (MFMA kernel, csrc/bwd_dense.hip) against fp64 from the definition (NGCF.py:131-136),
     incl. widths that are not multiples of 32 or 4, a row count that is not a multiple of the block, strided operands
     and the empty case.  Summation order differs from any reference GEMM: tolerance, relative to the result's scale."""
-    from seoul_tourism_recommendation_ngcf_amd import autograd, engine
+    from seoul_tourism_recommendation_ngcf_amd import engine
     g = torch.Generator(device=dev).manual_seed(n_rows + d_in)
 
     def mk(n, d, poison=False):     # strided: a column slice of a wider matrix; LE / E with NaN in the other columns
@@ -208,7 +207,7 @@ def test_weight_gradient_kernel_matches_fp64(n_rows, d_in, d_out, strided, dev):
         return t[:, :d]
     dM, LE, E = mk(n_rows, d_out), mk(n_rows, d_in, True), mk(n_rows, d_in, True)
     ws = engine.Workspace()
-    g1, gb1, g2, gb = autograd._bwd_weight(dM, LE, E, ws)
+    g1, gb1, g2, gb = engine.backward.bwd_weight(dM, LE, E, ws)
     assert g1.shape == (d_out, d_in) and g2.shape == (d_out, d_in) and gb.shape == (d_out,)
     got = torch.cat([g1, g2], 1)
     assert torch.equal(gb1, 2.0 * gb)
@@ -219,7 +218,7 @@ def test_weight_gradient_kernel_matches_fp64(n_rows, d_in, d_out, strided, dev):
     # the bias gradient (column sums of dM) from the same pass
     want_b = dM.double().sum(0)
     assert float((gb.double() - want_b).abs().max()) <= 2e-5 * max(float(want_b.abs().max()), 1.0)
-    a1, _, a2, gb2 = autograd._bwd_weight(dM, LE, E, ws)
+    a1, _, a2, gb2 = engine.backward.bwd_weight(dM, LE, E, ws)
     assert torch.equal(got, torch.cat([a1, a2], 1)) and torch.equal(gb, gb2)             # fixed summation order
 
 
@@ -235,7 +234,6 @@ def _nan_around(n, d, before, after, g, dev):
                                                         (257, 160, 96, False), (500, 300, 128, False), (64, 515, 512, True)])
 def test_fused_input_gradient_kernel_vs_torch(n_rows, d_in, d_out, strided, dev):
     """ngcf_layer_bwd_input_f32: dLE = dM.W1 + (dM.W2)*E, dE = dM.W1 + (dM.W2)*LE, one MFMA kernel per 128/160-column panel."""
-    from seoul_tourism_recommendation_ngcf_amd import autograd as ag
     eng = _pkg().engine
     g = torch.Generator().manual_seed(n_rows + d_in)
     dM = (torch.randn((n_rows, d_out), generator=g) * 0.3).to(dev)
@@ -244,7 +242,7 @@ def test_fused_input_gradient_kernel_vs_torch(n_rows, d_in, d_out, strided, dev)
         LE, E = _nan_around(n_rows, d_in, 0, 30, g, dev), _nan_around(n_rows, d_in, 3, 4, g, dev)
     else:
         LE, E = ((torch.randn((n_rows, d_in), generator=g) * 0.5).to(dev) for _ in range(2))
-    dLE, dE = ag._bwd_input(dM, W1, W2, LE, E, eng.Workspace())
+    dLE, dE = eng.backward.bwd_input(dM, W1, W2, LE, E, eng.Workspace())
     dS, dP = dM.double() @ W1.double(), dM.double() @ W2.double()
     scale = float(dS.abs().max()) + 1e-12
     np.testing.assert_allclose(dLE.cpu().numpy(), (dS + dP * E.double()).cpu().numpy(), atol=2e-6 * max(scale, 1.0), rtol=2e-5)
@@ -258,10 +256,9 @@ def test_resident_input_gradient_kernel_is_bit_identical_to_the_staged_one(n_row
     128-column panel resident in LDS, dM read once, no barrier after the prologue) plus `layer_bwd_input_narrow_kernel` for the
     1..4 columns beyond the last panel.  Same k order per output element as the staged kernel: the panels are bit-identical to it;
     the narrow columns (plain dot products, another order) within rounding; everything against fp64."""
-    from seoul_tourism_recommendation_ngcf_amd import autograd as ag
     eng = _pkg().engine
     g = torch.Generator().manual_seed(n_rows + d_in)
-    ldm = (d_out + 31) // 32 * 32                                      # dM as _bwd_pre hands it over: rows padded to 32 floats, padding NOT zeroed
+    ldm = (d_out + 31) // 32 * 32                                      # dM as bwd_pre hands it over: rows padded to 32 floats, padding NOT zeroed
     dM = torch.full((n_rows, ldm), float("nan"), device=dev)[:, :d_out]
     dM.copy_((torch.randn((n_rows, d_out), generator=g) * 0.3).to(dev))
     W1, W2 = ((torch.randn((d_out, d_in), generator=g) * 0.1).to(dev) for _ in range(2))
@@ -270,9 +267,9 @@ def test_resident_input_gradient_kernel_is_bit_identical_to_the_staged_one(n_row
     else:
         LE, E = ((torch.randn((n_rows, d_in), generator=g) * 0.5).to(dev) for _ in range(2))
     ws = eng.Workspace()
-    got = ag._bwd_input(dM, W1, W2, LE, E, ws)
+    got = eng.backward.bwd_input(dM, W1, W2, LE, E, ws)
     lib_options(bwd_input_resident=0)
-    want = ag._bwd_input(dM, W1, W2, LE, E, ws)                         # the staged kernel
+    want = eng.backward.bwd_input(dM, W1, W2, LE, E, ws)                         # the staged kernel
     lib_options(bwd_input_resident=1)
     n_panel = d_in if d_in % 128 == 0 or d_in % 128 > 4 else d_in // 128 * 128      # columns that ran on the resident kernel
     for a, b in zip(got, want):

@@ -20,6 +20,7 @@ import torch
 
 import bpr_multi_oracle as orc
 import ngcf_oracle as model_orc
+from loss_rig import I, U, batch as _batch, dev, float64_leaves, finish, held, lap, model as _model, pkg as _pkg, step_grads  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,18 +32,6 @@ BS = (1, 3, 4, 5, 1025)
 DS = (1, 63, 64, 65, 260)
 MS = (2, 3, 24, 63, 64)
 WD, GOUT = 0.025, 3.0
-
-
-def _pkg():
-    import seoul_tourism_recommendation_ngcf_amd as pkg
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
 
 
 def _inputs(B, m, D, seed):
@@ -65,18 +54,10 @@ def _existing(pkg, dev, u, p, n, bs, wd=WD):
     return [loss.detach()] + [x.grad for x in t]
 
 
-def _ulp32(x):
-    return float(np.spacing(np.float32(abs(x))))
-
-
 def _held_to_expanded(name, fused, expanded, want, ratios):
-    """The rule of the module docstring for one tensor (or the loss)."""
-    fused, expanded, want = (np.asarray(x, dtype=np.float64) for x in (fused, expanded, want))
-    assert np.isfinite(fused).all(), name
-    e_f, e_x = np.abs(fused - want).max(), np.abs(expanded - want).max()
-    bound = 2 * e_x + 4 * _ulp32(np.abs(want).max())
-    ratios[name] = max(ratios.get(name, 0.0), e_f / bound)
-    assert e_f <= bound, f"{name}: fused error {e_f:.3e}, expanded error {e_x:.3e}, bound {bound:.3e}"
+    """The rule of the module docstring (loss_rig.held) for one tensor (or the loss); the comparator is the expanded batch."""
+    bad = held(name, fused, expanded, want, ratios)
+    assert bad is None, bad
 
 
 # ---- identity (a): m = 1, mean = the existing kernels, bit for bit ------------------------------------------------------------
@@ -237,60 +218,25 @@ def test_wrappers_take_and_return_what_they_document(dev):
 
 
 # ---- through the model ---------------------------------------------------------------------------------------------------------
-U, I = 600, 30
-NUM = {"user": U, "item": I, "sex": 2, "age": 76, "month": 13, "day": 32, "dayofweek": 7}
-
-
-@pytest.fixture(scope="module")
-def lap(dev):
-    pkg = _pkg()
-    return [pkg.graphs.to_sparse_coo(s) for s in pkg.graphs.seoul_standin(dev, seed=6, n_user=U, n_item=I)]
-
-
-def _batch(g, B, m, dev):
-    r = lambda hi, k=B: torch.randint(0, hi, (k,), generator=g).to(dev)  # noqa: E731
-    return dict(year=torch.full((B,), 18, device=dev), u_id=torch.randperm(U, generator=g)[:B].to(dev), age=r(76), sex=r(2),
-                month=r(13), day=r(32), dow=r(7), pos_item=r(I)), torch.randint(0, I, (B, m), generator=g).to(dev)
-
-
-def _model(pkg, lap, dev, B, auto):
-    torch.manual_seed(4)
-    model = pkg.NGCF(65, [65, 65, 65], 0.0, [0.0, 0.0, 0.0], 1.0, lap, NUM, B, dev).to(dev)
-    model.node_dropout_mode = model.mess_dropout_mode = "device"
-    model.auto_train_graph = auto
-    model.train()
-    return model
-
-
 def _step_grads(model, crit, batch, neg_ids):
-    model.zero_grad(set_to_none=True)
-    u, p, n = model(node_flag=False, neg_item=neg_ids, **batch)
-    loss = crit(u, p, n)
-    loss.backward()
-    return loss.detach().clone(), {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None}
+    return step_grads(model, lambda mdl: crit(*mdl(node_flag=False, neg_item=neg_ids, **batch)))
 
 
 def _model_oracle(model, lap, batch, neg_ids, m, wd, bs):
     """float64 autograd through the oracle's propagation and a composition of the multi-negative definition."""
-    sd = {k: v.detach().double().cpu() for k, v in model.state_dict().items()}            # (after the forward: the injected user rows)
-    leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith(("w1_list", "w2_list", "item_emb", "user_emb"))}
-    w1, b1, w2, b2 = ([leaves[f"{w}_list.{k}.{x}"] for k in range(3)] for w, x in (("w1", "weight"), ("w1", "bias"), ("w2", "weight"), ("w2", "bias")))
-    L = lap[0].cpu().double().coalesce()
-    all_E = model_orc.propagate_torch(L, leaves["user_embedding.weight"], leaves["item_embedding.weight"], w1, b1, w2, b2)
+    leaves, all_E = float64_leaves(model, lap)
     u, p, n = model_orc.gather_torch(all_E, U, batch["u_id"].cpu(), batch["pos_item"].cpu(), neg_ids.cpu())
     B, D = u.shape
     sp = (u * p).sum(1).abs()
     sn = torch.einsum("bd,bjd->bj", u, n.reshape(B, m, D)).abs()
     rows = -torch.nn.functional.logsigmoid(sp[:, None] - sn).mean(1)
-    loss = (rows.sum() + wd * (u.pow(2).sum() + p.pow(2).sum() + n.pow(2).sum() / m)) / bs
-    loss.backward()
-    return float(loss.detach()), {k: v.grad.numpy() for k, v in leaves.items()}
+    return finish((rows.sum() + wd * (u.pow(2).sum() + p.pow(2).sum() + n.pow(2).sum() / m)) / bs, leaves)
 
 
 def test_through_the_model_against_the_expanded_call(lap, dev):
     pkg = _pkg()
     B, m = 8, 3
-    batch, neg = _batch(torch.Generator().manual_seed(8), B, m, dev)
+    batch, neg = _batch(torch.Generator().manual_seed(8), B, dev, m)
     expanded = {k: v.repeat_interleave(m) for k, v in batch.items()}
     runs = {}
     for auto in (False, True):

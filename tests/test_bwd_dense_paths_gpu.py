@@ -172,14 +172,14 @@ def test_weight_gradient_is_exact_on_every_path(c, dev, lib, lib_options):
 
 @pytest.mark.parametrize("n,d_in,d_out,seed", bo.WRAPPER_CASES)
 def test_weight_gradient_wrapper_cuts_a_wide_layer_into_exact_blocks(n, d_in, d_out, seed, dev, lib_options):
-    """autograd._bwd_weight at 515 -> 200: 2 x 5 calls of at most 128 x 128 (the last input block 3 columns wide), the bias from the
+    """engine.backward.bwd_weight at 515 -> 200: 2 x 5 calls of at most 128 x 128 (the last input block 3 columns wide), the bias from the
     first column block only."""
-    from seoul_tourism_recommendation_ngcf_amd import autograd, engine
+    from seoul_tourism_recommendation_ngcf_amd import engine
     lib_options(**DEFAULTS)
     ins = bo.weight_inputs(n, d_in, d_out, seed)
     want = bo.exact_weight(*ins)
     dM, LE, E = (torch.as_tensor(a.astype(np.float32)).to(dev) for a in ins)
-    got = autograd._bwd_weight(dM, LE, E, engine.Workspace())
+    got = engine.backward.bwd_weight(dM, LE, E, engine.Workspace())
     torch.cuda.synchronize()
     errs = [_mismatch(what, "wrapper", g.reshape(w.shape if w.ndim > 1 else (1, -1)), w if w.ndim > 1 else w[None])
             for what, g, w in zip(("gW1", "gb1", "gW2", "gb2"), got, (want[0], want[2], want[1], want[3]))]

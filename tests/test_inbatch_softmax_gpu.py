@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import inbatch_softmax_oracle as orc
-import ngcf_oracle as model_orc
+from loss_rig import I, U, batch as _batch, dev, float64_leaves, finish, held as _held, lap, model as _model, pkg as _pkg, step_grads  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,18 +32,6 @@ EDGES = [(1, 0, 1), (2, 0, 31), (31, 1, 32), (32, 31, 33), (33, 127, 65), (64, 1
 # (tests/test_inbatch_softmax_oracle.py holds the plan to these)
 CUTS = [(4097, 0, 33), (33, 0, 513), (33, 4064, 33)]
 NAMES = ("loss", "lse", "du", "dp", "dx")
-
-
-def _pkg():
-    import seoul_tourism_recommendation_ngcf_amd as pkg
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
 
 
 @functools.lru_cache(maxsize=None)
@@ -121,23 +109,6 @@ def _oracle(c, tau, wd, bs, use=("ids", "q")):
     if "q" in use:
         kw.update(logq=c["logq"], xlogq=c["xlogq"], pos_logq=c["pos_logq"])
     return orc.inbatch_softmax(c["u"], c["p"], 1.0 / tau, wd, bs, GOUT, **kw)
-
-
-def _ulp32(x):
-    return float(np.spacing(np.float32(abs(x))))
-
-
-def _held(name, fused, other, want, ratios):
-    """The rule of the module docstring for one tensor (or the loss); an empty tensor (dx without extras) holds."""
-    fused, other, want = (np.asarray(x, dtype=np.float64) for x in (fused, other, want))
-    assert fused.shape == other.shape == want.shape, name
-    assert np.isfinite(fused).all(), name
-    if want.size == 0:
-        return None
-    e_f, e_x = np.abs(fused - want).max(), np.abs(other - want).max()
-    bound = 2 * e_x + 4 * _ulp32(np.abs(want).max())
-    ratios[name] = max(ratios.get(name, 0.0), e_f / bound)
-    return None if e_f <= bound else f"{name}: fused error {e_f:.3e}, torch32 error {e_x:.3e}, bound {bound:.3e}"
 
 
 def _check(pkg, dev, c, tau, wd, bs, label, use=("ids", "q")):
@@ -291,24 +262,7 @@ def test_refusals_on_the_device(dev):
 
 
 # ---- through the model ---------------------------------------------------------------------------------------------------------
-U, I = 600, 30
-NUM = {"user": U, "item": I, "sex": 2, "age": 76, "month": 13, "day": 32, "dayofweek": 7}
 TAU = 0.5
-
-
-@pytest.fixture(scope="module")
-def lap(dev):
-    pkg = _pkg()
-    return [pkg.graphs.to_sparse_coo(s) for s in pkg.graphs.seoul_standin(dev, seed=6, n_user=U, n_item=I)]
-
-
-def _model(pkg, lap, dev, B, auto):
-    torch.manual_seed(4)
-    model = pkg.NGCF(65, [65, 65, 65], 0.0, [0.0, 0.0, 0.0], 1.0, lap, NUM, B, dev).to(dev)
-    model.node_dropout_mode = model.mess_dropout_mode = "device"
-    model.auto_train_graph = auto
-    model.train()
-    return model
 
 
 def _rows(dev, T, seed):
@@ -360,33 +314,21 @@ def _torch_loss(u, p, ids, lq, tau, wd, bs):
 
 
 def _step_grads(model, loss_fn, batch, dev):
-    model.zero_grad(set_to_none=True)
-    u, p, _ = model(node_flag=False, neg_item=torch.empty(0, dtype=torch.int64, device=dev), **batch)
-    loss = loss_fn(u, p)
-    loss.backward()
-    return loss.detach().clone(), {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None}
+    return step_grads(model, lambda mdl: loss_fn(*mdl(node_flag=False, neg_item=torch.empty(0, dtype=torch.int64, device=dev), **batch)[:2]))
 
 
 def _model_oracle(model, lap, batch, lq, tau, wd, bs):
     """float64 autograd through the oracle's propagation and the loss in torch's float64 ops."""
-    sd = {k: v.detach().double().cpu() for k, v in model.state_dict().items()}            # (after the forward: the injected user rows)
-    leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith(("w1_list", "w2_list", "item_emb", "user_emb"))}
-    w1, b1, w2, b2 = ([leaves[f"{w}_list.{k}.{x}"] for k in range(3)] for w, x in (("w1", "weight"), ("w1", "bias"), ("w2", "weight"), ("w2", "bias")))
-    L = lap[0].cpu().double().coalesce()
-    all_E = model_orc.propagate_torch(L, leaves["user_embedding.weight"], leaves["item_embedding.weight"], w1, b1, w2, b2)
+    leaves, all_E = float64_leaves(model, lap)
     ids = batch["pos_item"].cpu()
-    loss = _torch_loss(all_E[batch["u_id"].cpu()], all_E[U:][ids], ids, lq.double().cpu(), tau, wd, bs)
-    loss.backward()
-    return float(loss.detach()), {k: v.grad.numpy() for k, v in leaves.items()}
+    return finish(_torch_loss(all_E[batch["u_id"].cpu()], all_E[U:][ids], ids, lq.double().cpu(), tau, wd, bs), leaves)
 
 
 def test_parameter_gradients_of_one_eager_step_against_the_float64_step(lap, dev):
     pkg = _pkg()
     B = 8
     g = torch.Generator().manual_seed(8)
-    r = lambda hi, k=B: torch.randint(0, hi, (k,), generator=g).to(dev)  # noqa: E731
-    batch = dict(year=torch.full((B,), 18, device=dev), u_id=torch.randperm(U, generator=g)[:B].to(dev), age=r(76), sex=r(2),
-                 month=r(13), day=r(32), dow=r(7), pos_item=r(I))
+    batch = _batch(g, B, dev)
     batch["pos_item"][1] = batch["pos_item"][0]                               # a shared positive: a masked pair
     lq = (-12.0 * torch.rand(B, generator=g)).to(dev)
     crit = pkg.InBatchSoftmax(WD, B, temperature=TAU)

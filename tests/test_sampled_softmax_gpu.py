@@ -16,6 +16,7 @@ import bpr_multi_oracle as bpr_orc
 import ngcf_oracle as model_orc
 import sampled_softmax_oracle as orc
 import softmax_full_oracle as full_orc
+from loss_rig import I, U, batch as _batch, dev, float64_leaves, finish, lap, model as _model, pkg as _pkg, step_grads, ulp32 as _ulp32  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -24,18 +25,6 @@ DS = (1, 63, 64, 65, 260)
 MS = (1, 2, 3, 24, 63, 64)
 TAUS = (1.0, 0.25)
 WD, GOUT = 0.025, 3.0
-
-
-def _pkg():
-    import seoul_tourism_recommendation_ngcf_amd as pkg
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
 
 
 def _inputs(B, m, D, seed):
@@ -204,10 +193,6 @@ def test_a_rarely_proposed_negative_weighs_as_much_more_as_it_is_rarer(dev):
         np.testing.assert_allclose(a[:, 1] / a[:, 0], 500.0, rtol=1e-12)
 
 
-def _ulp32(x):
-    return float(np.spacing(np.float32(abs(x))))
-
-
 def test_a_constant_per_row_in_both_corrections_changes_nothing(dev):
     """logq + k_b and pos_logq + k_b for an integer k_b per row (logq in multiples of 2^-10, so the shifted values are exact in
     float32): the loss moves by at most 4 ulp - only the roundings of the corrected scores differ - and the gradients stay within
@@ -290,62 +275,29 @@ def test_wrappers_take_and_return_what_they_document(dev):
 
 
 # ---- through the model ---------------------------------------------------------------------------------------------------------
-U, I = 600, 30
-NUM = {"user": U, "item": I, "sex": 2, "age": 76, "month": 13, "day": 32, "dayofweek": 7}
 TAU = 0.5
 
 
-@pytest.fixture(scope="module")
-def lap(dev):
-    pkg = _pkg()
-    return [pkg.graphs.to_sparse_coo(s) for s in pkg.graphs.seoul_standin(dev, seed=6, n_user=U, n_item=I)]
-
-
-def _batch(g, B, m, dev):
-    r = lambda hi, k=B: torch.randint(0, hi, (k,), generator=g).to(dev)  # noqa: E731
-    return dict(year=torch.full((B,), 18, device=dev), u_id=torch.randperm(U, generator=g)[:B].to(dev), age=r(76), sex=r(2),
-                month=r(13), day=r(32), dow=r(7), pos_item=r(I)), torch.randint(0, I, (B, m), generator=g).to(dev)
-
-
-def _model(pkg, lap, dev, B, auto):
-    torch.manual_seed(4)
-    model = pkg.NGCF(65, [65, 65, 65], 0.0, [0.0, 0.0, 0.0], 1.0, lap, NUM, B, dev).to(dev)
-    model.node_dropout_mode = model.mess_dropout_mode = "device"
-    model.auto_train_graph = auto
-    model.train()
-    return model
-
-
 def _step_grads(model, crit, batch, neg_ids, logq, pos_logq):
-    model.zero_grad(set_to_none=True)
-    u, p, n = model(node_flag=False, neg_item=neg_ids, **batch)
-    loss = crit(u, p, n, logq, pos_logq)
-    loss.backward()
-    return loss.detach().clone(), {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None}
+    return step_grads(model, lambda mdl: crit(*mdl(node_flag=False, neg_item=neg_ids, **batch), logq, pos_logq))
 
 
 def _model_oracle(model, lap, batch, neg_ids, logq, pos_logq, m, tau, wd, bs):
     """float64 autograd through the oracle's propagation and a composition of the definition in torch's float64 ops."""
-    sd = {k: v.detach().double().cpu() for k, v in model.state_dict().items()}            # (after the forward: the injected user rows)
-    leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith(("w1_list", "w2_list", "item_emb", "user_emb"))}
-    w1, b1, w2, b2 = ([leaves[f"{w}_list.{k}.{x}"] for k in range(3)] for w, x in (("w1", "weight"), ("w1", "bias"), ("w2", "weight"), ("w2", "bias")))
-    L = lap[0].cpu().double().coalesce()
-    all_E = model_orc.propagate_torch(L, leaves["user_embedding.weight"], leaves["item_embedding.weight"], w1, b1, w2, b2)
+    leaves, all_E = float64_leaves(model, lap)
     u, p, n = model_orc.gather_torch(all_E, U, batch["u_id"].cpu(), batch["pos_item"].cpu(), neg_ids.cpu())
     B, D = u.shape
     z0 = (u * p).sum(1) / tau - pos_logq.double().cpu()
     zj = torch.einsum("bd,bjd->bj", u, n.reshape(B, m, D)) / tau - logq.double().cpu().reshape(B, m)
     rows = torch.logsumexp(torch.cat((z0[:, None], zj), 1), 1) - z0
-    loss = (rows.sum() + wd * (u.pow(2).sum() + p.pow(2).sum() + n.pow(2).sum() / m)) / bs
-    loss.backward()
-    return float(loss.detach()), {k: v.grad.numpy() for k, v in leaves.items()}
+    return finish((rows.sum() + wd * (u.pow(2).sum() + p.pow(2).sum() + n.pow(2).sum() / m)) / bs, leaves)
 
 
 def test_through_the_model_against_the_float64_step(lap, dev):
     pkg = _pkg()
     B, m = 8, 3
     g = torch.Generator().manual_seed(8)
-    batch, neg = _batch(g, B, m, dev)
+    batch, neg = _batch(g, B, dev, m)
     logq = (-12.0 * torch.rand((B, m), generator=g)).to(dev)
     pos_logq = (-12.0 * torch.rand(B, generator=g)).to(dev)
     runs = {}

@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 import torch
 
-import ngcf_oracle as model_orc
 import softmax_full_oracle as orc
+from loss_rig import (U, batch as _batch, dev, float64_leaves, finish, held as _held, lap, model as _model, pkg as _pkg,  # noqa: F401
+                      step_grads, ulp32 as _ulp32)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +30,6 @@ EDGES = [(1, 1, 1), (31, 31, 31), (32, 32, 32), (33, 33, 33), (65, 127, 65), (1,
 # (B, n_items, D): forward and dU cut with a ragged last piece; dI cut; the first D past the slab width (tests/test_softmax_full_oracle.py
 # holds the plan to these)
 CUTS = [(1, 4097, 65), (4097, 33, 65), (33, 33, 513)]
-
-
-def _pkg():
-    import seoul_tourism_recommendation_ngcf_amd as pkg
-    return pkg
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
 
 
 def _inputs(B, n, D, seed, scale=None):
@@ -96,20 +85,6 @@ def _torch32(dev, u, it, pos, tau, wd, bs):
         return loss.detach(), lse.detach(), tu.grad, ti.grad
     finally:
         torch.backends.cuda.matmul.allow_tf32 = saved
-
-
-def _ulp32(x):
-    return float(np.spacing(np.float32(abs(x))))
-
-
-def _held(name, fused, other, want, ratios):
-    """The rule of the module docstring for one tensor (or the loss)."""
-    fused, other, want = (np.asarray(x, dtype=np.float64) for x in (fused, other, want))
-    assert np.isfinite(fused).all(), name
-    e_f, e_x = np.abs(fused - want).max(), np.abs(other - want).max()
-    bound = 2 * e_x + 4 * _ulp32(np.abs(want).max())
-    ratios[name] = max(ratios.get(name, 0.0), e_f / bound)
-    return None if e_f <= bound else f"{name}: fused error {e_f:.3e}, torch32 error {e_x:.3e}, bound {bound:.3e}"
 
 
 NAMES = ("loss", "lse", "du", "ditems")
@@ -248,31 +223,7 @@ def test_only_the_gradient_asked_for_is_computed(dev):
 
 
 # ---- through the model ---------------------------------------------------------------------------------------------------------
-U, I = 600, 30
-NUM = {"user": U, "item": I, "sex": 2, "age": 76, "month": 13, "day": 32, "dayofweek": 7}
 TAU = 0.5
-
-
-@pytest.fixture(scope="module")
-def lap(dev):
-    pkg = _pkg()
-    return [pkg.graphs.to_sparse_coo(s) for s in pkg.graphs.seoul_standin(dev, seed=6, n_user=U, n_item=I)]
-
-
-def _batch(g, B, dev):
-    r = lambda hi, k=B: torch.randint(0, hi, (k,), generator=g).to(dev)  # noqa: E731
-    return dict(year=torch.full((B,), 18, device=dev), u_id=torch.randperm(U, generator=g)[:B].to(dev), age=r(76), sex=r(2),
-                month=r(13), day=r(32), dow=r(7), pos_item=r(I))
-
-
-def _model(pkg, lap, dev, B, auto):
-    torch.manual_seed(4)
-    model = pkg.NGCF(65, [65, 65, 65], 0.0, [0.0, 0.0, 0.0], 1.0, lap, NUM, B, dev).to(dev)
-    model.node_dropout_mode = model.mess_dropout_mode = "device"
-    if auto is not None:
-        model.auto_train_graph = auto
-    model.train()
-    return model
 
 
 def _torch_loss(u, pos, items, tau, wd, bs):
@@ -281,23 +232,16 @@ def _torch_loss(u, pos, items, tau, wd, bs):
 
 
 def _step_grads(model, loss_fn, batch, dev):
-    model.zero_grad(set_to_none=True)
-    u, _, _ = model(node_flag=False, neg_item=torch.empty(0, dtype=torch.int64, device=dev), **batch)
-    loss = loss_fn(u, batch["pos_item"], model.all_items_emb)
-    loss.backward()
-    return loss.detach().clone(), {k: v.grad.detach().clone() for k, v in model.named_parameters() if v.grad is not None}
+    def forward_and_loss(mdl):
+        u, _, _ = mdl(node_flag=False, neg_item=torch.empty(0, dtype=torch.int64, device=dev), **batch)
+        return loss_fn(u, batch["pos_item"], mdl.all_items_emb)
+    return step_grads(model, forward_and_loss)
 
 
 def _model_oracle(model, lap, batch, tau, wd, bs):
     """float64 autograd through the oracle's propagation and the loss in torch's float64 ops."""
-    sd = {k: v.detach().double().cpu() for k, v in model.state_dict().items()}            # (after the forward: the injected user rows)
-    leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith(("w1_list", "w2_list", "item_emb", "user_emb"))}
-    w1, b1, w2, b2 = ([leaves[f"{w}_list.{k}.{x}"] for k in range(3)] for w, x in (("w1", "weight"), ("w1", "bias"), ("w2", "weight"), ("w2", "bias")))
-    L = lap[0].cpu().double().coalesce()
-    all_E = model_orc.propagate_torch(L, leaves["user_embedding.weight"], leaves["item_embedding.weight"], w1, b1, w2, b2)
-    loss = _torch_loss(all_E[batch["u_id"].cpu()], batch["pos_item"].cpu(), all_E[U:], tau, wd, bs)
-    loss.backward()
-    return float(loss.detach()), {k: v.grad.numpy() for k, v in leaves.items()}
+    leaves, all_E = float64_leaves(model, lap)
+    return finish(_torch_loss(all_E[batch["u_id"].cpu()], batch["pos_item"].cpu(), all_E[U:], tau, wd, bs), leaves)
 
 
 def test_through_the_model_against_the_torch_composition(lap, dev):

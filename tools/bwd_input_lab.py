@@ -8,7 +8,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import seoul_tourism_recommendation_ngcf_amd as pkg  # noqa: E402
-from seoul_tourism_recommendation_ngcf_amd import _lib, autograd as ag  # noqa: E402
+from seoul_tourism_recommendation_ngcf_amd import _lib  # noqa: E402
 
 eng = pkg.engine
 dev = torch.device("cuda:0")
@@ -39,8 +39,8 @@ for d_in in (128, 130):
     W1, W2 = ((torch.rand((d_out, d_in), generator=g) - 0.5).to(dev) * 0.2 for _ in range(2))
     for res in (0, 1):
         _lib.set_option("bwd_input_resident", res)
-        t = timeit(lambda: ag._bwd_input(dM, W1, W2, LE, E, ws))
+        t = timeit(lambda: eng.backward.bwd_input(dM, W1, W2, LE, E, ws))
         print(f"d_in={d_in}: input gradients, bwd_input_resident={res}: {t * 1e3:.1f} us  ({4 * N * d_in * d_out / t / 1e9:.1f} TFLOP/s)", flush=True)
-    t = timeit(lambda: ag._bwd_weight(dM, LE, E, ws))
+    t = timeit(lambda: eng.backward.bwd_weight(dM, LE, E, ws))
     print(f"d_in={d_in}: weight gradients: {t * 1e3:.1f} us", flush=True)
     del dM, LE, E
