@@ -119,8 +119,6 @@ extern "C" int ngcf_add_rows_f32(float *out, int64_t ldo, const float *add, int6
 // 8 waves each keep 4 of the 32 output tiles in registers (v_mfma_f32_32x32x2_f32: A = dM^T, B = [S|P], k = row),
 // and write one partial result per workgroup; a second kernel adds the partials in workgroup order (fixed order,
 // no atomics).  Widths up to 128 (padded to multiples of 32 inside LDS); wider layers use the library GEMM.
-typedef float bw_f32x16 __attribute__((ext_vector_type(16)));
-typedef float bw_f32x4 __attribute__((ext_vector_type(4)));
 static constexpr int kBwRows = 32;        // rows per LDS block
 static constexpr int kBwWGs = 256;
 static constexpr int kBwM = 128, kBwN = 256;
@@ -137,21 +135,21 @@ __global__ __launch_bounds__(512) void bwd_weight_kernel(const float *__restrict
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
     for (int i = tid; i < 2 * kBwRows * kBwM; i += 512) (&As[0][0][0])[i] = 0.f;
     for (int i = tid; i < 2 * kBwRows * kBwN; i += 512) (&Bs[0][0][0])[i] = 0.f;
-    bw_f32x16 acc[4];
+    f32x16 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     float bsum = 0.f;
     // staging: 2 float4 slots per thread and operand: slot s -> row s / 32, columns 4 * (s % 32) ..
-    bw_f32x4 rm[2], rl[2], re[2];
+    f32x4 rm[2], rl[2], re[2];
     const int64_t n_blocks = (n_rows + kBwRows - 1) / kBwRows;
-    auto load4 = [&](const float *base, int64_t ld, int64_t row, int c, int width) -> bw_f32x4 {
-        bw_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    auto load4 = [&](const float *base, int64_t ld, int64_t row, int c, int width) -> f32x4 {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (row < n_rows && c < width) {
             const float *p = base + row * ld + c;
             if (ALIGNED && c + 4 <= width) {
-                v = *reinterpret_cast<const bw_f32x4 *>(p);
+                v = *reinterpret_cast<const f32x4 *>(p);
             } else {
                 v.x = p[0];
                 if (c + 1 < width) v.y = p[1];
@@ -175,10 +173,10 @@ __global__ __launch_bounds__(512) void bwd_weight_kernel(const float *__restrict
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             const int s = tid + s2 * 512, r = s >> 5, c = (s & 31) * 4;
-            *reinterpret_cast<bw_f32x4 *>(&As[buf][r][c]) = rm[s2];
+            *reinterpret_cast<f32x4 *>(&As[buf][r][c]) = rm[s2];
             if (c < P) {
-                *reinterpret_cast<bw_f32x4 *>(&Bs[buf][r][c]) = rl[s2] + re[s2];
-                *reinterpret_cast<bw_f32x4 *>(&Bs[buf][r][P + c]) = rl[s2] * re[s2];
+                *reinterpret_cast<f32x4 *>(&Bs[buf][r][c]) = rl[s2] + re[s2];
+                *reinterpret_cast<f32x4 *>(&Bs[buf][r][P + c]) = rl[s2] * re[s2];
             }
         }
     };
@@ -412,7 +410,7 @@ extern "C" int ngcf_layer_bwd_weight_f32(const float *dM, int64_t ldM, const flo
 // [N, 2 d_in] intermediate between them):
 //   dS = dM . W1,  dP = dM . W2                     ([n_rows, d_in] each; W1, W2 are nn.Linear weights [d_out, d_in])
 //   dLE = dS + dP * E,   dE = dS + dP * LE          (NGCF.py:131-136 differentiated)
-// Same structure as layer_dense_kernel (dense.hip): a workgroup of 4 waves owns 128 rows, each wave a 32 x 128 output
+// Same structure as layer_dense_kernel (dense_staged.hip): a workgroup of 4 waves owns 128 rows, each wave a 32 x 128 output
 // panel as four 32x32 tiles of v_mfma_f32_32x32x2_f32; K = d_out is walked in chunks of 32 through double-buffered LDS
 // (A: rows of dM, B: the weight rows W[k, col0 .. col0+128), which need no transpose).  The K loop runs twice over the same
 // rows of dM (second read from L2), once per weight matrix, so that both 64-register accumulators are live only in the
@@ -466,8 +464,8 @@ __global__ __launch_bounds__(256, 2) void layer_bwd_input_kernel(const float *__
     const int li = lane & 31, lh = lane >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * BM;
     const int d4 = (d_out + 3) & ~3;
-    bw_f32x16 acc[2][NTW];
-    bw_f32x4 xreg[XJ], wreg[NT];
+    f32x16 acc[2][NTW];
+    f32x4 xreg[XJ], wreg[NT];
     const int tile0 = SMALL ? wave * NTW : 0;         // first tile (32 columns) of this wave
     const int wrow = SMALL ? 0 : wave * 32;           // first row of this wave inside the workgroup's rows
 
@@ -479,14 +477,14 @@ __global__ __launch_bounds__(256, 2) void layer_bwd_input_kernel(const float *__
             grow = grow < n_rows ? grow : n_rows - 1;
             const int c0 = chunk * kBiKC + (f % 8) * 4;
             const int cc = c0 < d4 ? c0 : d4 - 4;
-            bw_f32x4 a = *reinterpret_cast<const bw_f32x4 *>(dM + grow * ldM + cc);
+            f32x4 a = *reinterpret_cast<const f32x4 *>(dM + grow * ldM + cc);
             a.x = c0 < d_out ? a.x : 0.f;
             a.y = c0 + 1 < d_out ? a.y : 0.f;
             a.z = c0 + 2 < d_out ? a.z : 0.f;
             a.w = c0 + 3 < d_out ? a.w : 0.f;
             xreg[j] = a;
         }
-        const bw_f32x4 *src = reinterpret_cast<const bw_f32x4 *>(Wp + ((int64_t)half * n_chunks + chunk) * kBiKC * WCOLS);
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(Wp + ((int64_t)half * n_chunks + chunk) * kBiKC * WCOLS);
 #pragma unroll
         for (int j = 0; j < NT; ++j) wreg[j] = src[tid + 256 * j];       // 32 x WCOLS floats = NT float4 per thread
     };
@@ -494,9 +492,9 @@ __global__ __launch_bounds__(256, 2) void layer_bwd_input_kernel(const float *__
 #pragma unroll
         for (int j = 0; j < XJ; ++j) {
             const int f = tid + 256 * j;
-            *reinterpret_cast<bw_f32x4 *>(Xs + buf * (BM * XLD) + (f / 8) * XLD + (f % 8) * 4) = xreg[j];
+            *reinterpret_cast<f32x4 *>(Xs + buf * (BM * XLD) + (f / 8) * XLD + (f % 8) * 4) = xreg[j];
         }
-        bw_f32x4 *dst = reinterpret_cast<bw_f32x4 *>(Ws + buf * (kBiKC * WCOLS));
+        f32x4 *dst = reinterpret_cast<f32x4 *>(Ws + buf * (kBiKC * WCOLS));
 #pragma unroll
         for (int j = 0; j < NT; ++j) dst[tid + 256 * j] = wreg[j];
     };
@@ -517,7 +515,7 @@ __global__ __launch_bounds__(256, 2) void layer_bwd_input_kernel(const float *__
             const float *W = Ws + buf * (kBiKC * WCOLS) + tile0 * 32 + li;
 #pragma unroll
             for (int kb = 0; kb < kBiKC / 8; ++kb) {
-                const bw_f32x4 a4 = *reinterpret_cast<const bw_f32x4 *>(X + kb * 8);
+                const f32x4 a4 = *reinterpret_cast<const f32x4 *>(X + kb * 8);
                 const float av[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
                 for (int sx = 0; sx < 4; ++sx) {
@@ -544,7 +542,7 @@ __global__ __launch_bounds__(256, 2) void layer_bwd_input_kernel(const float *__
 }
 
 
-// ---- r04: the same product with the weights RESIDENT in LDS (the structure of layer_dense_resident_kernel, dense.hip) --------
+// ---- r04: the same product with the weights RESIDENT in LDS (the structure of layer_dense_resident_kernel, dense_persistent.hip) --------
 // The staged kernel above runs at 37 % of the fp32 matrix peak at C3 (1.23 ms per 1.1 M-row layer): its two K loops over staged
 // chunks (8 barriers per 128 rows, dM read twice, the W chunks re-staged by every workgroup) and its epilogue (2 loads + 2 stores per
 // output element) run one after the other, so matrix time and memory time add up.  Here [W1 | W2] for one panel of 128 input
@@ -578,8 +576,8 @@ __global__ __launch_bounds__(kBiResWaves * 64) void layer_bwd_input_resident_ker
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int li = lane & 31, lh = lane >> 5;
     {
-        const bw_f32x4 *src = reinterpret_cast<const bw_f32x4 *>(Wr);
-        bw_f32x4 *dst = reinterpret_cast<bw_f32x4 *>(Wres);
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(Wr);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(Wres);
         const int n4 = n_chunks * kBiResDC * 256 / 4;
         for (int i = tid; i < n4; i += kBiResWaves * 64) dst[i] = src[i];
     }
@@ -595,12 +593,12 @@ __global__ __launch_bounds__(kBiResWaves * 64) void layer_bwd_input_resident_ker
     };
     // the lane's two 16-byte pieces of a chunk: dM at columns c*16 + lh*4 (a) and c*16 + 8 + lh*4 (b); columns past d_out are
     // re-read from the row's last float4 and zeroed at use
-    auto fetch = [&](const float *row, int c, bw_f32x4 &a, bw_f32x4 &b) {
+    auto fetch = [&](const float *row, int c, f32x4 &a, f32x4 &b) {
         const int ca = c * kBiResDC + lh * 4, cb = ca + 8;
-        a = *reinterpret_cast<const bw_f32x4 *>(row + (ca < d4 ? ca : d4 - 4));
-        b = *reinterpret_cast<const bw_f32x4 *>(row + (cb < d4 ? cb : d4 - 4));
+        a = *reinterpret_cast<const f32x4 *>(row + (ca < d4 ? ca : d4 - 4));   // the clamp of fetch_pieces() (dense_device.h), for one operand
+        b = *reinterpret_cast<const f32x4 *>(row + (cb < d4 ? cb : d4 - 4));
     };
-    bw_f32x4 a0, b0, a1, b1;                        // two chunks of look-ahead in two fixed register sets (every prefetch unconditional)
+    f32x4 a0, b0, a1, b1;                        // two chunks of look-ahead in two fixed register sets (every prefetch unconditional)
     int64_t tile = (int64_t)blockIdx.x * kBiResWaves + wave;
     {
         const float *r0 = dM + row_of(tile < n_tiles ? tile : 0) * ldM;
@@ -610,12 +608,12 @@ __global__ __launch_bounds__(kBiResWaves * 64) void layer_bwd_input_resident_ker
     for (; tile < n_tiles; tile += tile_step) {
         const int64_t row0 = tile * 32;
         const float *m_row = dM + row_of(tile) * ldM;
-        bw_f32x16 accS[4], accP[4];
+        f32x16 accS[4], accP[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) accS[t][r] = 0.f, accP[t][r] = 0.f;
-        auto chunk_mfma = [&](int c, bw_f32x4 a, bw_f32x4 b) {
+        auto chunk_mfma = [&](int c, f32x4 a, f32x4 b) {
             const int ca = c * kBiResDC + lh * 4, cb = ca + 8;
             if (cb + 4 > d_out) {                   // only the last chunk of a width that is not a multiple of 16
 #pragma unroll
@@ -627,12 +625,12 @@ __global__ __launch_bounds__(kBiResWaves * 64) void layer_bwd_input_resident_ker
             const float *wc = W + (int64_t)c * kBiResDC * 256;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                const bw_f32x4 av = kb ? b : a;
+                const f32x4 av = kb ? b : a;
 #pragma unroll
                 for (int sx = 0; sx < 4; ++sx) {
                     const float *wk = wc + (kb * 8 + lh * 4 + sx) * 256;
-                    const bw_f32x4 v1 = *reinterpret_cast<const bw_f32x4 *>(wk);
-                    const bw_f32x4 v2 = *reinterpret_cast<const bw_f32x4 *>(wk + 128);
+                    const f32x4 v1 = *reinterpret_cast<const f32x4 *>(wk);
+                    const f32x4 v2 = *reinterpret_cast<const f32x4 *>(wk + 128);
                     accS[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[sx], v1.x, accS[0], 0, 0, 0);
                     accS[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[sx], v1.y, accS[1], 0, 0, 0);
                     accS[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[sx], v1.z, accS[2], 0, 0, 0);
@@ -647,13 +645,13 @@ __global__ __launch_bounds__(kBiResWaves * 64) void layer_bwd_input_resident_ker
         int c = 0;
         for (; c + 1 < n_chunks; c += 2) {
             {
-                const bw_f32x4 ua = a0, ub = b0;
+                const f32x4 ua = a0, ub = b0;
                 fetch(m_row, c + 2 < last ? c + 2 : last, a0, b0);          // in flight under two chunks of MFMAs
                 __builtin_amdgcn_sched_barrier(0);
                 chunk_mfma(c, ua, ub);
             }
             {
-                const bw_f32x4 ua = a1, ub = b1;
+                const f32x4 ua = a1, ub = b1;
                 fetch(m_row, c + 3 < last ? c + 3 : last, a1, b1);
                 __builtin_amdgcn_sched_barrier(0);
                 chunk_mfma(c + 1, ua, ub);

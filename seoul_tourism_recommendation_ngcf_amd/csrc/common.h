@@ -62,7 +62,7 @@ struct NgcfOptions {
     int no_tail_table = 0;         // NGCF_NO_TAIL_TABLE: tail columns gathered out of the strided table
     int no_pad_product = 0;        // NGCF_NO_PAD_PRODUCT: small matrices: do not multiply the padding columns along
     int64_t fork_min = 200000000;  // NGCF_FORK_MIN: entry-columns from which the halves are forked under capture
-    // dense.hip
+    // dense.hip (dense_path)
     int dense_direct = 1;          // NGCF_DENSE_DIRECT: 0 never, 1 up to 8 192 rows, 2 at any row count
     int dense_resident = 4;        // NGCF_DENSE_RESIDENT: 4 the bf16 three-way split kernel; 1 the fp32 weights-resident kernel; 0 keeps the staged kernel
     int dense_resident_min_rows = 106496;  // NGCF_DENSE_RESIDENT_MIN_ROWS: rows from which the weights-resident kernel runs (65 536 = one round of its 2 048 waves; measured cross-over, profiles/r04_dense_rows_lab.txt)
@@ -342,6 +342,14 @@ template <int VEC> struct VecT;
 template <> struct VecT<4> { using type = float4; };
 template <> struct VecT<2> { using type = float2; };
 template <> struct VecT<1> { using type = float; };
+
+// The register vocabulary of the matrix-core kernels (dense*.hip, bwd_dense.hip, rank*.hip, softmax_tile_device.h, list_*.hip):
+// an MFMA 32 x 32 accumulator tile, a lane's 16-byte pieces and the bf16 fragments of 32x32x16.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: stays in registers inside lambdas
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ inline float4 vfma(float s, float4 x, float4 a)
 {

@@ -221,8 +221,6 @@ extern "C" int ngcf_exposure_summary(const int64_t *sorted_counts, const int64_t
 
 namespace {
 
-typedef float ldiv_f32x16 __attribute__((ext_vector_type(16)));
-
 struct ListDivKs {
     int v[NGCF_LIST_DIV_KS_MAX];
 };
@@ -236,7 +234,7 @@ __device__ inline double list_pair_distance(double g, double gaa, double gbb)
 }
 
 // this lane's column b of one tile whose rows are a_base + 0..31: s += d_ab over the valid a < b, ascending a
-__device__ inline double list_div_chain(const ldiv_f32x16 &acc, int a_base, int b, double s, const int32_t *sid, const float *sdiag,
+__device__ inline double list_div_chain(const f32x16 &acc, int a_base, int b, double s, const int32_t *sid, const float *sdiag,
                                         int half)
 {
 #pragma clang fp contract(off) reassociate(off)
@@ -258,7 +256,7 @@ __device__ inline double list_div_chain(const ldiv_f32x16 &acc, int a_base, int 
 }
 
 // G_cc of a diagonal tile: row c sits in half-wave (c >> 2) & 1, element 4 (c >> 3) + (c & 3)
-__device__ inline void list_div_diag(const ldiv_f32x16 &acc, int col, int half, float *sdiag)
+__device__ inline void list_div_diag(const f32x16 &acc, int col, int half, float *sdiag)
 {
     const int want = 4 * (col >> 3) + (col & 3);
     float g = 0.f;
@@ -353,7 +351,7 @@ __global__ __launch_bounds__(256) void list_diversity_kernel(const int64_t *__re
             }
         };
 
-        ldiv_f32x16 acc00, acc01, acc11;
+        f32x16 acc00, acc01, acc11;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc11[e] = 0.f;
         load(0);

@@ -26,8 +26,6 @@
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-typedef float mmr_f32x16 __attribute__((ext_vector_type(16)));
-
 // where G[a][b], a <= b, sits in a wave's region
 template <int NB> __device__ inline int mmr_gidx(int a, int b)
 {
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(256) void list_mmr_kernel(const int64_t *__restrict
             }
         };
 
-        mmr_f32x16 acc00, acc01, acc11;
+        f32x16 acc00, acc01, acc11;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc11[e] = 0.f;
         load(0);

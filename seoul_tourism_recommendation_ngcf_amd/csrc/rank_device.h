@@ -16,8 +16,6 @@
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-typedef float rank_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kRankIT = 128, kRankTK = 32;      // items of a tile, columns of a K chunk
 
 constexpr uint32_t kPadKey = 0u;                // below every score key but the one NaN pattern 0xffffffff (which ties it)

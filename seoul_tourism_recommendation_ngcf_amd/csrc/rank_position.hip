@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void pos_scan_kernel(const float *__restrict__
 #pragma unroll
             for (int w = 0; w < IT / 32; ++w) exm[tid * (IT / 32) + w] = m[w];
         }
-        rank_f32x16 acc[UB];
+        f32x16 acc[UB];
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
 #pragma unroll

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void softmax_full_fwd_kernel(const SoftmaxSide
             sCid[par + tid] = (has_ids && gi < i_end) ? col_id(a, gi) : 0;
             sQ[par + tid] = gi < i_end ? col_q(a, gi) : 0.f;
         }
-        rank_f32x16 acc[UB];
+        f32x16 acc[UB];
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
 #pragma unroll
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(256) void softmax_full_grad_kernel(const SoftmaxSid
     if (!INBATCH && tid < GT) sCnt[tid] = 0;
     int cnt_local = 0;
 
-    rank_f32x16 out_acc[4];
+    f32x16 out_acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void softmax_full_grad_kernel(const SoftmaxSid
             }
         }
         // phase 1: the score tile, as the forward computes it
-        rank_f32x16 acc;
+        f32x16 acc;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.f;
         for (int c = 0; c < n_chunks; ++c, ++step) {

@@ -175,7 +175,6 @@ bool swept_usable(const ngcf_csr *c, int64_t ldE, int d)
     return true;
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef NGCF_SWEPT_LABW
 #define NGCF_SWEPT_LABW 2      // loads allowed in flight when the adds of a half-chunk begin (see load_entries below)
 #endif

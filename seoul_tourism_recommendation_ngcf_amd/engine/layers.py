@@ -1,5 +1,5 @@
 """The wrappers of the training step's hot path, a dozen calls per step: the header's sections "propagation" (csrc/spmm*.hip,
-csrc/dense.hip), "feature injection", "gathers" and "BPR" (csrc/ops.hip).  They stay short: no check here may cost a host sync or
+csrc/dense*.hip), "feature injection", "gathers" and "BPR" (csrc/ops.hip).  They stay short: no check here may cost a host sync or
 more than a few comparisons (see `_on` and `_stream`)."""
 from __future__ import annotations
 

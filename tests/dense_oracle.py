@@ -1,5 +1,5 @@
 """Host oracle of the dense half of a layer (NGCF.py:131-146) as include/ngcf_hip.h defines it, in numpy / CPU torch, written from the
-header and the comments of csrc/dense.hip and csrc/common.h - no code shared with the product, nothing here runs on a GPU.
+header and the comments of csrc/dense*.hip, csrc/dense_device.h and csrc/common.h - no code shared with the product, nothing here runs on a GPU.
 tests/test_dense_oracle.py checks it on the CPU; tests/test_dense_paths_gpu.py holds every forward kernel to it and
 tests/test_dense_split_gpu.py imports the fp64 form's bounds.
 
