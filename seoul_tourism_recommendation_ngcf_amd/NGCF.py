@@ -194,6 +194,20 @@ class NGCF(nn.Module):
             self._scratch = torch.full((self.n_user,), -1, dtype=torch.int32, device=dev)
         return self._scratch
 
+    def _feature_tables(self):
+        return (self.age_emb.weight.data, self.sex_emb.weight.data, self.month_emb.weight.data, self.day_emb.weight.data,
+                self.dow_emb.weight.data)
+
+    def _inject_features(self, features, u_idx: torch.Tensor, status: torch.Tensor):
+        """NGCF.py:103-115 for all of `u_idx` at once: `features` = (age, sex, month, day, dow) into `user_embedding.weight.data`, no
+        autograd.  A `.data` write: the retained all_E is told which rows to follow (`E0Cache.touch`), here and nowhere else.
+        Returns `engine.feature_inject`'s keep-alive (the converted index tensors), held by the caller as long as it sees fit."""
+        with torch.no_grad():
+            keep = _eng.feature_inject(self.user_embedding.weight.data, self._feature_tables(), features, u_idx, self.emb_ratio,
+                                       self._scratch_buf(self._dev()), status)
+            self._e0_cache.touch(u_idx)
+        return keep
+
     def laplacian_csr(self, year_idx: int) -> "_eng.LaplacianCSR":
         """CSR of `lap_list[year_idx]`, built once and cached (replaces the per-call `.to(device)`, NGCF.py:118)."""
         dev = self._dev()
@@ -402,13 +416,7 @@ class NGCF(nn.Module):
                 return out
         # feature injection into user_embedding.weight.data, no autograd (NGCF.py:103-115)
         u_idx = u_id.to(device=dev, dtype=torch.int64).contiguous()
-        with torch.no_grad():
-            keep = _eng.feature_inject(
-                self.user_embedding.weight.data,
-                (self.age_emb.weight.data, self.sex_emb.weight.data, self.month_emb.weight.data,
-                 self.day_emb.weight.data, self.dow_emb.weight.data),
-                (age, sex, month, day, dow), u_idx, self.emb_ratio, self._scratch_buf(dev), status)
-        self._e0_cache.touch(u_idx)                                    # (a `.data` write: the retained all_E follows these rows)
+        keep = self._inject_features((age, sex, month, day, dow), u_idx, status)
 
         year_idx = self._year_index(year)                              # == year.unique()[0] % 18, NGCF.py:117
         self.propagate(year_idx, bool(node_flag))

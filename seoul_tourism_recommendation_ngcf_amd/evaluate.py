@@ -10,6 +10,8 @@ and novelty of the items' exposure and the intra-list diversity (engine.lists).
 The reference's own test protocol - one user against a short candidate list whose first entry is the held-out item, Test-BPR / HR@3 /
 NDCG@ks / RMSE (Experiment.eval, experiment.py:66-119) - is `candidate_ranking`: one propagation per year and one launch per chunk
 of cases (engine.eval_candidates) in place of a forward, a mm, two topk and five read-backs per case.
+What the four share with `recommend.py` - eval mode under no_grad and the caller's mode restored, the propagate, the chunk loop, the
+status word and its one read-back - is `serving.py`; each body below is what is particular to it.
 """
 from __future__ import annotations
 
@@ -17,16 +19,9 @@ from typing import Optional, Sequence, Union
 
 import torch
 
-from . import engine
+from . import engine, serving
 
 _Sets = Union["engine.ItemSets", tuple]
-
-
-def _as_sets(s, n_user: int, n_item: int, dev) -> "engine.ItemSets":
-    if isinstance(s, engine.ItemSets):
-        return s
-    users, items = s[0], s[1]                       # (users, items[, weights]) pairs
-    return engine.ItemSets.from_pairs(users.to(dev), items.to(dev), n_user, n_item)
 
 
 def full_ranking(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0,
@@ -39,72 +34,48 @@ def full_ranking(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), ye
     "users": number of users with a non-empty test row}."""
     ks = [int(x) for x in ks]
     k = max(ks)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            model.propagate(year_idx)
-            U, I = model.all_users_emb, model.all_items_emb
-            dev = U.device
-            n_user, n_item = int(U.shape[0]), int(I.shape[0])
-            excl = _as_sets(train, n_user, n_item, dev)
-            truth = _as_sets(test, n_user, n_item, dev)
-            if users is None:
-                users = torch.arange(n_user, device=dev, dtype=torch.int64)
-            users = users.reshape(-1).to(device=dev, dtype=torch.int64)
-            sums = torch.zeros(4 * len(ks) + 1, dtype=torch.float64, device=dev)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            for c0 in range(0, int(users.numel()), int(user_chunk)):
-                ids = users[c0:c0 + int(user_chunk)]
-                _, top = engine.rank_topk(U, I, k, user_ids=ids, exclude=excl, status=status)
-                engine.ranking_metrics(top, truth, ks, user_ids=ids, sums=sums, status=status)
-            if int(status.item()) != 0:
-                raise IndexError(f"full_ranking: a user id lies outside [0, {n_user})")
-            return engine.metrics_from_sums(sums, ks)
-    finally:
-        model.train(was_training)
+    with serving.inference(model):
+        t = serving.propagated(model, year_idx)
+        excl, truth = serving.as_sets(train, t), serving.as_sets(test, t)
+        users = serving.ids_or_all(users, t.n_user, t.dev)
+        sums = torch.zeros(4 * len(ks) + 1, dtype=torch.float64, device=t.dev)
+        status = serving.status_word(t.dev)
+        for sl in serving.chunks(users.numel(), user_chunk):
+            ids = users[sl]
+            _, top = engine.rank_topk(t.U, t.I, k, user_ids=ids, exclude=excl, status=status)
+            engine.ranking_metrics(top, truth, ks, user_ids=ids, sums=sums, status=status)
+        if serving.read_back(status)[0] != 0:
+            raise IndexError(f"full_ranking: a user id lies outside [0, {t.n_user})")
+        return engine.metrics_from_sums(sums, ks)
 
 
 def full_ranks(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0,
                users: Optional[torch.Tensor] = None, user_chunk: int = 65536, return_positions: bool = False):
     """`full_ranking` without the top list's horizon: the exact position of every held-out item of `test` among its user's eligible
     items (engine.ranks.rank_positions; the items of `train` are not eligible) and from the positions MRR, MAP, AUC, the uncut
-    NDCG and the @K metrics for any K in [1, n_item] (engine.ranks.position_metrics).  Same plumbing as `full_ranking`: one
-    propagate in eval mode under no_grad, the caller's mode restored, `user_chunk` users per launch against strided views of all_E,
-    one read-back at the end.  Returns {"mrr", "map", "auc", "ndcg", "recall@K", "ndcg@K", "precision@K", "hr@K", "users",
-    "auc_users"}; with `return_positions` the tuple (that dict, the int32 positions - -2 for users that were not ranked -, the truth
-    ItemSets whose `colidx` they align with)."""
+    NDCG and the @K metrics for any K in [1, n_item] (engine.ranks.position_metrics).  Same plumbing as `full_ranking` (`serving.py`):
+    `user_chunk` users per launch against strided views of all_E, one read-back at the end.  Returns {"mrr", "map", "auc", "ndcg",
+    "recall@K", "ndcg@K", "precision@K", "hr@K", "users", "auc_users"}; with `return_positions` the tuple (that dict, the int32
+    positions - -2 for users that were not ranked -, the truth ItemSets whose `colidx` they align with)."""
     ks = [int(x) for x in ks]
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            model.propagate(year_idx)
-            U, I = model.all_users_emb, model.all_items_emb
-            dev = U.device
-            n_user, n_item = int(U.shape[0]), int(I.shape[0])
-            excl = _as_sets(train, n_user, n_item, dev)
-            truth = _as_sets(test, n_user, n_item, dev)
-            if users is None:
-                users = torch.arange(n_user, device=dev, dtype=torch.int64)
-            users = users.reshape(-1).to(device=dev, dtype=torch.int64)
-            sums = torch.zeros(4 + 4 * len(ks) + 2, dtype=torch.float64, device=dev)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            position = torch.full((int(truth.colidx.numel()),), engine.ranks.NOT_RANKED, dtype=torch.int32, device=dev)
-            for c0 in range(0, int(users.numel()), int(user_chunk)):
-                ids = users[c0:c0 + int(user_chunk)]
-                engine.ranks.rank_positions(U, I, truth, user_ids=ids, exclude=excl, out=position, status=status)
-                engine.ranks.position_metrics(position, truth, ks, n_item, exclude=excl, user_ids=ids, sums=sums, status=status)
-            host = torch.cat((sums, status.double())).cpu()            # the one read-back
-            word = int(host[-1])
-            if word & 4:
-                raise RuntimeError("full_ranks: `users` repeats users with long test rows past the workspace; use a smaller user_chunk")
-            if word != 0:
-                raise IndexError(f"full_ranks: a user id lies outside [0, {n_user}) or a held-out item outside [0, {n_item})")
-            out = engine.ranks.position_metrics_from_sums(host[:-1], ks)
-            return (out, position, truth) if return_positions else out
-    finally:
-        model.train(was_training)
+    with serving.inference(model):
+        t = serving.propagated(model, year_idx)
+        excl, truth = serving.as_sets(train, t), serving.as_sets(test, t)
+        users = serving.ids_or_all(users, t.n_user, t.dev)
+        sums = torch.zeros(4 + 4 * len(ks) + 2, dtype=torch.float64, device=t.dev)
+        status = serving.status_word(t.dev)
+        position = torch.full((int(truth.colidx.numel()),), engine.ranks.NOT_RANKED, dtype=torch.int32, device=t.dev)
+        for sl in serving.chunks(users.numel(), user_chunk):
+            ids = users[sl]
+            engine.ranks.rank_positions(t.U, t.I, truth, user_ids=ids, exclude=excl, out=position, status=status)
+            engine.ranks.position_metrics(position, truth, ks, t.n_item, exclude=excl, user_ids=ids, sums=sums, status=status)
+        word, host = serving.read_back(status, sums)
+        if word & 4:
+            raise RuntimeError("full_ranks: `users` repeats users with long test rows past the workspace; use a smaller user_chunk")
+        if word != 0:
+            raise IndexError(f"full_ranks: a user id lies outside [0, {t.n_user}) or a held-out item outside [0, {t.n_item})")
+        out = engine.ranks.position_metrics_from_sums(host, ks)
+        return (out, position, truth) if return_positions else out
 
 
 def list_quality(model, train: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0, user_ids: Optional[torch.Tensor] = None,
@@ -125,55 +96,44 @@ def list_quality(model, train: _Sets, ks: Sequence[int] = (20,), year_idx: int =
     if len(div_ks) > engine.lists.DIVERSITY_KS_MAX:
         raise ValueError(f"list_quality: at most {engine.lists.DIVERSITY_KS_MAX} cut-offs up to {engine.lists.DIVERSITY_K_MAX}")
     k = max(ks)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            model.propagate(year_idx)
-            U, I = model.all_users_emb, model.all_items_emb
-            dev = U.device
-            n_user, n_item = int(U.shape[0]), int(I.shape[0])
-            excl = _as_sets(train, n_user, n_item, dev)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            popularity = engine.lists.exposure_counts((excl.colidx.to(torch.int64) - excl.col_offset).reshape(-1, 1), n_item,
-                                                      status=status)
-            counts = [torch.zeros(n_item, dtype=torch.int64, device=dev) for _ in ks]
-            div = torch.zeros(2 * len(div_ks), dtype=torch.float64, device=dev)
+    with serving.inference(model):
+        t = serving.propagated(model, year_idx)
+        excl = serving.as_sets(train, t)
+        status = serving.status_word(t.dev)
+        popularity = engine.lists.exposure_counts((excl.colidx.to(torch.int64) - excl.col_offset).reshape(-1, 1), t.n_item, status=status)
+        counts = [torch.zeros(t.n_item, dtype=torch.int64, device=t.dev) for _ in ks]
+        div = torch.zeros(2 * len(div_ks), dtype=torch.float64, device=t.dev)
 
-            def add(top):
-                for K, c in zip(ks, counts):
-                    engine.lists.exposure_counts(top, n_item, k=K, out=c, status=status)
-                if div_ks:
-                    engine.lists.list_diversity(top, I, div_ks, sums=div, status=status)
+        def add(top):
+            for K, c in zip(ks, counts):
+                engine.lists.exposure_counts(top, t.n_item, k=K, out=c, status=status)
+            if div_ks:
+                engine.lists.list_diversity(top, t.I, div_ks, sums=div, status=status)
 
-            if lists is not None:
-                lists = lists.to(device=dev, dtype=torch.int64)
-                if lists.dim() != 2 or int(lists.shape[1]) < k:
-                    raise ValueError(f"list_quality: lists must be [G, >= {k}], got {tuple(lists.shape)}")
-                n_lists = int(lists.shape[0])
-                add(lists)
-            else:
-                if user_ids is None:
-                    user_ids = torch.arange(n_user, device=dev, dtype=torch.int64)
-                user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64)
-                n_lists = int(user_ids.numel())
-                for c0 in range(0, n_lists, int(user_chunk)):
-                    _, top = engine.rank_topk(U, I, k, user_ids=user_ids[c0:c0 + int(user_chunk)], exclude=excl, status=status)
-                    add(top)
-            words = [engine.lists.exposure_summary_launch(c, popularity, n_user) for c in counts]
-            host = torch.cat(words + [div.view(torch.int64), status.to(torch.int64)]).cpu()          # the one read-back
-            if int(host[-1]) != 0:
-                raise IndexError(f"list_quality: a user id lies outside [0, {n_user}) or a list entry is not below {n_item}")
-            means = engine.lists.diversity_from_sums(host[6 * len(ks):-1].view(torch.float64), div_ks) if div_ks else {}
-            out = {}
-            for q, K in enumerate(ks):
-                fig = engine.lists.exposure_figures(host[6 * q:6 * q + 6].tolist(), n_item)
-                out[K] = {name: fig[name] for name in ("coverage", "gini", "entropy", "novelty")}
-                out[K]["ild"] = means.get(f"ild@{K}", float("nan"))
-                out[K]["users"] = n_lists
-            return out
-    finally:
-        model.train(was_training)
+        if lists is not None:
+            lists = lists.to(device=t.dev, dtype=torch.int64)
+            if lists.dim() != 2 or int(lists.shape[1]) < k:
+                raise ValueError(f"list_quality: lists must be [G, >= {k}], got {tuple(lists.shape)}")
+            n_lists = int(lists.shape[0])
+            add(lists)
+        else:
+            user_ids = serving.ids_or_all(user_ids, t.n_user, t.dev)
+            n_lists = int(user_ids.numel())
+            for sl in serving.chunks(n_lists, user_chunk):
+                _, top = engine.rank_topk(t.U, t.I, k, user_ids=user_ids[sl], exclude=excl, status=status)
+                add(top)
+        words = [engine.lists.exposure_summary_launch(c, popularity, t.n_user) for c in counts]
+        word, host = serving.read_back(status, *words, div.view(torch.int64))        # int64 words: the fp64 sums travel as their bits
+        if word != 0:
+            raise IndexError(f"list_quality: a user id lies outside [0, {t.n_user}) or a list entry is not below {t.n_item}")
+        means = engine.lists.diversity_from_sums(host[6 * len(ks):].view(torch.float64), div_ks) if div_ks else {}
+        out = {}
+        for q, K in enumerate(ks):
+            fig = engine.lists.exposure_figures(host[6 * q:6 * q + 6].tolist(), t.n_item)
+            out[K] = {name: fig[name] for name in ("coverage", "gini", "entropy", "novelty")}
+            out[K]["ild"] = means.get(f"ild@{K}", float("nan"))
+            out[K]["users"] = n_lists
+        return out
 
 
 def candidate_ranking(model, user_ids: torch.Tensor, candidates: torch.Tensor, *, year=None, features=None,
@@ -206,63 +166,50 @@ def candidate_ranking(model, user_ids: torch.Tensor, candidates: torch.Tensor, *
     reference's data) from the second epoch on; equivalently this function equals the SECOND pass of the reference's loop over the
     same cases."""
     ks = [int(x) for x in ks]
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            dev = model._dev()
-            user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-            candidates = candidates.to(device=dev, dtype=torch.int64)
-            T = int(user_ids.numel())
-            if candidates.dim() != 2 or int(candidates.shape[0]) != T:
-                raise ValueError(f"candidate_ranking: candidates must be [T = {T}, C], got {tuple(candidates.shape)}")
-            C = int(candidates.shape[1])
-            if ratings is not None:
-                ratings = ratings.reshape(-1).to(device=dev, dtype=torch.float32)
-            wd, bs = (float(criterion.weight_decay), float(criterion.batch_size)) if criterion is not None else (0.0, 1.0)
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            if features is not None:                                   # NGCF.py:103-115, all cases at once
-                if len(features) != 5:
-                    raise ValueError("candidate_ranking: features = (age, sex, month, day, dow)")
-                keep = engine.feature_inject(
-                    model.user_embedding.weight.data,
-                    (model.age_emb.weight.data, model.sex_emb.weight.data, model.month_emb.weight.data,
-                     model.day_emb.weight.data, model.dow_emb.weight.data),
-                    features, user_ids, model.emb_ratio, model._scratch_buf(dev), status)
-                model._e0_cache.touch(user_ids)
-                del keep
-            # cases by Laplacian slice
-            year_h = None if year is None else torch.as_tensor(year).reshape(-1).cpu()
-            if year_h is None or int(year_h.numel()) == 1:
-                groups = [(0 if year_h is None else model._year_index(year_h), None)]
-            else:
-                if int(year_h.numel()) != T:
-                    raise ValueError(f"candidate_ranking: {int(year_h.numel())} years for {T} cases")
-                idx_of = {int(v): model._year_index(torch.tensor([int(v)])) for v in torch.unique(year_h).tolist()}
-                case_idx = torch.tensor([idx_of[int(v)] for v in year_h.tolist()], dtype=torch.int64)
-                groups = [(y, (case_idx == y).nonzero().flatten().to(dev)) for y in sorted(set(idx_of.values()))]
-            sums = torch.zeros(len(ks) + 4, dtype=torch.float64, device=dev)
-            scores = torch.empty((T, C), dtype=torch.float32, device=dev) if return_scores else None
-            position = torch.empty((T,), dtype=torch.int32, device=dev) if return_scores else None
-            for y, sel in groups:
-                model.propagate(y)
-                U, I = model.all_users_emb, model.all_items_emb
-                uid, cand, rat = ((user_ids, candidates, ratings) if sel is None else
-                                  (user_ids[sel], candidates[sel], None if ratings is None else ratings[sel]))
-                for c0 in range(0, int(uid.numel()), int(case_chunk)):
-                    sl = slice(c0, c0 + int(case_chunk))
-                    _, pos, sc = engine.eval_candidates(U, I, uid[sl], cand[sl], None if rat is None else rat[sl], ks, hit_k, wd, bs,
-                                                        user_repeat, sums=sums, status=status, return_scores=return_scores,
-                                                        return_position=return_scores)
-                    if return_scores:
-                        dst = sl if sel is None else sel[sl]
-                        scores[dst], position[dst] = sc, pos
-            host = torch.cat((sums, status.double())).cpu()            # the one read-back
-            if int(host[-1]) != 0:
-                raise IndexError("candidate_ranking: a user id, a candidate or a feature id is out of range")
-            out = engine.candidate_metrics_from_sums(host[:-1], ks, hit_k)
-            if criterion is None:
-                del out["bpr"]
-            return (out, scores, position) if return_scores else out
-    finally:
-        model.train(was_training)
+    with serving.inference(model):
+        dev = model._dev()
+        user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        candidates = candidates.to(device=dev, dtype=torch.int64)
+        T = int(user_ids.numel())
+        if candidates.dim() != 2 or int(candidates.shape[0]) != T:
+            raise ValueError(f"candidate_ranking: candidates must be [T = {T}, C], got {tuple(candidates.shape)}")
+        C = int(candidates.shape[1])
+        if ratings is not None:
+            ratings = ratings.reshape(-1).to(device=dev, dtype=torch.float32)
+        wd, bs = (float(criterion.weight_decay), float(criterion.batch_size)) if criterion is not None else (0.0, 1.0)
+        status = serving.status_word(dev)
+        if features is not None:                                       # NGCF.py:103-115, all cases at once
+            if len(features) != 5:
+                raise ValueError("candidate_ranking: features = (age, sex, month, day, dow)")
+            model._inject_features(features, user_ids, status)         # (its keep-alive is dropped here, as before)
+        # cases by Laplacian slice
+        one, year_h = serving.year_slice(model, year)
+        if one is not None:
+            groups = [(one, None)]
+        else:
+            if int(year_h.numel()) != T:
+                raise ValueError(f"candidate_ranking: {int(year_h.numel())} years for {T} cases")
+            idx_of = {int(v): serving.year_slice(model, int(v))[0] for v in torch.unique(year_h).tolist()}
+            case_idx = torch.tensor([idx_of[int(v)] for v in year_h.tolist()], dtype=torch.int64)
+            groups = [(y, (case_idx == y).nonzero().flatten().to(dev)) for y in sorted(set(idx_of.values()))]
+        sums = torch.zeros(len(ks) + 4, dtype=torch.float64, device=dev)
+        scores = torch.empty((T, C), dtype=torch.float32, device=dev) if return_scores else None
+        position = torch.empty((T,), dtype=torch.int32, device=dev) if return_scores else None
+        for y, sel in groups:
+            t = serving.propagated(model, y)
+            uid, cand, rat = ((user_ids, candidates, ratings) if sel is None else
+                              (user_ids[sel], candidates[sel], None if ratings is None else ratings[sel]))
+            for sl in serving.chunks(uid.numel(), case_chunk):
+                _, pos, sc = engine.eval_candidates(t.U, t.I, uid[sl], cand[sl], None if rat is None else rat[sl], ks, hit_k, wd, bs,
+                                                    user_repeat, sums=sums, status=status, return_scores=return_scores,
+                                                    return_position=return_scores)
+                if return_scores:
+                    dst = sl if sel is None else sel[sl]
+                    scores[dst], position[dst] = sc, pos
+        word, host = serving.read_back(status, sums)
+        if word != 0:
+            raise IndexError("candidate_ranking: a user id, a candidate or a feature id is out of range")
+        out = engine.candidate_metrics_from_sums(host, ks, hit_k)
+        if criterion is None:
+            del out["bpr"]
+        return (out, scores, position) if return_scores else out

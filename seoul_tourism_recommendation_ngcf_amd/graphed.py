@@ -110,9 +110,7 @@ class GraphedForward:
     def _body(self):
         m, i = self.model, self.inputs
         with torch.no_grad():
-            _eng.feature_inject(m.user_embedding.weight.data,
-                                (m.age_emb.weight.data, m.sex_emb.weight.data, m.month_emb.weight.data,
-                                 m.day_emb.weight.data, m.dow_emb.weight.data),
+            _eng.feature_inject(m.user_embedding.weight.data, m._feature_tables(),
                                 (i["age"], i["sex"], i["month"], i["day"], i["dow"]), i["u_id"], m.emb_ratio,
                                 self.scratch, self.status)
             w1, b1, w2, b2 = m._layer_params()

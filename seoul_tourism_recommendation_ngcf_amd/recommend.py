@@ -19,8 +19,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from . import engine
-from .evaluate import _as_sets
+from . import engine, serving
 
 
 def demo_views(user_ids: torch.Tensor, age: torch.Tensor, sex: torch.Tensor, month: torch.Tensor, day: torch.Tensor):
@@ -118,7 +117,7 @@ def blended_ranking(model, user_ids: torch.Tensor, *, features=None, year=None, 
     rating descending, ties lowest item first; slots past the eligible items are (-1, -inf).
 
       features    (age, sex, month, day, dow), one entry per request row, or None: no injection (NGCF.py:103-115; one
-                  `engine.feature_inject` call for all rows, as `evaluate.candidate_ranking`).
+                  `NGCF._inject_features` call for all rows).
       year        None (Laplacian slice 0) or one year: slice `model._year_index` of it (the demo passes [0]).
       columns     None: one column per distinct user id in ascending id order (`df_daily_user`, the reference's live view), the ids
                   are returned too; an int64 [R] vector of column numbers; or a (rowptr, rows) CSR, e.g. `demo_views`' - a row
@@ -143,60 +142,44 @@ def blended_ranking(model, user_ids: torch.Tensor, *, features=None, year=None, 
     request row); here the integer sums come first, then three products.  With weights that are exact in binary (0.5 / 0.25 /
     0.25) the two are equal; otherwise they differ by rounding only, at most 3 * rows_in_column * 2^-52 relative for non-negative
     weights (every term is then non-negative)."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            dev = model._dev()
-            user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-            R = int(user_ids.numel())
-            if len(weights) != 3:
-                raise ValueError("blended_ranking: weights = (w_pref, w_con, w_dis)")
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            if features is not None:                                   # NGCF.py:103-115, all rows at once
-                if len(features) != 5:
-                    raise ValueError("blended_ranking: features = (age, sex, month, day, dow)")
-                keep = engine.feature_inject(
-                    model.user_embedding.weight.data,
-                    (model.age_emb.weight.data, model.sex_emb.weight.data, model.month_emb.weight.data,
-                     model.day_emb.weight.data, model.dow_emb.weight.data),
-                    features, user_ids, model.emb_ratio, model._scratch_buf(dev), status)
-                model._e0_cache.touch(user_ids)
-                del keep
-            year_h = None if year is None else torch.as_tensor(year).reshape(-1).cpu()
-            if year_h is not None and int(year_h.numel()) != 1:
-                raise ValueError("blended_ranking: year is a single value")
-            model.propagate(0 if year_h is None else model._year_index(year_h))
-            U, I = model.all_users_emb, model.all_items_emb
-            n_user, n_item = int(U.shape[0]), int(I.shape[0])
-            Pl = min(int(points), n_item)
-            excl = None if exclude is None else _as_sets(exclude, n_user, n_item, dev)
-            rowptr, rows, ids = _columns_csr(columns, user_ids)
-            con, con_slot = _context_lists(congestion, congestion_slot, R, Pl, n_item, dev, "congestion")
-            dis, dis_slot = _context_lists(distance, distance_slot, R, Pl, n_item, dev, "distance")
-            if item_mask is not None:
-                item_mask = item_mask.to(dev)
-            pref = None
-            for c0 in range(0, R, int(row_chunk)):
-                _, idx = engine.rank_topk(U, I, Pl, user_ids=user_ids[c0:c0 + int(row_chunk)], exclude=excl, status=status)
-                if R <= int(row_chunk):
-                    pref = idx
-                else:
-                    if pref is None:
-                        pref = torch.empty((R, Pl), dtype=torch.int64, device=dev)
-                    pref[c0:c0 + int(row_chunk)] = idx
+    with serving.inference(model):
+        dev = model._dev()
+        user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        R = int(user_ids.numel())
+        if len(weights) != 3:
+            raise ValueError("blended_ranking: weights = (w_pref, w_con, w_dis)")
+        status = serving.status_word(dev)
+        if features is not None:                                       # NGCF.py:103-115, all rows at once
+            if len(features) != 5:
+                raise ValueError("blended_ranking: features = (age, sex, month, day, dow)")
+            model._inject_features(features, user_ids, status)         # (its keep-alive is dropped here, as before)
+        y, _ = serving.year_slice(model, year)
+        if y is None:
+            raise ValueError("blended_ranking: year is a single value")
+        t = serving.propagated(model, y)
+        Pl = min(int(points), t.n_item)
+        excl = None if exclude is None else serving.as_sets(exclude, t)
+        rowptr, rows, ids = _columns_csr(columns, user_ids)
+        con, con_slot = _context_lists(congestion, congestion_slot, R, Pl, t.n_item, dev, "congestion")
+        dis, dis_slot = _context_lists(distance, distance_slot, R, Pl, t.n_item, dev, "distance")
+        if item_mask is not None:
+            item_mask = item_mask.to(dev)
+        cuts = list(serving.chunks(R, row_chunk))
+        pref = None if len(cuts) == 1 else torch.empty((R, Pl), dtype=torch.int64, device=dev)
+        for sl in cuts:
+            _, idx = engine.rank_topk(t.U, t.I, Pl, user_ids=user_ids[sl], exclude=excl, status=status)
             if pref is None:
-                pref = torch.empty((0, Pl), dtype=torch.int64, device=dev)
-            out = engine.blend_points(pref, rowptr, rows, n_item, points=int(points), weights=weights, con=con, con_slot=con_slot,
-                                      dis=dis, dis_slot=dis_slot, item_mask=item_mask, top=int(top), return_table=return_table,
-                                      status=status)
-            if int(status.item()) != 0:                                # the one read-back
-                raise IndexError("blended_ranking: a user id, a feature id, a context slot or a column's row index is out of range")
-            if ids is not None:
-                out = out[:2] + (ids,) + out[2:]
-            return out
-    finally:
-        model.train(was_training)
+                pref = idx                                             # one chunk: rank_topk's own tensor, no copy
+            else:
+                pref[sl] = idx
+        out = engine.blend_points(pref, rowptr, rows, t.n_item, points=int(points), weights=weights, con=con, con_slot=con_slot,
+                                  dis=dis, dis_slot=dis_slot, item_mask=item_mask, top=int(top), return_table=return_table,
+                                  status=status)
+        if serving.read_back(status)[0] != 0:
+            raise IndexError("blended_ranking: a user id, a feature id, a context slot or a column's row index is out of range")
+        if ids is not None:
+            out = out[:2] + (ids,) + out[2:]
+        return out
 
 
 def diversified_ranking(model, user_ids: torch.Tensor, *, train=None, lam: float = 0.7, pool: int = 64, top: int = 10,
@@ -232,32 +215,24 @@ def diversified_ranking(model, user_ids: torch.Tensor, *, train=None, lam: float
         raise ValueError(f"{fn}: user_chunk={user_chunk}")
     if not isinstance(user_ids, torch.Tensor) or user_ids.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"{fn}: user_ids must be an int32 or int64 tensor")
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            model.propagate(year_idx)
-            U, I = model.all_users_emb, model.all_items_emb
-            dev = U.device
-            n_user, n_item = int(U.shape[0]), int(I.shape[0])
-            n = min(pool, n_item)
-            if top > n:
-                raise ValueError(f"{fn}: top={top} above the pool of {n} entries (the catalogue has {n_item} items)")
-            excl = None if train is None else _as_sets(train, n_user, n_item, dev)
-            user_ids = user_ids.reshape(-1).to(device=dev, dtype=torch.int64)
-            B = int(user_ids.numel())
-            status = torch.zeros(1, dtype=torch.int32, device=dev)
-            items = torch.empty((B, top), dtype=torch.int64, device=dev)
-            keys = torch.empty((B, top), dtype=torch.float64, device=dev)
-            for c0 in range(0, B, user_chunk):
-                vals, idx = engine.rank_topk(U, I, n, user_ids=user_ids[c0:c0 + user_chunk], exclude=excl, status=status)
-                items[c0:c0 + user_chunk], keys[c0:c0 + user_chunk] = engine.lists.mmr_rerank(
-                    idx, vals, I, top, lam=lam, normalize=normalize, return_keys=True, status=status)
-            if int(status.item()) != 0:                                # the one read-back
-                raise IndexError(f"{fn}: a user id lies outside [0, {n_user})")
-            return items, keys
-    finally:
-        model.train(was_training)
+    with serving.inference(model):
+        t = serving.propagated(model, year_idx)
+        n = min(pool, t.n_item)
+        if top > n:
+            raise ValueError(f"{fn}: top={top} above the pool of {n} entries (the catalogue has {t.n_item} items)")
+        excl = None if train is None else serving.as_sets(train, t)
+        user_ids = user_ids.reshape(-1).to(device=t.dev, dtype=torch.int64)
+        B = int(user_ids.numel())
+        status = serving.status_word(t.dev)
+        items = torch.empty((B, top), dtype=torch.int64, device=t.dev)
+        keys = torch.empty((B, top), dtype=torch.float64, device=t.dev)
+        for sl in serving.chunks(B, user_chunk):
+            vals, idx = engine.rank_topk(t.U, t.I, n, user_ids=user_ids[sl], exclude=excl, status=status)
+            items[sl], keys[sl] = engine.lists.mmr_rerank(idx, vals, t.I, top, lam=lam, normalize=normalize, return_keys=True,
+                                                          status=status)
+        if serving.read_back(status)[0] != 0:
+            raise IndexError(f"{fn}: a user id lies outside [0, {t.n_user})")
+        return items, keys
 
 
 # ---- the trip context from raw rows: what demo.py builds between its pickles and the blend -------------------------------------------

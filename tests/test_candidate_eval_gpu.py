@@ -323,3 +323,40 @@ def test_candidate_ranking_reproduces_the_reference_loop():
     with pytest.raises(RuntimeError, match="out of range"):
         pkg.evaluate.candidate_ranking(fresh, uid, cand, ks=(21,))
     assert math.isfinite(one["bpr"]) and one["rmse"] == 0.0
+
+
+def test_candidate_ranking_injection_reaches_the_retained_all_E():
+    """`NGCF._inject_features` tells the E0 cache which rows it rewrote: an inference forward retains its all_E, `candidate_ranking`
+    injects other users' rows through `.data`, and the next forward - on the SAME buffer - equals a forward of a fresh model loaded
+    with the post-injection state, bit for bit."""
+    import seoul_tourism_recommendation_ngcf_amd as pkg
+    model, uid, cand, _, feats, _ = _loop_setup(DEV)
+    model.eval()
+    model.auto_graph = False                                            # the eager inference path: the one that retains all_E
+    seen = set(uid.tolist())
+    u = torch.tensor([x for x in range(2000) if x not in seen][:8])      # the forward's own users: none of the injected ones
+    batch = dict(year=torch.full((8,), 18), u_id=u, age=u % 76, sex=u % 2, month=u % 13, day=u % 32, dow=u % 7,
+                 pos_item=torch.arange(8), neg_item=torch.arange(8, 16))
+    batch = {k: v.to(DEV) for k, v in batch.items()}
+
+    def forward(m):
+        with torch.no_grad():
+            return m(node_flag=False, **batch)
+
+    before = forward(model)                                             # (emb_ratio = 1: this batch's own injection is the same every time)
+    ptr = model._all_E.data_ptr()
+    assert model._e0_cache.all_E is model._all_E
+    w0 = model.user_embedding.weight.detach().clone()
+    pkg.evaluate.candidate_ranking(model, uid, cand, features=feats, ks=(10,))
+    assert not torch.equal(model.user_embedding.weight[uid.to(DEV)], w0[uid.to(DEV)])      # the injection moved the cases' rows
+    after = forward(model)
+    assert model._all_E.data_ptr() == ptr                               # retained, not rebuilt: only the touched rows were copied
+    assert torch.equal(model.all_users_emb[:, :65], model.user_embedding.weight)
+    fresh, *_ = _loop_setup(DEV)
+    fresh.load_state_dict(model.state_dict())
+    fresh.eval()
+    fresh.auto_graph = False
+    want = forward(fresh)
+    for got, ref in zip(after, want):
+        assert torch.equal(got, ref)
+    assert not torch.equal(after[1], before[1])                         # and the items' rows did depend on the injected users
