@@ -632,6 +632,57 @@ int ngcf_rank_metrics(const int64_t *top_idx, int64_t B, int k, const int64_t *u
                       const int64_t *truth_rowptr, const int32_t *truth_colidx, int64_t truth_col_offset,
                       const int32_t *ks_host, int n_ks, float *per_user, double *sums, int32_t *status, void *stream);
 
+/* ---- certified two-stage ranking: bf16 shortlist, exact fp32 re-score (csrc/rank_prefilter.hip) ---- */
+/* ngcf_rank_topk_f32's answer for less fp32 matrix work: every (user, item) pair is scored with bf16 MFMA, the approximate score is
+ * turned into an UPPER BOUND of the exact one, the `pool` items with the largest bounds are re-scored exactly, and a per-user
+ * certificate says whether the pool's top-k is provably the catalogue's.  A certified row has ngcf_rank_topk_f32's bits; an
+ * uncertified one has to be ranked again by ngcf_rank_topk_f32 (engine/shortlist.py does).
+ *
+ * The bound.  For fp32 rows u, i of width D let u^, i^ be their bf16 images (round to nearest even, 8 significant bits:
+ * |x^ - x| <= 2^-8 |x|), s the score of ngcf_rank_topk_f32 (one ascending-k fmaf chain from 0) and s~ the bf16 MFMA score of u^, i^
+ * (products exact in fp32, every partial sum within one fp32 ulp of exact, whether the unit truncates or rounds).  Then
+ *     |s - s~| <= (beta - 2^-23) |u| |i|,    beta = 2^-7 + 2^-16 + (4 D + 2) 2^-24    (|.| the Euclidean norm)
+ * - 2^-7 + 2^-16 for the two operand roundings, 4 D 2^-24 for the two accumulation chains (D 2^-24 + 2 D 2^-24 and their second-order
+ * terms, D <= NGCF_RANK_PREFILTER_DMAX), and the last 2^-23 pays for the one rounding of the bound's own evaluation
+ *     ub = fmaf(bu, ni, s~),    ni >= |i| and bu >= beta |u| fp32 values rounded UP (the norm in fp64, its nearest fp32, one ulp up),
+ * so ub >= s for every pair.  The model needs no underflow and no overflow: a row is REGULAR when every element is 0 or has a
+ * magnitude in [2^-40, 2^40] (DESIGN 4.3.22 says why not 2^-60).  An irregular user is never certified; one irregular item in the
+ * table and no user is.
+ *
+ * ngcf_rank_pack_items: the fp32 item table (rows of pitch ldi >= D, as ngcf_rank_topk_f32 takes them) -> out_bf16
+ * [n_items, Dp] bf16 (Dp = D rounded up to NGCF_RANK_PREFILTER_KSTEP, the padding zero; 16-byte aligned), norm_up [n_items] = ni,
+ * flags[0] = 1 iff an item is irregular (else 0).  One pass, reusable while the table is unchanged.
+ *
+ * ngcf_rank_shortlist_bf16: batch rows, user_ids, exclusion sets and *status as in ngcf_rank_topk_f32.  Per batch row the `pool`
+ * (1 <= pool <= NGCF_RANK_POOL_MAX) eligible items with the largest (float_key(ub), item) pairs in ngcf_rank_topk_f32's order (key
+ * descending, item ascending): pool_idx [B, pool] int32, -1 past the eligible items; pool_thr [B] = the pool-th ub, -inf when the
+ * pool is not full; user_flags [B] = 1 for an irregular user row (and for an r outside [0, n_user_rows), whose pool_idx row is
+ * left untouched).  debug_scores (NULL, or float [2, B, n_items]: tests and the lab) receives s~ and ub of every pair.  The
+ * workspace (ngcf_rank_prefilter_workspace_bytes) holds bu and, when the item range is split, the per-split lists.
+ *
+ * ngcf_rank_rescore: per batch row the pool's fp32 item rows are gathered through LDS (no [B, pool, D] buffer), scored with
+ * ngcf_rank_topk_f32's chain (the same bits), sorted in that order, and the best k (1 <= k <= pool) written as ngcf_rank_topk_f32
+ * writes them ((-inf, -1) past the eligible items).  certified[b] = 1 iff the user row and the table are regular AND (the pool is
+ * not full - it then holds every eligible item - OR the k-th exact score is strictly greater than pool_thr[b]); else 0.
+ *
+ * Integer atomics in LDS only (the status word's bit, set for a bad id alone, is the exception all entry points share), no float
+ * atomics: identical from run to run, and a row does not depend on B, the batch order or the item split. */
+#define NGCF_RANK_PREFILTER_KSTEP 16
+#define NGCF_RANK_POOL_MAX 256
+#define NGCF_RANK_PREFILTER_DMAX 4096
+int ngcf_rank_pack_items(const float *items, int64_t ldi, int64_t n_items, int D, void *out_bf16, float *norm_up, int32_t *flags,
+                         void *stream);
+int64_t ngcf_rank_prefilter_workspace_bytes(int64_t B, int64_t n_items, int D, int pool);
+int ngcf_rank_shortlist_bf16(const float *users, int64_t ldu, const int64_t *user_ids, int64_t n_user_rows, int64_t B,
+                             const void *packed_bf16, const float *norm_up, int64_t n_items, int D, int pool,
+                             const int64_t *excl_rowptr, const int32_t *excl_colidx, int64_t excl_col_offset,
+                             int32_t *pool_idx, float *pool_thr, int32_t *user_flags, float *debug_scores, int32_t *status,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int ngcf_rank_rescore(const float *users, int64_t ldu, const int64_t *user_ids, int64_t n_user_rows, int64_t B,
+                      const float *items, int64_t ldi, int64_t n_items, int D, int k, int pool, const int32_t *pool_idx,
+                      const float *pool_thr, const int32_t *user_flags, const int32_t *item_flags, float *out_val, int64_t *out_idx,
+                      uint8_t *certified, void *stream);
+
 /* ---- exact held-out positions (csrc/rank_position.hip) ---- */
 /* The exact rank of every held-out item among its user's eligible items, with no score matrix and no top list.  Batch row b is user
  * r = user_ids ? user_ids[b] : b; the truth set and the optional exclusion set are item sets as above (rowptr int64, colidx int32

@@ -13,7 +13,7 @@ import subprocess
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-SOURCES = [os.path.join(CSRC, f) for f in ("library.hip", "csr.hip", "csr_filter.hip", "spmm.hip", "spmm_swept.hip", "dense.hip", "dense_staged.hip", "dense_persistent.hip", "dense_wide.hip", "ops.hip", "bwd_gather.hip", "bwd_dense.hip", "spmm_t_rows.hip", "comm.hip", "hostrng.hip", "rank.hip", "rank_position.hip", "eval_candidates.hip", "blend.hip", "sample.hip", "sample_hard.hip", "sample_weighted.hip", "quantile.hip", "yeo_johnson.hip", "laplacian.hip", "groupby.hip", "select.hip", "context.hip", "text.hip", "adam.hip", "bpr_multi.hip", "list_quality.hip", "list_rerank.hip", "softmax_full.hip", "sampled_softmax.hip", "inbatch_softmax.hip")]
+SOURCES = [os.path.join(CSRC, f) for f in ("library.hip", "csr.hip", "csr_filter.hip", "spmm.hip", "spmm_swept.hip", "dense.hip", "dense_staged.hip", "dense_persistent.hip", "dense_wide.hip", "ops.hip", "bwd_gather.hip", "bwd_dense.hip", "spmm_t_rows.hip", "comm.hip", "hostrng.hip", "rank.hip", "rank_position.hip", "rank_prefilter.hip", "eval_candidates.hip", "blend.hip", "sample.hip", "sample_hard.hip", "sample_weighted.hip", "quantile.hip", "yeo_johnson.hip", "laplacian.hip", "groupby.hip", "select.hip", "context.hip", "text.hip", "adam.hip", "bpr_multi.hip", "list_quality.hip", "list_rerank.hip", "softmax_full.hip", "sampled_softmax.hip", "inbatch_softmax.hip")]
 HEADERS = [os.path.join(os.path.dirname(PKG_DIR), "include", "ngcf_hip.h"), os.path.join(CSRC, "common.h"),
            os.path.join(CSRC, "spmm_device.h"), os.path.join(CSRC, "dense_device.h"), os.path.join(CSRC, "dd_math.h"), os.path.join(CSRC, "dd_log2.h"),os.path.join(CSRC, "swept_plan.h"),
            os.path.join(CSRC, "cand_device.h"), os.path.join(CSRC, "sample_device.h"), os.path.join(CSRC, "rank_device.h"), os.path.join(CSRC, "loss_rows_device.h"),

@@ -113,6 +113,12 @@ PROTOTYPES = {
     "ngcf_rank_topk_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp,
                                      _vp, _i64, _vp]),
     "ngcf_rank_metrics": (C.c_int, [_vp, _i64, C.c_int, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i32), C.c_int, _vp, _vp, _vp, _vp]),
+    "ngcf_rank_pack_items": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp]),
+    "ngcf_rank_prefilter_workspace_bytes": (_i64, [_i64, _i64, C.c_int, C.c_int]),
+    "ngcf_rank_shortlist_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _i64, _vp]),
+    "ngcf_rank_rescore": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
     "ngcf_rank_positions_workspace_bytes": (_i64, [_i64, _i64, C.c_int, _i64]),
     "ngcf_rank_positions_f32": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
                                           _vp, _vp, _vp, _i64, _vp]),

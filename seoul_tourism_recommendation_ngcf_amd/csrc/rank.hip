@@ -23,57 +23,6 @@
 
 namespace {
 
-// Compaction of the users listed in flist[0..nf): sort each one's CAPP pairs (positions >= count hold padding), keep the best k,
-// pad the rest, set the threshold.  All threads of the workgroup take part; one barrier per bitonic stage.
-template <int CAPP>
-__device__ void rank_compact(uint32_t *bk, int32_t *bi, uint32_t *cnt, uint32_t *thk, int32_t *thi, const int *flist, int nf, int k)
-{
-    const int half = CAPP / 2;
-    const int n_pairs = nf * half;
-    for (int size = 2; size <= CAPP; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int p = threadIdx.x; p < n_pairs; p += blockDim.x) {
-                const int u = flist[p / half], q = p % half;
-                const int a = (q / stride) * (2 * stride) + (q % stride), b = a + stride;
-                uint32_t *K = bk + u * CAPP;
-                int32_t *I = bi + u * CAPP;
-                const bool desc = (a & size) == 0;
-                const uint32_t ka = K[a], kb = K[b];
-                const int32_t ia = I[a], ib = I[b];
-                if (pair_before(ka, ia, kb, ib) != desc) {
-                    K[a] = kb; K[b] = ka;
-                    I[a] = ib; I[b] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int p = threadIdx.x; p < nf * CAPP; p += blockDim.x) {
-        const int u = flist[p / CAPP], pos = p % CAPP;
-        if (pos >= k) {
-            bk[u * CAPP + pos] = kPadKey;
-            bi[u * CAPP + pos] = kPadIdx;
-        }
-    }
-    for (int j = threadIdx.x; j < nf; j += blockDim.x) {
-        const int u = flist[j];
-        if (cnt[u] >= (uint32_t)k) {
-            cnt[u] = (uint32_t)k;
-            thk[u] = bk[u * CAPP + k - 1];
-            thi[u] = bi[u * CAPP + k - 1];
-        }
-    }
-    __syncthreads();
-}
-
-// Batch row b -> user row r (user_ids may be NULL); -1 past the batch, -2 out of range (status set by the caller's rule).
-__device__ inline int64_t rank_user(const int64_t *user_ids, int64_t b, int64_t B, int64_t n_user_rows)
-{
-    if (b >= B) return -1;
-    const int64_t r = user_ids ? user_ids[b] : b;
-    return (r < 0 || r >= n_user_rows) ? -2 : r;
-}
-
 template <int UB>
 __global__ __launch_bounds__(256) void rank_topk_kernel(const float *__restrict__ users, int64_t ldu, const int64_t *__restrict__ user_ids,
                                                         int64_t n_user_rows, int64_t B, const float *__restrict__ items, int64_t ldi,
@@ -239,53 +188,17 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(const float *__restrict_
     }
 }
 
-// Merge of the per-split lists of one batch row (item splits ascending): the same threshold / buffer / compaction, 256 pairs a round.
-__global__ __launch_bounds__(256) void rank_merge_kernel(const uint32_t *__restrict__ part_key, const int32_t *__restrict__ part_idx,
-                                                         int n_splits, int64_t B, int k, const int64_t *__restrict__ user_ids,
-                                                         int64_t n_user_rows, float *__restrict__ out_val, int64_t *__restrict__ out_idx)
-{
-    constexpr int CAPP = 512, ROUND = 256;
-    __shared__ uint32_t bk[CAPP];
-    __shared__ int32_t bi[CAPP];
-    __shared__ uint32_t cnt[1], thk[1];
-    __shared__ int32_t thi[1];
-    __shared__ int flist[1];
-    const int64_t b = blockIdx.x;
-    if (rank_user(user_ids, b, B, n_user_rows) < 0) return;  // status was set by the ranking launch
-    const int tid = threadIdx.x;
-    for (int p = tid; p < CAPP; p += 256) {
-        bk[p] = kPadKey;
-        bi[p] = kPadIdx;
+// What rank_merge_kernel writes for slot j of batch row b: the value and the item, (-inf, -1) past the eligible items.
+struct RankTopkOut {
+    float *val;
+    int64_t *idx;
+    int k;
+    __device__ void operator()(int64_t b, int j, bool has, uint32_t key, int32_t item) const
+    {
+        val[b * k + j] = has ? float_unkey(key) : -INFINITY;
+        idx[b * k + j] = has ? (int64_t)item : -1;
     }
-    if (tid == 0) {
-        cnt[0] = 0;
-        thk[0] = kPadKey;
-        thi[0] = kPadIdx;
-        flist[0] = 0;
-    }
-    __syncthreads();
-    const int64_t total = (int64_t)n_splits * k;
-    for (int64_t r0 = 0; r0 < total; r0 += ROUND) {
-        const int64_t p = r0 + tid;
-        if (p < total) {
-            const int64_t o = ((p / k) * B + b) * k + p % k;
-            const uint32_t key = part_key[o];
-            const int32_t idx = part_idx[o];
-            if (pair_before(key, idx, thk[0], thi[0])) {
-                const uint32_t pos = atomicAdd(&cnt[0], 1u);
-                bk[pos] = key;
-                bi[pos] = idx;
-            }
-        }
-        __syncthreads();
-        if (r0 + ROUND >= total || cnt[0] > (uint32_t)(CAPP - ROUND)) rank_compact<CAPP>(bk, bi, cnt, thk, thi, flist, 1, k);
-    }
-    for (int j = tid; j < k; j += 256) {
-        const bool has = j < (int)cnt[0];
-        out_val[b * k + j] = has ? float_unkey(bk[j]) : -INFINITY;
-        out_idx[b * k + j] = has ? (int64_t)bi[j] : -1;
-    }
-}
+};
 
 struct RankPlan {
     int ub;                 // 32-user blocks per workgroup
@@ -359,7 +272,8 @@ extern "C" int ngcf_rank_topk_f32(const float *users, int64_t ldu, const int64_t
 #undef NGCF_RANK_LAUNCH
     LAUNCH_CHECK();
     if (p.splits > 1) {
-        rank_merge_kernel<<<dim3((unsigned)B), 256, 0, stream>>>(pk, pi, (int)p.splits, B, k, user_ids, n_user_rows, out_val, out_idx);
+        rank_merge_kernel<<<dim3((unsigned)B), 256, 0, stream>>>(pk, pi, (int)p.splits, B, k, user_ids, n_user_rows,
+                                                                 RankTopkOut{out_val, out_idx, k});
         LAUNCH_CHECK();
     }
     return NGCF_OK;

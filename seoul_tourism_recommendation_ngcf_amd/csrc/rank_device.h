@@ -1,4 +1,5 @@
-// What the full-catalogue ranking kernels share (rank.hip, rank_position.hip; the sums and their host tail list_quality.hip too),
+// What the full-catalogue ranking kernels share (rank.hip, rank_position.hip, rank_prefilter.hip; the sums and their host tail
+// list_quality.hip too),
 // defined once so that every kernel that orders, splits, searches or sums does it the same way.
 #ifndef NGCF_RANK_DEVICE_H
 #define NGCF_RANK_DEVICE_H
@@ -58,6 +59,110 @@ inline ItemSplit rank_item_split(int64_t user_tiles, int64_t n_items)
     p.split_items = (tiles + s - 1) / s * kRankIT;
     p.splits = (n_items + p.split_items - 1) / p.split_items;
     return p;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Streaming selection (rank.hip, rank_prefilter.hip): a user's LDS buffer of CAPP (key, item) pairs, a count and a threshold = the
+// current k-th best pair; a pair enters only if it beats the threshold, a buffer that could overflow is compacted.
+// ---------------------------------------------------------------------------------------------
+// Compaction of the users listed in flist[0..nf): sort each one's CAPP pairs (positions >= count hold padding), keep the best k,
+// pad the rest, set the threshold.  All threads of the workgroup take part; one barrier per bitonic stage.
+template <int CAPP>
+__device__ void rank_compact(uint32_t *bk, int32_t *bi, uint32_t *cnt, uint32_t *thk, int32_t *thi, const int *flist, int nf, int k)
+{
+    const int half = CAPP / 2;
+    const int n_pairs = nf * half;
+    for (int size = 2; size <= CAPP; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int p = threadIdx.x; p < n_pairs; p += blockDim.x) {
+                const int u = flist[p / half], q = p % half;
+                const int a = (q / stride) * (2 * stride) + (q % stride), b = a + stride;
+                uint32_t *K = bk + u * CAPP;
+                int32_t *I = bi + u * CAPP;
+                const bool desc = (a & size) == 0;
+                const uint32_t ka = K[a], kb = K[b];
+                const int32_t ia = I[a], ib = I[b];
+                if (pair_before(ka, ia, kb, ib) != desc) {
+                    K[a] = kb; K[b] = ka;
+                    I[a] = ib; I[b] = ia;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int p = threadIdx.x; p < nf * CAPP; p += blockDim.x) {
+        const int u = flist[p / CAPP], pos = p % CAPP;
+        if (pos >= k) {
+            bk[u * CAPP + pos] = kPadKey;
+            bi[u * CAPP + pos] = kPadIdx;
+        }
+    }
+    for (int j = threadIdx.x; j < nf; j += blockDim.x) {
+        const int u = flist[j];
+        if (cnt[u] >= (uint32_t)k) {
+            cnt[u] = (uint32_t)k;
+            thk[u] = bk[u * CAPP + k - 1];
+            thi[u] = bi[u * CAPP + k - 1];
+        }
+    }
+    __syncthreads();
+}
+
+// Batch row b -> user row r (user_ids may be NULL); -1 past the batch, -2 out of range (status set by the caller's rule).
+__device__ inline int64_t rank_user(const int64_t *user_ids, int64_t b, int64_t B, int64_t n_user_rows)
+{
+    if (b >= B) return -1;
+    const int64_t r = user_ids ? user_ids[b] : b;
+    return (r < 0 || r >= n_user_rows) ? -2 : r;
+}
+
+// Merge of the per-split lists of one batch row (item splits ascending): the same threshold / buffer / compaction, 256 pairs a round;
+// out(b, j, has, key, item) writes slot j < k of the merged list (rank.hip: values and items; rank_prefilter.hip: items and threshold).
+template <typename Out>
+__global__ __launch_bounds__(256) void rank_merge_kernel(const uint32_t *__restrict__ part_key, const int32_t *__restrict__ part_idx,
+                                                         int n_splits, int64_t B, int k, const int64_t *__restrict__ user_ids,
+                                                         int64_t n_user_rows, Out out)
+{
+    constexpr int CAPP = 512, ROUND = 256;
+    __shared__ uint32_t bk[CAPP];
+    __shared__ int32_t bi[CAPP];
+    __shared__ uint32_t cnt[1], thk[1];
+    __shared__ int32_t thi[1];
+    __shared__ int flist[1];
+    const int64_t b = blockIdx.x;
+    if (rank_user(user_ids, b, B, n_user_rows) < 0) return;  // status was set by the ranking launch
+    const int tid = threadIdx.x;
+    for (int p = tid; p < CAPP; p += 256) {
+        bk[p] = kPadKey;
+        bi[p] = kPadIdx;
+    }
+    if (tid == 0) {
+        cnt[0] = 0;
+        thk[0] = kPadKey;
+        thi[0] = kPadIdx;
+        flist[0] = 0;
+    }
+    __syncthreads();
+    const int64_t total = (int64_t)n_splits * k;
+    for (int64_t r0 = 0; r0 < total; r0 += ROUND) {
+        const int64_t p = r0 + tid;
+        if (p < total) {
+            const int64_t o = ((p / k) * B + b) * k + p % k;
+            const uint32_t key = part_key[o];
+            const int32_t idx = part_idx[o];
+            if (pair_before(key, idx, thk[0], thi[0])) {
+                const uint32_t pos = atomicAdd(&cnt[0], 1u);
+                bk[pos] = key;
+                bi[pos] = idx;
+            }
+        }
+        __syncthreads();
+        if (r0 + ROUND >= total || cnt[0] > (uint32_t)(CAPP - ROUND)) rank_compact<CAPP>(bk, bi, cnt, thk, thi, flist, 1, k);
+    }
+    for (int j = tid; j < k; j += 256) {
+        const bool has = j < (int)cnt[0];
+        out(b, j, has, bk[j], bi[j]);
+    }
 }
 
 // sums[s] += part[0][s] + part[1][s] + ..: one thread per slot, the workgroups' partials in ascending order

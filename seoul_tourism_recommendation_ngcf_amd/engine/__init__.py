@@ -6,14 +6,15 @@ the device: `_lib.load()` runs inside the calls.  Callers reach every name below
 the backward pass (csrc/bwd_dense.hip, csrc/bwd_gather.hip: `engine.backward.<name>`, and `engine.layers.bpr_backward` next to `bpr_loss`),
 the trip-context family (csrc/context.hip), the delimited-text family (csrc/text.hip), the optimizer step (csrc/adam.hip), the exact
 held-out positions (csrc/rank_position.hip), the hard and the popularity-weighted negatives (csrc/sample_hard.hip, csrc/sample_weighted.hip), the loss against m negatives per positive
-(csrc/bpr_multi.hip) and the beyond-accuracy list figures with the diversifying re-rank (csrc/list_quality.hip, csrc/list_rerank.hip) keep their modules' names: `engine.context.<name>`,
+(csrc/bpr_multi.hip), the beyond-accuracy list figures with the diversifying re-rank (csrc/list_quality.hip, csrc/list_rerank.hip) and the certified
+two-stage ranking (csrc/rank_prefilter.hip) keep their modules' names: `engine.context.<name>`,
 `engine.text.<name>`, `engine.optim.<name>`, `engine.ranks.<name>`, `engine.negatives.<name>`, `engine.losses.<name>`,
-`engine.lists.<name>`.
+`engine.lists.<name>`, `engine.shortlist.<name>`.
 """
 import ctypes as C  # noqa: F401  (NGCF.py builds its pointers with `engine.C`)
 
 from .. import _lib  # noqa: F401
-from . import backward, context, layers, lists, losses, negatives, optim, ranks, text  # noqa: F401
+from . import backward, context, layers, lists, losses, negatives, optim, ranks, shortlist, text  # noqa: F401
 from ._plumbing import Workspace, _device_view, _f32c, _on, _ptr, _require_device, _row_major_ld, _stream
 from .csr import LaplacianCSR, shard_plan
 from .groupby import (DECIMAL_MAX_CHARS, GROUPBY_FULL, GROUPBY_LDS_SLOTS, GROUPBY_LOST, GROUPBY_MAX_KEYS, GROUPBY_MAX_VALUES,

@@ -25,13 +25,20 @@ _Sets = Union["engine.ItemSets", tuple]
 
 
 def full_ranking(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0,
-                 users: Optional[torch.Tensor] = None, user_chunk: int = 65536) -> dict:
+                 users: Optional[torch.Tensor] = None, user_chunk: int = 65536, *, prefilter: Optional[str] = None,
+                 pool: Optional[int] = None) -> dict:
     """Metrics @K for every K in `ks` of a full ranking of `users` (default: all) by `model` (an NGCF), with the items of `train`
     excluded and `test` as the truth.  `train` / `test`: engine.ItemSets (e.g. `ItemSets.from_laplacian(model.laplacian_csr(y),
     n_user)` for the training graph) or (users, items[, weights]) pairs.  The embeddings come from `model.propagate(year_idx)` in
     eval mode under no_grad; the caller's train/eval mode is restored.  Users are ranked `user_chunk` at a time against strided
     views of all_E (no copies); the host reads back once.  Returns {"recall@K": .., "ndcg@K": .., "precision@K": .., "hr@K": ..,
-    "users": number of users with a non-empty test row}."""
+    "users": number of users with a non-empty test row}.
+    `prefilter="bf16"` ranks every chunk with `engine.shortlist.rank_topk_certified` (`pool`: its shortlist size) on an item table
+    packed once per call: the same top lists bit for bit, so the same dict, plus "certified", the share of the users whose
+    certificate held (the others were ranked again by `rank_topk`).  It adds ONE read-back per chunk (how many users fell back).
+    None is the fp32 path; any other string is a ValueError."""
+    if prefilter not in (None, "bf16"):
+        raise ValueError(f"full_ranking: prefilter={prefilter!r} is neither None nor 'bf16'")
     ks = [int(x) for x in ks]
     k = max(ks)
     with serving.inference(model):
@@ -40,13 +47,28 @@ def full_ranking(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), ye
         users = serving.ids_or_all(users, t.n_user, t.dev)
         sums = torch.zeros(4 * len(ks) + 1, dtype=torch.float64, device=t.dev)
         status = serving.status_word(t.dev)
+        if prefilter is not None:
+            packed = engine.shortlist.pack_items(t.I)
+            n_certified = torch.zeros((), dtype=torch.int64, device=t.dev)
         for sl in serving.chunks(users.numel(), user_chunk):
             ids = users[sl]
-            _, top = engine.rank_topk(t.U, t.I, k, user_ids=ids, exclude=excl, status=status)
+            if prefilter is None:
+                _, top = engine.rank_topk(t.U, t.I, k, user_ids=ids, exclude=excl, status=status)
+            else:
+                _, top, cert = engine.shortlist.rank_topk_certified(t.U, t.I, k, user_ids=ids, exclude=excl, status=status, packed=packed,
+                                                                    pool=pool, return_certified=True)
+                n_certified += cert.sum()
             engine.ranking_metrics(top, truth, ks, user_ids=ids, sums=sums, status=status)
-        if serving.read_back(status)[0] != 0:
+        if prefilter is None:
+            word, host = serving.read_back(status)[0], None
+        else:
+            word, host = serving.read_back(status, n_certified.reshape(1).to(torch.int32))
+        if word != 0:
             raise IndexError(f"full_ranking: a user id lies outside [0, {t.n_user})")
-        return engine.metrics_from_sums(sums, ks)
+        out = engine.metrics_from_sums(sums, ks)
+        if host is not None:
+            out["certified"] = int(host[0]) / max(int(users.numel()), 1)
+        return out
 
 
 def full_ranks(model, train: _Sets, test: _Sets, ks: Sequence[int] = (20,), year_idx: int = 0,
